@@ -9,10 +9,12 @@ receding-horizon MPC steps (update_time 0.1 s, ideal prediction, warm start).  O
 timed "step" = one MPC step of the whole batch: prediction + horizon bookkeeping +
 `omgx_batch_solve`, everything resident in HBM.  Solver tolerance = the
 reference's default `ipopt.tol = 1e-3` (`problems/problem.py:57`).  The cold-solve
-rate is reported alongside (`cold_solve`).
+rate is reported alongside with `--full` (`cold_solve`).
 
 Launch: python bench.py --gpus N --steps K --warmup W   (N>1 via torch.distributed.run)
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports them; `--full` adds
+the cold-solve co-headline, the closed-loop parity leg, the side legs, the sampling roofline and the CPU baseline.
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy.
 """
 import argparse
 import gc
@@ -59,6 +61,29 @@ def quiet_host():
     step with every change of the allocation history (first process on a box: no .pyc yet, another history, no pause)."""
     gc.collect()
     gc.disable()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=20240807):
+    """--dump-outputs: what the timed path handed its caller after its last timed step, one float64 `<name>.npy` per array
+    (rows = agents).  Above DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of agent rows is taken from every array and
+    its indices are written as `agent_index.npy`.  Called after the timed region: a device-to-host copy of each array."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64)
+    n_rows = min(a.shape[0] for a in host.values())
+    row_bytes = sum(a[0].nbytes for a in host.values())
+    if row_bytes * n_rows > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * n_rows) // row_bytes)
+        idx = np.sort(np.random.default_rng(seed).choice(n_rows, size=keep, replace=False))
+        host = dict((k, a[idx]) for k, a in host.items())
+        host['agent_index'] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def executed_flops_per_iter(tpl):
@@ -749,6 +774,9 @@ def bench_formation(args, rank, local_rank, world, dist, dev):
     elapsed = time.perf_counter() - t0
     gc.enable()
     solver.set_stats(None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, 'rank%d' % rank),
+                     dict(x=ops.x, p=ops.p, z_ij=ops.z_ij.reshape(hi - lo, -1), l_ij=ops.l_ij.reshape(hi - lo, -1), status=status))
     # where an update's time goes (a second, untimed pass with an event after every phase of the iteration: x-update,
     # centre, the two collectives, z / lambda update, read-back -- what a multi-GPU run needs to be diagnosable)
     ops.timeline = []
@@ -825,6 +853,9 @@ def bench_cold(args, rank, local_rank, world, dist, dev):
     elapsed = time.perf_counter() - t0
     kernel_ms = [elapsed / args.steps * 1e3]
     status, iters = mpc.status, mpc.iters
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, 'rank%d' % rank),
+                     dict((k, getattr(mpc, k)) for k in ('x', 'lam', 'p', 'status', 'iters')))
     n_ok = int((status == 0).sum().item())
     it_sum = int(iters.sum().item())
     elapsed, n_ok_all = reduce_report(elapsed, n_ok, device=dev, dist=dist)
@@ -888,10 +919,16 @@ def main():
     ap.add_argument('--tol', type=float, default=1e-3)
     ap.add_argument('--knot-intervals', type=int, default=11, help='(p2p workload; BASELINE configs[1]: 11)')
     ap.add_argument('--obstacles', type=int, default=3, help='(p2p workload; BASELINE configs[1]: 3)')
+    ap.add_argument('--full', action='store_true',
+                    help='p2p: besides the headline also the cold-solve co-headline, the closed-loop parity leg, the side legs '
+                         '(whole manoeuvre, tolerance curve, latency, host boundary, fused store, rollout, lifted class), the '
+                         'sampling roofline and the CPU baseline; without it a run measures the timed steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the timed path computed in its last step to DIR/<name>.npy (float64)')
     ap.add_argument('--cpu-seconds', type=float, default=12.0,
                     help='seconds of timed CPU work for the cpu_baseline leg (all host cores; a quarter of it on one)')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the latency / host-boundary / 8d-rule legs (profiling runs)')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the latency / host-boundary / 8d-rule legs (profiling runs)')
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak',
                     help="p2p workload at N > 1: weak = --agents per GPU (default), strong = --agents in total, sharded over the ranks "
                          "(BASELINE's metric as worded: the 1024-agent batch at 1/2/4/8 GPU)")
@@ -902,7 +939,7 @@ def main():
                     help="also test IPOPT's absolute tolerances on the unscaled problem at their documented defaults (compl_inf_tol = "
                          "constr_viol_tol = 1e-4, in force when the reference sets only ipopt.tol): omgx_options version 8")
     ap.add_argument('--refine', type=int, default=None, help='p2p: omgx_options.refine (default: the library default, 1); 0 switches the refinement of regularised steps off (A/B runs)')
-    ap.add_argument('--no-parity', action='store_true', help='skip the closed-loop parity leg (`parity_at_tol`: 26 launches of a 64-agent batch) -- profiling passes whose per-launch averages must cover the 1024-agent launches only')
+    ap.add_argument('--no-parity', action='store_true', help='with --full: skip the closed-loop parity leg (`parity_at_tol`: 26 launches of a 64-agent batch) -- profiling passes whose per-launch averages must cover the 1024-agent launches only')
     ap.add_argument('--sustained-steps', type=int, default=120, help='updates of the whole-manoeuvre leg (`sustained`)')
     ap.add_argument('--workload', choices=['p2p', 'formation', 'rendezvous', 'quadrotor', 'holonomic3d'], default='p2p',
                     help="p2p = BASELINE.json configs[1] (headline); formation = configs[3], 512-agent ADMM")
@@ -945,40 +982,42 @@ def main():
         opts.update(IPOPT_DEFAULT_TOLERANCES)
     if args.refine is not None:
         opts['refine'] = args.refine
-    # single-handle batch: the cold co-headline and the side legs (latency, fused store, rollout)
-    mpc = BatchP2P(problem, P, ops='hip', device=dev, options=opts)
-    solver = mpc.solver
 
     def barrier():
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- cold solve from the reference's initial guess (reported, not the headline) ----------
-    x0_init, p_init = mpc.x.clone(), mpc.p.clone()
-    cold_ms, cold_first_ms, cold_passes, cold_kernel_all = [], [], 0, []
-    solver.set_timing(True)
-    for rep in range(4):                    # (the first repetition is not counted: lazy loading of the small torch kernels)
-        mpc.x.copy_(x0_init)
-        mpc.p.copy_(p_init)
-        mpc.time = 0.0
-        # the whole cold solve between two events on the launch stream: the first pass over every agent and the
-        # restart passes for the (rare) agents whose phase I stalls from the reference's straight-line guess
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        mpc.solve_cold(bends=())
-        cold_first_ms.append(solver.last_kernel_ms())
-        cold_kernel_all.append(cold_first_ms[-1])
-        first_ok = int((mpc.status == 0).sum().item())
-        cold_passes = mpc.restart_failed()
-        b.record()
-        torch.cuda.synchronize()
-        cold_ms.append(a.elapsed_time(b))
-        if rep == 0:
-            cold_ms, cold_first_ms = [], []
-    cold_ok = int((mpc.status == 0).sum().item())
-    cold_iters = int(mpc.iters.sum().item())
-    solver.set_timing(False)
+    cold_kernel_all, cold_iters = [], 0
+    if args.full:
+        # single-handle batch: the cold co-headline and the side legs (latency, fused store, rollout)
+        mpc = BatchP2P(problem, P, ops='hip', device=dev, options=opts)
+        solver = mpc.solver
+        # ---- cold solve from the reference's initial guess (reported, not the headline) ----------
+        x0_init, p_init = mpc.x.clone(), mpc.p.clone()
+        cold_ms, cold_first_ms, cold_passes = [], [], 0
+        solver.set_timing(True)
+        for rep in range(4):                    # (the first repetition is not counted: lazy loading of the small torch kernels)
+            mpc.x.copy_(x0_init)
+            mpc.p.copy_(p_init)
+            mpc.time = 0.0
+            # the whole cold solve between two events on the launch stream: the first pass over every agent and the
+            # restart passes for the (rare) agents whose phase I stalls from the reference's straight-line guess
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            mpc.solve_cold(bends=())
+            cold_first_ms.append(solver.last_kernel_ms())
+            cold_kernel_all.append(cold_first_ms[-1])
+            first_ok = int((mpc.status == 0).sum().item())
+            cold_passes = mpc.restart_failed()
+            b.record()
+            torch.cuda.synchronize()
+            cold_ms.append(a.elapsed_time(b))
+            if rep == 0:
+                cold_ms, cold_first_ms = [], []
+        cold_ok = int((mpc.status == 0).sum().item())
+        cold_iters = int(mpc.iters.sum().item())
+        solver.set_timing(False)
     # ---- receding-horizon steps: SURVEY.md 8d protocol (cold solve, then warm-started steps) ----
     # THE PER-STEP PRODUCT PATH (`receding_horizon_batch`): one handle, or -- for a batch of at least two rounds of resident
     # workgroups, the headline's 1024 agents on 512 slots -- three stream-ordered sub-batch launches per step (round 5; per agent the
@@ -1035,6 +1074,10 @@ def main():
     stats = sum(sd.cpu().numpy() for sd in stats_d)   # rows: {solved, sum of iterations, agents}; the maximum separately
     stats[:, 2] = np.max([sd.cpu().numpy()[:, 2] for sd in stats_d], axis=0)
     assert (stats[:, 3] == B).all()
+    if args.dump_outputs:
+        # the plan, multipliers, parameters (predicted initial conditions, obstacles, time) and per-agent outcome of the last step
+        dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, 'rank%d' % rank),
+                     dict((k, getattr(rh, k)) for k in ('x', 'lam', 'p', 'status', 'iters')))
     # launch intervals on the device clock (ms since ev_base): what the solve kernels occupied the chip for is the UNION of
     # the intervals (the sub-batch launches of one step, and the next step of a sub-batch, overlap)
     spans = [[(ev_base.elapsed_time(a), ev_base.elapsed_time(b)) for a, b in row] for row in ev[W:]]
@@ -1064,7 +1107,6 @@ def main():
     flops_per_iter = n ** 3 / 3.0 + 2.0 * n ** 2          # dense-n LDL' + 2 solves
     achieved = (it_sum / n_meas) * flops_per_iter / (k_ms * 1e-3) / 1e12
     exec_flops = executed_flops_per_iter(tpl)
-    cold_k = float(np.mean(cold_ms))
     traffic, traffic_source = measured_traffic(B)
     n_total = args.agents if strong else B * world
     out = {
@@ -1088,19 +1130,7 @@ def main():
         'p50_batch_latency_ms': float(np.median(step_latency_ms)), 'max_batch_latency_ms': float(np.max(step_latency_ms)),
         'max_iters_in_a_step': int(stats[:, 2].max()), 'host_enqueue_ms_per_step': t_host / K * 1e3,
         'solved_fraction': n_ok / float(B), 'mean_iters': it_sum / float(n_meas * B),
-        # co-headline: the cold solve of the whole batch from the reference's initial guess (SURVEY 8d target
-        # >= 1e4 solves/s), with its own roofline object
-        'cold_solve': {'solves_per_s': cold_ok / (cold_k * 1e-3), 'kernel_ms': cold_k,
-                       'solved_fraction': cold_ok / float(B), 'mean_iters': cold_iters / float(B),
-                       'first_pass': {'kernel_ms': float(np.mean(cold_first_ms)), 'solved_fraction': first_ok / float(B)},
-                       'restart_passes': cold_passes,
-                       'roofline': {'bound': 'mfma', 'kernel': 'ipm_solve_kernel',
-                                    'achieved': cold_iters * flops_per_iter / (cold_k * 1e-3) / 1e12,
-                                    'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                                    'frac': cold_iters * flops_per_iter / (cold_k * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS,
-                                    'executed_TFLOPs': cold_iters * exec_flops / (cold_k * 1e-3) / 1e12,
-                                    'traffic': None, 'kernel_ms': cold_k}},
-        'lds_bytes_per_agent': solver.lds_bytes,
+        'lds_bytes_per_agent': (solver if args.full else parts[0].solver).lds_bytes,
         'roofline': {'bound': 'mfma', 'kernel': 'ipm_solve_kernel', 'achieved': achieved,
                      'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s',
                      'frac': achieved / FP64_MATRIX_PEAK_TFLOPS, 'traffic': traffic, 'traffic_source': traffic_source,
@@ -1124,6 +1154,22 @@ def main():
         rh.close()
     else:
         rh.solver.close()
+    if not args.full:
+        emit(out)
+        return
+    # co-headline: the cold solve of the whole batch from the reference's initial guess (SURVEY 8d target
+    # >= 1e4 solves/s), with its own roofline object
+    cold_k = float(np.mean(cold_ms))
+    out['cold_solve'] = {'solves_per_s': cold_ok / (cold_k * 1e-3), 'kernel_ms': cold_k,
+                         'solved_fraction': cold_ok / float(B), 'mean_iters': cold_iters / float(B),
+                         'first_pass': {'kernel_ms': float(np.mean(cold_first_ms)), 'solved_fraction': first_ok / float(B)},
+                         'restart_passes': cold_passes,
+                         'roofline': {'bound': 'mfma', 'kernel': 'ipm_solve_kernel',
+                                      'achieved': cold_iters * flops_per_iter / (cold_k * 1e-3) / 1e12,
+                                      'peak': FP64_MATRIX_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                                      'frac': cold_iters * flops_per_iter / (cold_k * 1e-3) / 1e12 / FP64_MATRIX_PEAK_TFLOPS,
+                                      'executed_TFLOPs': cold_iters * exec_flops / (cold_k * 1e-3) / 1e12,
+                                      'traffic': None, 'kernel_ms': cold_k}}
     if world == 1 and not args.no_parity:
         # the accuracy the solver settings of `value` buy: closed loop against an independent solver in the loop (64 agents, 25 updates)
         try:

@@ -1,13 +1,14 @@
 #!/bin/bash
 # same-box A/B of library builds on the default bench: bash tools/gpu_ab.sh name1 name2 ... (tools/scratch/ab/libomgx_<name>.so; "cur" = the tree's)
-cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/ab
-AB=$GRAFT_REPO_ROOT/tools/scratch/ab
+R=$(cd "$(dirname "$0")/.." && pwd)
+cd "$R"
+mkdir -p out/ab
+AB=$R/tools/scratch/ab
 for rep in 1 2; do
 for v in "$@"; do
-  L=$AB/libomgx_$v.so; [ $v = cur ] && L=$GRAFT_REPO_ROOT/omg-tools_amd/csrc/libomgx.so
-  OMGX_LIB=$L timeout 300 python bench.py --no-cpu --no-extras > gpurun_out/ab/p2p_${v}_$rep.json 2> gpurun_out/ab/p2p_${v}_$rep.err
-  python - gpurun_out/ab/p2p_${v}_$rep.json <<'PY'
+  L=$AB/libomgx_$v.so; [ $v = cur ] && L=$R/omg-tools_amd/csrc/libomgx.so
+  OMGX_LIB=$L timeout 300 python bench.py --full --no-cpu --no-extras > out/ab/p2p_${v}_$rep.json 2> out/ab/p2p_${v}_$rep.err
+  python - out/ab/p2p_${v}_$rep.json <<'PY'
 import json, sys
 try:
     e = json.load(open(sys.argv[1]))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Condense rocprofv3 output directories (gpurun_out/prof/{stats,fetch,write}) into the small
+"""Condense rocprofv3 output directories (out/prof/{stats,fetch,write}, written by tools/run_profiles.sh) into the small
 files committed under profiles/.  Usage: python tools/profile_summary.py <round-tag>"""
 import csv
 import glob
@@ -8,8 +8,8 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_COLD = 5      # bench.py --streams 1: four timed cold solves of the side-leg handle + the cold solve of the headline's own handle
-PROF = os.path.join(ROOT, 'gpurun_out', 'prof')
+N_COLD = 5      # bench.py --full --streams 1: four timed cold solves of the side-leg handle + the cold solve of the headline's own handle
+PROF = os.path.join(ROOT, 'out', 'prof')
 
 
 def newest(pattern):
@@ -33,8 +33,8 @@ def pmc(name):
 
 
 def issue_passes(tag, out, n_cold=N_COLD):
-    """Instruction-fetch / issue decomposition (round 5): every counter of the passes gpurun_out/prof/issue*/, mean per launch
-    of ipm_solve_kernel, cold launches (the first `n_cold`: bench.py --streams 1 solves the batch cold five times) and
+    """Instruction-fetch / issue decomposition (round 5): every counter of the passes out/prof/issue*/, mean per launch
+    of ipm_solve_kernel, cold launches (the first `n_cold`: bench.py --full --streams 1 solves the batch cold five times) and
     receding-horizon steps apart, plus the ratios that decompose the wave-wait share."""
     res = {}
     for d in sorted(glob.glob(os.path.join(PROF, 'issue*'))):
@@ -65,7 +65,7 @@ def issue_passes(tag, out, n_cold=N_COLD):
         der['ifetch_per_wave_cycle_' + s_] = ratio('SQ_IFETCH', 'SQ_WAVE_CYCLES', k)
         der['salu_cycles_over_wave_cycles_' + s_] = ratio('SQ_INST_CYCLES_SALU', 'SQ_WAVE_CYCLES', k)
     res['derived'] = der
-    res['note'] = ('separate rocprofv3 --pmc passes (counters only, no trace domain) of `python bench.py --streams 1 --no-cpu '
+    res['note'] = ('separate rocprofv3 --pmc passes (counters only, no trace domain) of `python bench.py --full --streams 1 --no-cpu '
                    '--no-extras --steps 5 --warmup 1`: launches 0-%d are cold solves of the 1024-agent batch, the rest '
                    'receding-horizon steps; counters the box does not know are absent' % (n_cold - 1))
     json.dump(res, open(os.path.join(out, '%s_pmc_issue.json' % tag), 'w'), indent=1)
@@ -89,7 +89,7 @@ def main():
     hbm = (fetch['mean_kb_per_launch'] + write['mean_kb_per_launch']) * 1024.0
     json.dump({'FETCH_SIZE': fetch, 'WRITE_SIZE': write, 'hbm_bytes_per_launch': hbm, 'cold_launches': N_COLD, 'launches_per_step': 1,
                'note': 'rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes '
-                       '(python bench.py --streams 1 --no-cpu --no-extras --steps 5 --warmup 1: 5 cold solves of the 1024-agent batch + 6 '
+                       '(python bench.py --full --streams 1 --no-cpu --no-extras --steps 5 --warmup 1: 5 cold solves of the 1024-agent batch + 6 '
                        'receding-horizon steps, one launch per step), kernel ipm_solve_kernel (the instance of the workspace mode, see VGPR / LDS / workgroup columns), 1024 agents; counter unit KB; mean over those launches.'},
               open(os.path.join(out, '%s_pmc_hbm.json' % tag), 'w'), indent=1)
     # further counter passes: mean per launch of every counter, cold launches (the first 4) and warm ones apart
@@ -105,7 +105,7 @@ def main():
     for k in ('mean_cold', 'mean_warm'):
         mf['mfma_busy_over_cu_busy_' + k[5:]] = mf['SQ_VALU_MFMA_BUSY_CYCLES'][k] / max(1.0, mf['SQ_BUSY_CU_CYCLES'][k])
     mf['note'] = ('rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 -- python bench.py '
-                  '--streams 1 --no-cpu --no-extras --steps 5 --warmup 1; launches 0-4 are the cold solves of the batch, the rest '
+                  '--full --streams 1 --no-cpu --no-extras --steps 5 --warmup 1; launches 0-4 are the cold solves of the batch, the rest '
                   'receding-horizon steps; 1024 agents')
     json.dump(mf, open(os.path.join(out, '%s_pmc_mfma.json' % tag), 'w'), indent=1)
     lw = multi('lds', ['SQ_LDS_BANK_CONFLICT', 'SQ_LDS_IDX_ACTIVE', 'SQ_INSTS_LDS'])

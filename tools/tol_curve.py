@@ -4,7 +4,7 @@ knot crossings) and -- on a GPU -- the bench's headline protocol at that toleran
 
   python tools/tol_curve.py cpu             host build of the kernel source (oracle/port): the accuracy column only (the HIP path
                                             gives the same digits, tests/test_closed_loop.py)
-  python tools/tol_curve.py gpu [outfile]   HIP path: accuracy + `python bench.py --tol X --no-cpu --no-extras` per tolerance
+  python tools/tol_curve.py gpu [outfile]   HIP path: accuracy + `python bench.py --full --tol X --no-cpu --no-extras` per tolerance
 """
 import json
 import os
@@ -80,7 +80,7 @@ def main():
         row = accuracy(make, tol)
         made[-1].solver.close()
         for form, extra in (('three_streams', []), ('one_launch', ['--streams', '1'])):
-            out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--tol', repr(tol), '--no-cpu', '--no-extras'] + extra,
+            out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--tol', repr(tol), '--no-cpu', '--no-extras'] + extra,
                                  capture_output=True, text=True)
             try:
                 d = json.loads(out.stdout.strip().splitlines()[-1])
