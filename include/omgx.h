@@ -404,7 +404,8 @@ int  omgx_batch_predict_quadrotor(omgx_batch* b, const double* x, double* p, int
  * in place (device pointers: OMGX_PTR_DEVICE | OMGX_BOUNDS_DEVICE required; OMGX_BOUNDS_SHARED as for omgx_batch_solve);
  * the handle's options apply (warm_start = 1 expected), cross_options (optional) to the solves right after a crossing.
  * With omgx_batch_set_stats step k of the call fills the next free row; with omgx_batch_set_store every step writes the
- * agent's sampled trajectories as a single solve would (the last step's stay).  iters_log / status_log (optional, device,
+ * agent's sampled trajectories as a single solve would (the last step's stay), with omgx_batch_set_signals every step appends its
+ * travelled samples to the log (all of them stay).  iters_log / status_log (optional, device,
  * [n_steps][n_agents]) keep the per-step values.  Templates of the wave path without two-sided rows only (config 1 / 2
  * class, ADMM x-update templates); others return OMGX_E_INVALID -- step with omgx_batch_solve.  Host arrays are read
  * during the call. */
@@ -447,6 +448,41 @@ typedef struct omgx_store_spec {
 } omgx_store_spec;
 int  omgx_batch_store(omgx_batch* b, const double* x, const omgx_store_spec* sp);
 int  omgx_batch_set_store(omgx_batch* b, const omgx_store_spec* sp);
+
+/* (OMGX_HAS_SIGNALS) The travelled trajectories: what `Simulator.run` returns as `vehicle.signals` -- state, input, dinput the
+ * vehicle went through, sample by sample, from the first update to arrival.  `Vehicle.simulate` with `ideal_update` (reference
+ * `vehicles/vehicle.py:359-369`) appends samples 1 .. n_samp of every fresh plan, ahead of the first also sample 0
+ * (`trajectories[:, 0]`); one append for agent b, whose plan was solved at t_rel = p[b, p_t] (time since the last knot):
+ *   count[b] == 0:  log[b, o, k, 0] = d^o/dt^o spline_k at u = t_rel * inv_T                           (the first call only)
+ *   log[b, o, k, c0 + i - 1] = d^o/dt^o spline_k at u = (t_rel + i sample_time) * inv_T,  i = 1 .. n_samp  (c0 = count[b], or 1)
+ *   count[b] += n_samp (+ 1 with column 0)
+ * o < n_der: state, input, dinput (time derivatives: spline-domain derivatives * inv_T^o, as omgx_batch_store).  An append that
+ * does not fit in cap columns writes nothing, leaves count[b] and sets overflow[b] = 1.  The caller zeroes count and overflow.
+ * n_samp = int(round(update_time / sample_time, 6)).  Limits: those of omgx_batch_store.
+ * omgx_batch_set_signals: every following omgx_batch_solve AND every step of omgx_batch_rollout appends for the agents it
+ * solved, inside the kernel (the solution is still in LDS there) -- an agent the stop rule has stopped (omgx_batch_set_stop) or
+ * an OMGX_ONLY_FAILED pass skips is not appended, an agent whose solve ended with another status than Solve_Succeeded is (the
+ * loop carries on with that x, and so does the reference's); sp == NULL switches it off.  Independent of omgx_batch_set_store:
+ * both may be on.  The solves themselves are the same bits with the log on or off.  omgx_batch_signals_append: the same
+ * routine for a given x, p (device), one launch on the handle's stream; under_way (optional, [n_agents] int32 device): agents
+ * with 0 are skipped.  The three callers write the same bits.  The arrays a spec points at must stay valid while it is set. */
+#define OMGX_HAS_SIGNALS 1
+typedef struct omgx_signals_spec {
+  double*  log;            /* [B, n_der, n_spl, cap] device */
+  int32_t* count;          /* [B] device, in/out */
+  int32_t* overflow;       /* [B] device, or NULL */
+  const double* knots;     /* [n_knots] host, n_knots <= 40 */
+  int32_t coeff_off, n_spl, degree, n_knots, n_der, n_samp, cap, p_t;
+  double  sample_time, inv_T;
+} omgx_signals_spec;
+int  omgx_batch_set_signals(omgx_batch* b, const omgx_signals_spec* sp);
+int  omgx_batch_signals_append(omgx_batch* b, const double* x, const double* p, const int32_t* under_way,
+                               const omgx_signals_spec* sp);
+/* What `problem.final()` reports per vehicle, from the log: target [B, n_spl] (device), summary [B, 8] (device) =
+ * {columns, motion time (columns - 1) * sample_time, path length sum |state_c - state_{c-1}|, largest |input|, largest |dinput|
+ * (0 when n_der < 3), |state_last - target|, |input_last|, 0 (reserved)}; Euclidean norms over the n_spl splines, summed in a
+ * fixed order (the same bits in every run). */
+int  omgx_batch_signals_reduce(omgx_batch* b, const omgx_signals_spec* sp, const double* target, double* summary);
 
 /* Same shift on any device-resident row-major array (stride doubles per row, n_rows rows):
  * used for the ADMM consensus state on a knot crossing (`problems/admm.py:477-491`).

@@ -78,6 +78,21 @@ struct StoreArgs {
   double dt, inv_T;
   KnotArg knots;
 };
+// The travelled trajectories (omgx_batch_set_signals): what `Vehicle.simulate` with `ideal_update` appends to `vehicle.signals`
+// after every update (reference `vehicles/vehicle.py:359-369`) -- samples 1 .. n_samp of the fresh plan, ahead of the first
+// update's also sample 0.  log [B, n_der, n_spl, cap]: order o = time-derivative order of spline k (state, input, dinput),
+// scaled by inv_T^o as in sample_agent; count [B]: columns written so far; overflow [B] (or nullptr): 1 = an append did not fit.
+struct SignalArgs {
+  double* log;
+  int32_t* count;
+  int32_t* overflow;
+  int coeff_off, n_spl, degree, n_knots, n_der, n_samp, cap, p_t;
+  double sample_time, inv_T;
+  KnotArg knots;
+};
+// What the `stp` argument of the solve and rollout kernels points at in device memory: the fused store and, right behind it, the
+// fused log (st.out == nullptr / sg.log == nullptr: that part is off; the pointer itself is null when both are)
+struct StoreBlock { StoreArgs st; SignalArgs sg; };
 
 __host__ __device__ inline size_t sample_scratch_doubles(int n_spl, int degree, int n_knots, int n_der) {
   const int L = n_knots - degree - 1, n_span = n_knots - 2 * degree - 1, D1 = degree + 1;
@@ -169,6 +184,96 @@ __device__ void sample_agent(const double* coeffs, double* scratch, int n_spl, i
       }
     }
     if (vtot_b) vtot_b[i] = (OutT)sqrt(v2);
+  }
+}
+
+// One append of the travelled-trajectory log for agent b by the whole workgroup: the batched twin of `Vehicle.simulate` with
+// `ideal_update` (reference `vehicles/vehicle.py:359-369`).  coeffs: the plan just solved ([n_spl][L], global memory or LDS),
+// t_rel: the time since the last knot it was solved at (p[p_t]), scratch: sample_scratch_doubles() doubles.  Column 0 (the
+// plan at t_rel, `trajectories[:, 0]`) goes ahead of the first append; then the n_samp columns at t_rel + i sample_time,
+// i = 1 .. n_samp.  An append that does not fit writes nothing but overflow[b] = 1.  The one routine behind
+// signals_append_kernel, the epilogue of the solve kernel and the step loop of the rollout kernel: sample_agent's arithmetic
+// per column does not depend on the workgroup size, so the three write the same bits.  Barriers inside: every thread of the
+// workgroup calls it, with the same arguments.
+__device__ __noinline__ void signals_append_agent(const SignalArgs& sg, int b, const double* coeffs, double t_rel, double* scratch) {
+  __syncthreads();      // (the scratch may still be read by the fused store; every thread reads count[b] before thread 0 moves it)
+  const int cnt = sg.count[b];
+  const int first = cnt == 0 ? 0 : 1;
+  const int n_col = sg.n_samp + 1 - first;
+  if (cnt < 0 || cnt > sg.cap - n_col) {      // (the same branch in every thread)
+    if (threadIdx.x == 0 && sg.overflow) sg.overflow[b] = 1;
+    return;
+  }
+  // sample i of the plan -> column cnt - first + i of the agent's block: rows of `cap` columns, i = first .. n_samp
+  sample_agent<double>(coeffs, scratch, sg.n_spl, sg.degree, sg.knots, sg.n_knots, sg.n_der, t_rel * sg.inv_T, sg.sample_time * sg.inv_T,
+                       sg.inv_T, sg.cap, first, sg.n_samp + 1, sg.log + (size_t)b * sg.n_der * sg.n_spl * sg.cap + (cnt - first),
+                       (double*)nullptr);
+  __syncthreads();
+  if (threadIdx.x == 0) sg.count[b] = cnt + n_col;
+}
+
+// stand-alone append for a given x, p (omgx_batch_signals_append): one workgroup per agent; under_way (optional): agents whose
+// loop the stop rule has ended are not appended
+__global__ void __launch_bounds__(256)
+signals_append_kernel(const double* __restrict__ x, int n_var, const double* __restrict__ p, int n_par,
+                      const int32_t* __restrict__ under_way, SignalArgs sg) {
+  extern __shared__ __align__(16) double lds[];
+  const int b = blockIdx.x;
+  if (under_way && under_way[b] == 0) return;
+  signals_append_agent(sg, b, x + (size_t)b * n_var + sg.coeff_off, p[(size_t)b * n_par + sg.p_t], lds);
+}
+
+// What `problem.final()` reports per vehicle, from the log (omgx_batch_signals_reduce): one wave per agent.  summary[b] =
+// {columns, motion time, path length, largest |input|, largest |dinput|, |state_last - target|, |input_last|, 0}; Euclidean norms
+// over the n_spl splines, each square and each sum rounded on its own (no fused multiply-add: a host check in plain numpy
+// statements gets the same bits).  Lane l takes the columns l, l + 64, ... in order and the lanes are combined by a fixed
+// butterfly: the same result in every run.
+__global__ void __launch_bounds__(64)
+signals_reduce_kernel(const double* __restrict__ log, const int32_t* __restrict__ count, const double* __restrict__ target,
+                      double* __restrict__ summary, int n_der, int n_spl, int cap, double sample_time) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int n = count[b];
+  n = n < 0 ? 0 : (n > cap ? cap : n);
+  const double* lg = log + (size_t)b * n_der * n_spl * cap;
+  double path = 0.0, vmax = 0.0, amax = 0.0;
+  for (int c = lane; c < n; c += 64) {
+    if (c >= 1) {
+      double s2 = 0.0;
+      for (int k = 0; k < n_spl; ++k) { const double dd = lg[(size_t)k * cap + c] - lg[(size_t)k * cap + c - 1]; s2 = s2 + dd * dd; }
+      path = path + sqrt(s2);
+    }
+    if (n_der >= 2) {
+      double s2 = 0.0;
+      for (int k = 0; k < n_spl; ++k) { const double v = lg[((size_t)n_spl + k) * cap + c]; s2 = s2 + v * v; }
+      vmax = fmax(vmax, sqrt(s2));
+    }
+    if (n_der >= 3) {
+      double s2 = 0.0;
+      for (int k = 0; k < n_spl; ++k) { const double v = lg[((size_t)2 * n_spl + k) * cap + c]; s2 = s2 + v * v; }
+      amax = fmax(amax, sqrt(s2));
+    }
+  }
+  for (int m = 32; m >= 1; m >>= 1) {
+    path = path + __shfl_xor(path, m, 64);
+    vmax = fmax(vmax, __shfl_xor(vmax, m, 64));
+    amax = fmax(amax, __shfl_xor(amax, m, 64));
+  }
+  if (lane == 0) {
+    double dist = 0.0, vlast = 0.0;
+    if (n >= 1) {
+      double s2 = 0.0;
+      for (int k = 0; k < n_spl; ++k) { const double dd = lg[(size_t)k * cap + n - 1] - target[(size_t)b * n_spl + k]; s2 = s2 + dd * dd; }
+      dist = sqrt(s2);
+      if (n_der >= 2) {
+        s2 = 0.0;
+        for (int k = 0; k < n_spl; ++k) { const double v = lg[((size_t)n_spl + k) * cap + n - 1]; s2 = s2 + v * v; }
+        vlast = sqrt(s2);
+      }
+    }
+    double* sm = summary + (size_t)b * 8;
+    sm[0] = (double)n; sm[1] = n >= 1 ? (n - 1) * sample_time : 0.0; sm[2] = path; sm[3] = vmax; sm[4] = amax;
+    sm[5] = dist; sm[6] = vlast; sm[7] = 0.0;
   }
 }
 
@@ -303,10 +408,15 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
       // (the specification sits in device memory: as a by-value kernel argument its 90 dwords would be kept in
       // scalar registers across the whole solve)
       const StoreArgs st = *stp;
-      __syncthreads();
-      sample_agent<double>(w.x + st.coeff_off, w.kkt, st.n_spl, st.degree, st.knots, st.n_knots, st.n_der, st.t0[b],
-                           st.dt, st.inv_T, st.n_samp, 0, st.n_samp, st.out + (size_t)b * st.n_der * st.n_spl * st.n_samp,
-                           st.v_tot ? st.v_tot + (size_t)b * st.n_samp : nullptr);
+      if (st.out) {
+        __syncthreads();
+        sample_agent<double>(w.x + st.coeff_off, w.kkt, st.n_spl, st.degree, st.knots, st.n_knots, st.n_der, st.t0[b],
+                             st.dt, st.inv_T, st.n_samp, 0, st.n_samp, st.out + (size_t)b * st.n_der * st.n_spl * st.n_samp,
+                             st.v_tot ? st.v_tot + (size_t)b * st.n_samp : nullptr);
+      }
+      // the travelled trajectory of this update (omgx_batch_set_signals): the specification sits behind the store's
+      const SignalArgs& sg = reinterpret_cast<const StoreBlock*>(stp)->sg;
+      if (sg.log) signals_append_agent(sg, b, w.x + sg.coeff_off, p[(size_t)b * d.n_par + sg.p_t], w.kkt);
       if (prep) { __syncthreads(); omgx::Kkt K0; K0.bind(d, T, w.kkt); omgx::kkt_describe(c, d, K0, w, true); }      // (the scratch may have reached the descriptors)
     }
 #ifdef OMGX_PROFILE
@@ -813,10 +923,15 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
       }
       if (stp) {      // `Vehicle.store` of this step (omgx_batch_set_store), as in the solve kernel's epilogue
         const StoreArgs st2 = *stp;
-        __syncthreads();
-        sample_agent<double>(w.x + st2.coeff_off, w.kkt, st2.n_spl, st2.degree, st2.knots, st2.n_knots, st2.n_der, st2.t0[b],
-                             st2.dt, st2.inv_T, st2.n_samp, 0, st2.n_samp, st2.out + (size_t)b * st2.n_der * st2.n_spl * st2.n_samp,
-                             st2.v_tot ? st2.v_tot + (size_t)b * st2.n_samp : nullptr);
+        if (st2.out) {
+          __syncthreads();
+          sample_agent<double>(w.x + st2.coeff_off, w.kkt, st2.n_spl, st2.degree, st2.knots, st2.n_knots, st2.n_der, st2.t0[b],
+                               st2.dt, st2.inv_T, st2.n_samp, 0, st2.n_samp, st2.out + (size_t)b * st2.n_der * st2.n_spl * st2.n_samp,
+                               st2.v_tot ? st2.v_tot + (size_t)b * st2.n_samp : nullptr);
+        }
+        // the travelled trajectory of this step (omgx_batch_set_signals): every update of the manoeuvre is logged inside the launch
+        const SignalArgs& sg = reinterpret_cast<const StoreBlock*>(stp)->sg;
+        if (sg.log) signals_append_agent(sg, b, w.x + sg.coeff_off, pb[sg.p_t], w.kkt);
       }
       __syncthreads();
     }
@@ -986,7 +1101,9 @@ struct omgx_batch {
   int64_t* d_stats = nullptr;       // optional [stats_slots][4] launch statistics (device, owned by the caller)
   int stats_slots = 0; long long stats_launch = 0;
   StoreArgs store = {};             // trajectories written by the solve kernel (omgx_batch_set_store); out == nullptr: off
-  StoreArgs* d_store = nullptr;     // its copy in device memory (what the kernel reads)
+  SignalArgs signals = {};          // travelled trajectories appended by the solve and rollout kernels (omgx_batch_set_signals); log == nullptr: off
+  StoreBlock store_host = {};       // the two as the kernels read them ...
+  StoreBlock* d_store = nullptr;    // ... and their copy in device memory
   RolloutArgs* d_rollout = nullptr; RolloutStep* d_ro_steps = nullptr; int ro_steps_cap = 0; int32_t* d_ro_perm = nullptr;      // omgx_batch_rollout
   std::vector<int32_t> ro_perm_host;
   StopArgs* d_stop = nullptr;       // omgx_batch_set_stop: device copy of the arguments
@@ -1793,7 +1910,7 @@ int omgx_batch_solve(omgx_batch* b, const double* p, const double* x0, const dou
   hipExtLaunchKernelGGL(ipm_kernel_for(b->ws_mode, b->dims.wave_ok, b->dims.general, b->opts.refine), dim3(b->n_slabs), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream,
                         e0, e1, 0u, d, b->dev,
                         b->opts, b->kkt_doubles, kp, kx0, klb, kub, shared ? 1 : 0, kx, klam, kst, kit, B, b->d_prof,
-                        b->d_slabs, b->slab_doubles, b->d_dw, b->d_order, (const StoreArgs*)(b->store.out ? b->d_store : nullptr), (flags & OMGX_ONLY_FAILED) ? 1 : 0,
+                        b->d_slabs, b->slab_doubles, b->d_dw, b->d_order, (const StoreArgs*)((b->store.out || b->signals.log) ? &b->d_store->st : nullptr), (flags & OMGX_ONLY_FAILED) ? 1 : 0,
                         b->d_next, b->d_x0_alt, b->d_x0_alt ? b->n_alt : 0, b->d_attempts,
                         (unsigned long long*)(b->d_stats ? b->d_stats + 4 * (size_t)(b->stats_launch++ % b->stats_slots) : nullptr),
                         b->stagger, (const CenterArgs*)(b->center_on ? b->d_center : nullptr),
@@ -2103,9 +2220,101 @@ int omgx_batch_store(omgx_batch* b, const double* x, const omgx_store_spec* sp) 
   return OMGX_OK;
 }
 
+namespace {
+// the fused store and the fused log travel in one block of device memory (the kernels' `stp`): uploaded on the handle's stream,
+// ordered behind the launches that still read the previous one (pageable source: staged before the call returns)
+int upload_store_block(omgx_batch* b) {
+  HIPCHK(hipSetDevice(b->device));
+  if (!b->d_store) HIPCHK(hipMalloc((void**)&b->d_store, sizeof(StoreBlock)));
+  b->store_host.st = b->store; b->store_host.sg = b->signals;
+  HIPCHK(hipMemcpyAsync(b->d_store, &b->store_host, sizeof(StoreBlock), hipMemcpyHostToDevice, b->stream));
+  return OMGX_OK;
+}
+
+// the part of a log specification that can be judged without a handle
+int check_signals_spec(const omgx_signals_spec* sp) {
+  char buf[200];
+  if (!sp->log || !sp->count || !sp->knots) { g_err = "signals: null log / count / knots"; return OMGX_E_INVALID; }
+  if (sp->degree < 1 || sp->degree > 5) { g_err = "signals: degree outside 1 .. 5"; return OMGX_E_INVALID; }
+  if (sp->n_knots > 40 || sp->n_knots < 2 * sp->degree + 2) {
+    snprintf(buf, sizeof buf, "signals: n_knots = %d outside %d .. 40", sp->n_knots, 2 * sp->degree + 2);
+    g_err = buf; return OMGX_E_INVALID;
+  }
+  if (sp->n_der < 1 || sp->n_der > sp->degree + 1) {
+    snprintf(buf, sizeof buf, "signals: n_der = %d outside 1 .. degree + 1 = %d", sp->n_der, sp->degree + 1);
+    g_err = buf; return OMGX_E_INVALID;
+  }
+  if (sp->n_spl <= 0 || sp->n_samp <= 0 || !(sp->sample_time > 0.0) || !(sp->inv_T > 0.0)) {
+    g_err = "signals: n_spl, n_samp, sample_time and inv_T must be positive"; return OMGX_E_INVALID;
+  }
+  if (sp->cap < sp->n_samp + 1) {
+    snprintf(buf, sizeof buf, "signals: cap = %d holds less than the first append (n_samp + 1 = %d columns)", sp->cap, sp->n_samp + 1);
+    g_err = buf; return OMGX_E_INVALID;
+  }
+  if (sp->p_t < 0 || sp->coeff_off < 0) { g_err = "signals: p_t / coeff_off out of range"; return OMGX_E_INVALID; }
+  return OMGX_OK;
+}
+
+int fill_signals(omgx_batch* b, const omgx_signals_spec* sp, SignalArgs* sg) {
+  if (!sp) { g_err = "null argument"; return OMGX_E_INVALID; }
+  const int rc = check_signals_spec(sp);
+  if (rc != OMGX_OK) return rc;
+  if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
+  const int L = sp->n_knots - sp->degree - 1;
+  if (sp->coeff_off + sp->n_spl * L > b->dims.n_var) { g_err = "signals: coefficients outside x"; return OMGX_E_INVALID; }
+  if (sp->p_t >= b->dims.n_par) { g_err = "signals: p_t out of range"; return OMGX_E_INVALID; }
+  sg->log = sp->log; sg->count = sp->count; sg->overflow = sp->overflow;
+  sg->coeff_off = sp->coeff_off; sg->n_spl = sp->n_spl; sg->degree = sp->degree; sg->n_knots = sp->n_knots; sg->n_der = sp->n_der;
+  sg->n_samp = sp->n_samp; sg->cap = sp->cap; sg->p_t = sp->p_t; sg->sample_time = sp->sample_time; sg->inv_T = sp->inv_T;
+  for (int i = 0; i < 40; ++i) sg->knots.k[i] = i < sp->n_knots ? sp->knots[i] : 0.0;
+  return OMGX_OK;
+}
+}  // namespace
+
+int omgx_batch_set_signals(omgx_batch* b, const omgx_signals_spec* sp) {
+  if (!sp) {
+    if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
+    b->signals = SignalArgs{};
+    return b->store.out ? upload_store_block(b) : OMGX_OK;
+  }
+  SignalArgs sg;
+  const int rc = fill_signals(b, sp, &sg);
+  if (rc != OMGX_OK) return rc;
+  if (sample_scratch_doubles(sg.n_spl, sg.degree, sg.n_knots, sg.n_der) > (size_t)b->kkt_doubles) {
+    g_err = "signals: the per-agent scratch does not fit the KKT store"; return OMGX_E_TOOLARGE;
+  }
+  b->signals = sg;
+  return upload_store_block(b);
+}
+
+int omgx_batch_signals_append(omgx_batch* b, const double* x, const double* p, const int32_t* under_way, const omgx_signals_spec* sp) {
+  SignalArgs sg;
+  const int rc = fill_signals(b, sp, &sg);
+  if (rc != OMGX_OK) return rc;
+  if (!x || !p) { g_err = "null argument"; return OMGX_E_INVALID; }
+  HIPCHK(hipSetDevice(b->device));
+  const size_t lds = sample_scratch_doubles(sg.n_spl, sg.degree, sg.n_knots, sg.n_der) * sizeof(double);
+  if (lds > 64 * 1024) { g_err = "signals: the per-agent scratch exceeds 64 KiB of LDS"; return OMGX_E_TOOLARGE; }
+  hipLaunchKernelGGL(signals_append_kernel, dim3(b->n_agents), dim3(256), lds, b->stream, x, b->dims.n_var, p, b->dims.n_par, under_way, sg);
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
+int omgx_batch_signals_reduce(omgx_batch* b, const omgx_signals_spec* sp, const double* target, double* summary) {
+  SignalArgs sg;
+  const int rc = fill_signals(b, sp, &sg);
+  if (rc != OMGX_OK) return rc;
+  if (!target || !summary) { g_err = "null argument"; return OMGX_E_INVALID; }
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(signals_reduce_kernel, dim3(b->n_agents), dim3(64), 0, b->stream, (const double*)sg.log, (const int32_t*)sg.count, target,
+                     summary, sg.n_der, sg.n_spl, sg.cap, sg.sample_time);
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
 int omgx_batch_set_store(omgx_batch* b, const omgx_store_spec* sp) {
   if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
-  if (!sp) { b->store = StoreArgs{}; return OMGX_OK; }
+  if (!sp) { b->store = StoreArgs{}; return b->signals.log ? upload_store_block(b) : OMGX_OK; }
   HIPCHK(hipSetDevice(b->device));
   StoreArgs st;
   int rc = fill_store(b, sp, &st);
@@ -2113,10 +2322,8 @@ int omgx_batch_set_store(omgx_batch* b, const omgx_store_spec* sp) {
   if (sample_scratch_doubles(st.n_spl, st.degree, st.n_knots, st.n_der) > (size_t)b->kkt_doubles) {
     g_err = "store: the per-agent scratch does not fit the KKT store"; return OMGX_E_TOOLARGE;
   }
-  if (!b->d_store) HIPCHK(hipMalloc((void**)&b->d_store, sizeof(StoreArgs)));
   b->store = st;
-  HIPCHK(hipMemcpyAsync(b->d_store, &b->store, sizeof(StoreArgs), hipMemcpyHostToDevice, b->stream));
-  return OMGX_OK;
+  return upload_store_block(b);
 }
 
 int omgx_batch_predict_quadrotor(omgx_batch* b, const double* x, double* p, int32_t coeff_off, int32_t degree, const double* knots,
@@ -2233,7 +2440,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   hipExtLaunchKernelGGL(kern, dim3(b->n_slabs < b->n_agents ? b->n_slabs : b->n_agents), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream, e0, e1, 0u,
                         d, b->dev, b->opts, b->kkt_doubles, p, x, lbg, ubg, shared ? 1 : 0, lam_g, status, iters, b->n_agents,
                         b->d_slabs, b->slab_doubles, b->d_dw, b->d_next, (const RolloutArgs*)b->d_rollout, b->stagger, b->d_order,
-                        (const StoreArgs*)(b->store.out ? b->d_store : nullptr));
+                        (const StoreArgs*)((b->store.out || b->signals.log) ? &b->d_store->st : nullptr));
   HIPCHK(hipGetLastError());
   return OMGX_OK;
 }

@@ -191,6 +191,14 @@ class CStoreSpec(C.Structure):
                 ('n_der', C.c_int32), ('n_samp', C.c_int32), ('dt', C.c_double), ('inv_T', C.c_double)]
 
 
+class CSignalsSpec(C.Structure):
+    """include/omgx.h omgx_signals_spec"""
+    _fields_ = [('log', C.c_void_p), ('count', C.c_void_p), ('overflow', C.c_void_p), ('knots', C.c_void_p),
+                ('coeff_off', C.c_int32), ('n_spl', C.c_int32), ('degree', C.c_int32), ('n_knots', C.c_int32),
+                ('n_der', C.c_int32), ('n_samp', C.c_int32), ('cap', C.c_int32), ('p_t', C.c_int32),
+                ('sample_time', C.c_double), ('inv_T', C.c_double)]
+
+
 PREDICT_IDEAL, PREDICT_RK4 = 0, 1
 ONLY_FAILED = 8
 
@@ -295,6 +303,9 @@ def load_library(path=None):
                                                  C.c_void_p, C.c_int32, C.c_double, C.c_double]
     lib.omgx_batch_store.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CStoreSpec)]
     lib.omgx_batch_set_store.argtypes = [C.c_void_p, C.POINTER(CStoreSpec)]
+    lib.omgx_batch_set_signals.argtypes = [C.c_void_p, C.POINTER(CSignalsSpec)]
+    lib.omgx_batch_signals_append.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CSignalsSpec)]
+    lib.omgx_batch_signals_reduce.argtypes = [C.c_void_p, C.POINTER(CSignalsSpec), C.c_void_p, C.c_void_p]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -621,6 +632,59 @@ class BatchSolver(object):
             return
         self._store = self._store_spec(out, v_tot, t0, coeff_off, n_spl, degree, knots, n_der, n_samp, dt, inv_T)
         _check(self.lib, self.lib.omgx_batch_set_store(self._h, C.byref(self._store)), 'omgx_batch_set_store')
+
+    def _signals_spec(self, log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T):
+        """omgx_signals_spec from device tensors: log [B, n_der, n_spl, cap] fp64, count / overflow [B] int32 (overflow may be None)."""
+        if log.dim() != 4 or log.shape[0] != self.n_agents or log.shape[2] != int(n_spl) or not log.is_contiguous() or log.element_size() != 8 \
+                or not log.is_floating_point():
+            raise ValueError('log must be a contiguous [n_agents, n_der, n_spl, cap] float64 device tensor')
+        for nm, a in (('count', count), ('overflow', overflow)):
+            if a is None and nm == 'overflow':
+                continue
+            if a is None or a.dim() != 1 or a.shape[0] != self.n_agents or not a.is_contiguous() or a.element_size() != 4 or a.is_floating_point():
+                raise ValueError('%s must be a contiguous [n_agents] int32 device tensor' % nm)
+        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        sp = CSignalsSpec(log.data_ptr(), count.data_ptr(), overflow.data_ptr() if overflow is not None else None, knots.ctypes.data,
+                          int(coeff_off), int(n_spl), int(degree), len(knots), int(log.shape[1]), int(n_samp), int(log.shape[3]), int(p_t),
+                          float(sample_time), float(inv_T))
+        sp._keep = (knots, log, count, overflow)
+        return sp
+
+    def set_signals(self, log=None, count=None, overflow=None, coeff_off=0, n_spl=0, degree=0, knots=None, n_samp=0, p_t=0,
+                    sample_time=0.0, inv_T=1.0):
+        """Every following solve and every step of a rollout appends the travelled samples of the plans it found to the log, inside
+        the kernel (include/omgx.h omgx_batch_set_signals; log=None: off).  The tensors are kept alive here while the log is on."""
+        if log is None:
+            self._signals = None
+            _check(self.lib, self.lib.omgx_batch_set_signals(self._h, None), 'omgx_batch_set_signals')
+            return
+        sp = self._signals_spec(log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T)
+        _check(self.lib, self.lib.omgx_batch_set_signals(self._h, C.byref(sp)), 'omgx_batch_set_signals')
+        self._signals = sp
+
+    def signals_append(self, x, p, log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T, under_way=None):
+        """The same append for the plans in x at the times p[:, p_t] (device tensors), one launch (omgx_batch_signals_append);
+        under_way: optional [n_agents] int32 device tensor, agents with 0 are skipped."""
+        for nm, a, w in (('x', x, self.template.n_var), ('p', p, self.template.n_par)):
+            if a.dim() != 2 or a.shape[0] != self.n_agents or a.shape[1] != w or not a.is_contiguous() or a.element_size() != 8:
+                raise ValueError('%s must be a contiguous [n_agents, %d] float64 device tensor' % (nm, w))
+        if under_way is not None and (under_way.dim() != 1 or under_way.shape[0] != self.n_agents or not under_way.is_contiguous()
+                                      or under_way.element_size() != 4 or under_way.is_floating_point()):
+            raise ValueError('under_way must be a contiguous [n_agents] int32 device tensor')
+        sp = self._signals_spec(log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T)
+        _check(self.lib, self.lib.omgx_batch_signals_append(self._h, x.data_ptr(), p.data_ptr(),
+                                                             under_way.data_ptr() if under_way is not None else None, C.byref(sp)),
+               'omgx_batch_signals_append')
+
+    def signals_reduce(self, log, count, target, summary, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T):
+        """summary [B, 8] <- {columns, motion time, path length, max |input|, max |dinput|, |state_last - target|, |input_last|, 0}
+        from the log (omgx_batch_signals_reduce); target [B, n_spl].  Device tensors."""
+        for nm, a, w in (('target', target, int(n_spl)), ('summary', summary, 8)):
+            if a.dim() != 2 or a.shape[0] != self.n_agents or a.shape[1] != w or not a.is_contiguous() or a.element_size() != 8:
+                raise ValueError('%s must be a contiguous [n_agents, %d] float64 device tensor' % (nm, w))
+        sp = self._signals_spec(log, count, None, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T)
+        _check(self.lib, self.lib.omgx_batch_signals_reduce(self._h, C.byref(sp), target.data_ptr(), summary.data_ptr()),
+               'omgx_batch_signals_reduce')
 
     def sample(self, x, coeff_off, n_spl, degree, knots, n_der, t0, dt, n_samp,
                out=None, as_f32=False, device=False):

@@ -118,6 +118,8 @@ class BatchP2P(object):
         self._shift_dense = [(e, m.reshape(e[1], e[1])) for e, m in zip(ents, mats)]
         self.time = 0.0
         self.under_way, self.stop_tol = None, 1e-3        # (stop_at_arrival)
+        self._sig = None                                  # (record_signals)
+        self._plan_ready = False                          # (solve_cold has run: x holds a plan)
         # (warm_mu_factor 0.1: a step starts at the barrier parameter the previous solve of the agent ended with, tol / 10,
         # unless the shifted point is far off that central path -- a tenth of its average complementarity then: at tol 1e-3
         # the same iterates as factor 0, at 1e-6 0.03 % instead of 0.4 % of the steps end at the iteration cap)
@@ -182,6 +184,8 @@ class BatchP2P(object):
         elif self.pool is not None:
             if self.under_way is not None:
                 raise NotImplementedError('stop_at_arrival: not with a host pool (its workers run the step glue themselves)')
+            if self._sig is not None:
+                raise NotImplementedError('record_signals: not with a host pool (its workers run the step glue themselves)')
             if not warm:
                 self.lam[:] = 0.
             self.pool.solve(self.p, self.x, self.lam, self.status, self.iters, self.dw, step=step_desc,
@@ -201,11 +205,13 @@ class BatchP2P(object):
                                         status0=self.status[idx] if warm else None, warm_start=int(warm),
                                         n_threads=self.n_threads, dw_state=dw, **kw)
                     self.x[idx], self.lam[idx], self.status[idx], self.iters[idx], self.dw[idx] = r['x'], r['lam_g'], r['status'], r['iters'], dw
+                self._signals_append_host(self.under_way)
                 return
             r = self.port.solve(self.tpl, self.p, self.x, lam_g0=self.lam if warm else None,
                                 status0=self.status if warm else None, warm_start=int(warm),
                                 n_threads=self.n_threads, dw_state=self.dw, **kw)
             self.x, self.lam, self.status, self.iters = r['x'], r['lam_g'], r['status'], r['iters']
+            self._signals_append_host(None)
 
     def solve_cold(self, bends=(1.0, -1.0, 2.5, -2.5), fused=True):
         """Cold solve from the reference's initial guess (`get_init_spline_value`: coefficients on the straight
@@ -215,21 +221,38 @@ class BatchP2P(object):
         re-initialise by hand), `bends=()` switches it off.  fused: the restarts run inside the launch of the first
         attempt (`omgx_batch_set_restarts`), else as separate passes over the failed agents (`restart_failed`) --
         same guesses, same results.  Returns the largest number of restarts an agent needed."""
-        if self.kind != 'hip' or not bends:
+        if self.kind != 'hip':
             self._solve(False)
+            self._plan_ready = True
             return 0
-        if not fused:
-            self._solve(False)
-            return self.restart_failed(bends)
-        t = self.torch
-        alts = t.stack([self._bent(self.x, s) for s in bends]).contiguous()
-        attempts = t.zeros(self.B, dtype=t.int32, device=self.dev)
-        self.solver.set_restarts(alts, attempts)
+        self._plan_ready = True
+        # the log (record_signals) takes the cold plan ONCE, after the last restart pass: the fused log stays off during the launches
+        # of the cold solve (an agent that a restart solves again must not be logged twice) and one stand-alone append follows
+        if self._sig is not None:
+            self.solver.set_signals(None)
         try:
-            self._solve(False)
+            if not bends:
+                self._solve(False)
+                n_restarts = 0
+            elif not fused:
+                self._solve(False)
+                n_restarts = self.restart_failed(bends)
+            else:
+                t = self.torch
+                alts = t.stack([self._bent(self.x, s) for s in bends]).contiguous()
+                attempts = t.zeros(self.B, dtype=t.int32, device=self.dev)
+                self.solver.set_restarts(alts, attempts)
+                try:
+                    self._solve(False)
+                finally:
+                    self.solver.set_restarts(None)
+                n_restarts = int(attempts.max().item())
         finally:
-            self.solver.set_restarts(None)
-        return int(attempts.max().item())
+            if self._sig is not None:
+                self._signals_fused(True)
+        if self._sig is not None:
+            self._signals_append_now()
+        return n_restarts
 
     def _bent(self, x_first, s):
         """The initial guess x_first with its spline coefficients moved sideways (perpendicular to start -> goal in
@@ -414,10 +437,155 @@ class BatchP2P(object):
         else:
             self.under_way = np.ones(self.B, dtype=bool)
 
+    # -- the travelled trajectories ----------------------------------------------------------------
+    def record_signals(self, sample_time=0.01, max_updates=200, on=True, cap=None):
+        """Keep the trajectories the vehicles actually travel, as the reference's `Simulator.run` returns them in `vehicle.signals`
+        (`Vehicle.simulate` with `ideal_update`, `vehicles/vehicle.py:359-369`): after every update the samples 1 .. n_samp of the fresh
+        plan (n_samp = update_time / sample_time), ahead of the first also sample 0.  From now on `solve_cold` (once, after its last
+        restart pass), every `step` and every step inside a `rollout` launch append for the agents they solved -- inside the solve /
+        rollout kernel on the device loop (`omgx_batch_set_signals`), so a whole manoeuvre in one launch leaves its whole log.  An agent
+        the stop rule has stopped is not appended; one whose solve did not succeed is (the loop carries on with that plan).  Room for
+        `max_updates` updates: cap = 1 + n_samp * max_updates columns per agent; an append beyond it writes nothing and sets
+        `overflow` (cap=: another number of columns, at least n_samp + 1).  Called after `solve_cold`, the current plan is appended before the call returns: the log always starts with the plan
+        the loop starts from.  State, input and dinput (time-derivative orders 0, 1, 2 of the plan) are kept.  on=False drops the log."""
+        if not on:
+            if self._sig is not None and self.kind == 'hip':
+                self.solver.set_signals(None)
+            self._sig = None
+            return
+        if self.kind == 'host' and self.pool is not None:
+            raise NotImplementedError('record_signals: not with a host pool (its workers run the step glue themselves)')
+        n_samp = int(round(self.update_time / float(sample_time), 6))
+        if n_samp < 1 or int(max_updates) < 1:
+            raise ValueError('record_signals: sample_time must not exceed update_time and max_updates must be positive')
+        n_der = min(3, self.basis.degree + 1)
+        cap = 1 + n_samp * int(max_updates) if cap is None else int(cap)
+        if cap < n_samp + 1:
+            raise ValueError('record_signals: cap = %d holds less than the first append (%d columns)' % (cap, n_samp + 1))
+        shape = (self.B, n_der, self.n_spl, cap)
+        sig = dict(sample_time=float(sample_time), n_samp=n_samp, cap=cap, n_der=n_der, t_start=self.time)
+        if self.kind == 'hip':
+            t = self.torch
+            sig['log'] = t.zeros(shape, dtype=t.float64, device=self.dev)
+            sig['count'] = t.zeros(self.B, dtype=t.int32, device=self.dev)
+            sig['overflow'] = t.zeros(self.B, dtype=t.int32, device=self.dev)
+        else:
+            sig['log'], sig['count'], sig['overflow'] = np.zeros(shape), np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        self._sig = sig
+        if self.kind == 'hip':
+            self._signals_fused(True)
+        if self._plan_ready:
+            self._signals_append_now()
+
+    def _signals_args(self):
+        g = self._sig
+        return dict(coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree, knots=self.basis.knots, n_samp=g['n_samp'],
+                    p_t=self.o_t, sample_time=g['sample_time'], inv_T=1.0 / self.T)
+
+    def _signals_fused(self, on):
+        g = self._sig
+        if on:
+            self.solver.set_signals(g['log'], g['count'], g['overflow'], **self._signals_args())
+        else:
+            self.solver.set_signals(None)
+
+    def _signals_append_now(self):
+        """One append of the current plan (x at the time p[:, t]) outside a solve: the stand-alone kernel / the host statements."""
+        if self.kind == 'hip':
+            g = self._sig
+            self.solver.signals_append(self.x, self.p, g['log'], g['count'], g['overflow'], under_way=self.under_way, **self._signals_args())
+        else:
+            self._signals_append_host(self.under_way)
+
+    def _signals_append_host(self, under_way):
+        """`omgx_batch_signals_append` in numpy (host loop): the same semantics, `Basis.eval_basis` / `derivative` as `_eval_rows`."""
+        g = self._sig
+        if g is None:
+            return
+        L, ns, n_samp, cap, st = self.L, self.n_spl, g['n_samp'], g['cap'], g['sample_time']
+        inv_T = 1.0 / self.T
+        for b in range(self.B):
+            if under_way is not None and not under_way[b]:
+                continue
+            cnt = int(g['count'][b])
+            first = 0 if cnt == 0 else 1
+            n_col = n_samp + 1 - first
+            if cnt + n_col > cap:
+                g['overflow'][b] = 1
+                continue
+            t_rel = float(self.p[b, self.o_t])
+            u = (t_rel + np.arange(first, n_samp + 1) * st) * inv_T
+            c = self.x[b, self.o_spl:self.o_spl + ns * L].reshape(ns, L)
+            for o in range(g['n_der']):
+                if o == 0:
+                    E = self.basis.eval_basis(u)
+                else:
+                    dbasis, Po = self.basis.derivative(o)
+                    E = dbasis.eval_basis(u) @ Po * inv_T ** o
+                g['log'][b, o, :, cnt:cnt + n_col] = c @ E.T
+            g['count'][b] = cnt + n_col
+
+    def signals(self):
+        """The log of `record_signals`: dict with `count` [B] (columns written per agent), `time` [cap] (the time of the first logged
+        plan + c * sample_time), `splines` [B, n_der, n_spl, cap] (time-derivative order o of spline k in column c) and `overflow` [B]
+        (1: an append did not fit and was dropped); for the point-mass classes (state0 / input0 parameters) also `state`, `input`,
+        `dinput` [B, n_spl, cap] as views of `splines`.  Device tensors on the device loop (the caller's stream is ordered behind the
+        launches that wrote them), arrays on the host loop.  The columns of agent b at or beyond `count[b]` are NOT DEFINED: the
+        vehicles arrive at different updates, every agent's signals are its first `count[b]` columns."""
+        g = self._sig
+        if g is None:
+            raise RuntimeError('signals(): call record_signals() first')
+        tax = g['t_start'] + np.arange(g['cap']) * g['sample_time']
+        out = dict(count=g['count'], time=tax, splines=g['log'], overflow=g['overflow'])
+        if (self.veh.label, 'state0') in self.tpl.par_layout:
+            for o, nm in enumerate(('state', 'input', 'dinput')[:g['n_der']]):
+                out[nm] = g['log'][:, o]
+        return out
+
+    def summary(self):
+        """[B, 8] per agent, what `problem.final()` would report from its signals: columns, motion time (columns - 1) * sample_time,
+        path length, largest |input|, largest |dinput|, |state_last - poseT|, |input_last|, 0 (reserved); Euclidean norms.  Device
+        loop: `omgx_batch_signals_reduce` (one launch, fixed summation order); host loop: the same in numpy."""
+        g = self._sig
+        if g is None:
+            raise RuntimeError('summary(): call record_signals() first')
+        if (self.veh.label, 'poseT') not in self.tpl.par_layout:
+            raise NotImplementedError('summary(): the class has no poseT parameter')
+        o_pose = self.tpl.entry_range(self.veh.label, 'poseT', 'par')[0]
+        if self.kind == 'hip':
+            t = self.torch
+            target = self.p[:, o_pose:o_pose + self.n_spl].contiguous()
+            out = t.zeros((self.B, 8), dtype=t.float64, device=self.dev)
+            a = self._signals_args()
+            self.solver.signals_reduce(g['log'], g['count'], target, out, **a)
+            return out
+        return signals_summary_numpy(g['log'], g['count'], self.p[:, o_pose:o_pose + self.n_spl], g['sample_time'])
+
     # -- convenience -----------------------------------------------------------------------
     def host(self, name):
         a = getattr(self, name)
         return a.cpu().numpy() if self.kind == 'hip' else np.asarray(a)
+
+
+def signals_summary_numpy(log, count, target, sample_time):
+    """`omgx_batch_signals_reduce` in numpy: [B, 8] from a log [B, n_der, n_spl, cap], count [B], target [B, n_spl]."""
+    log, count, target = np.asarray(log), np.asarray(count), np.asarray(target)
+    B, n_der = log.shape[0], log.shape[1]
+    out = np.zeros((B, 8))
+    for b in range(B):
+        n = int(count[b])
+        if n < 1:
+            continue
+        sig = log[b, :, :, :n]
+        nrm = lambda a: np.sqrt((a * a).sum(axis=0))
+        out[b, 0], out[b, 1] = n, (n - 1) * sample_time
+        out[b, 2] = nrm(np.diff(sig[0], axis=1)).sum()
+        if n_der >= 2:
+            out[b, 3], out[b, 6] = nrm(sig[1]).max(), nrm(sig[1])[-1]
+        if n_der >= 3:
+            out[b, 4] = nrm(sig[2]).max()
+        out[b, 5] = nrm(sig[0][:, -1:] - target[b][:, None])[0]
+    return out
 
 
 def split_bounds(B, n_streams, slots=None):
@@ -527,6 +695,25 @@ class StreamedP2P(object):
     def stop_at_arrival(self, stop_tol=1e-3, on=True):
         for m in self.parts:
             m.stop_at_arrival(stop_tol, on)
+
+    def record_signals(self, sample_time=0.01, max_updates=200, on=True, cap=None):
+        """`BatchP2P.record_signals` for every sub-batch (each logs on its own stream)."""
+        self._each(lambda m: m.record_signals(sample_time, max_updates, on, cap))
+
+    def signals(self):
+        """`BatchP2P.signals` of the whole batch: the sub-batches' logs joined and concatenated, like `gather`."""
+        parts = [m.signals() for m in self.parts]
+        self.join()
+        out = dict(time=parts[0]['time'])
+        for key in parts[0]:
+            if key != 'time':
+                out[key] = self.torch.cat([q[key] for q in parts])
+        return out
+
+    def summary(self):
+        out = self._each(lambda m: m.summary())
+        self.join()
+        return self.torch.cat(out)
 
     @property
     def under_way(self):
