@@ -22,6 +22,7 @@ import numpy as np
 
 from .distributed import shard_range
 from .consensus import zupdate_matrices, reverse_slots
+from .splines import advance_obstacles, step_clock
 
 
 class AdmmLayoutC(C.Structure):
@@ -344,18 +345,9 @@ class FormationMPC(object):
 
     def step(self):
         lay, ops = self.lay, self.ops
-        t_prev, t_now = self.time, self.time + self.update_time
-        from .splines import since_knot
-        rel_prev = since_knot(t_prev, self.knot_time)
-        tau = (rel_prev + self.update_time) / self.T
-        crossed = int(np.round(t_prev / self.knot_time, 6)) < int(np.round(t_now / self.knot_time, 6))
-        t_rel = since_knot(t_now, self.knot_time)
+        t_now, tau, t_rel, crossed = step_clock(self.time, self.update_time, self.knot_time, self.T)
         ops.predict(self.o_spl, self.n_spl, self.basis, tau, 1.0 / self.T, [lay.p_state0, lay.p_input0], lay.p_t, t_rel)
-        dt = self.update_time
-        for ox, ov, oa, nd in self.obst:        # x <- x + v dt + a dt^2 / 2, v <- v + a dt (`environment/obstacle.py:246-264`)
-            px, pv, pa = ops.p[:, ox:ox + nd], ops.p[:, ov:ov + nd], ops.p[:, oa:oa + nd]
-            px += dt * pv + (0.5 * dt * dt) * pa
-            pv += dt * pa
+        advance_obstacles(ops.p, self.obst, self.update_time)
         if crossed:
             ops.shift(*self.shift)
         self.time = t_now

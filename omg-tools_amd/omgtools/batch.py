@@ -1,27 +1,26 @@
-"""`BatchP2P`: B independent point-to-point agents driven through the
-receding-horizon loop with everything resident on the device.
+"""`BatchP2P`: B independent point-to-point agents driven through the receding-horizon loop with everything resident on the device.
 
-The reference loops `Deployer.update` -> `problem.predict / solve / store`
-(`execution/deployer.py:43-79`) for one agent in Python.  Here one MPC step of the
-whole batch is: (1) ideal prediction -- the initial condition of the next solve is
-the current plan evaluated `update_time` ahead (`vehicles/vehicle.py:323-326`,
-C++ `Vehicle::predict` Vehicle.cpp:61-80); (2) horizon bookkeeping `t = time since
-the last knot crossing` and, on a crossing, the warm-start shift of every `seg`
-spline variable (`problems/point2point.py:187-198`, `basics/optilayer.py:470-490`)
-plus an index shift of the multipliers; (3) `omgx_batch_solve` with a primal-dual
-warm start.  The glue is a handful of tiny tensor ops on [B, *] device arrays
-(torch is only the allocator/stream here); no data leaves HBM between steps.
+The reference loops `Deployer.update` -> `problem.predict / solve / store` (`execution/deployer.py:43-79`) for one agent in Python.
+Here one MPC step of the whole batch is: (1) ideal prediction -- the initial condition of the next solve is the current plan
+evaluated `update_time` ahead (`vehicles/vehicle.py:323-326`, C++ `Vehicle::predict` Vehicle.cpp:61-80); (2) horizon bookkeeping
+`t = time since the last knot crossing` and, on a crossing, the warm-start shift of every `seg` spline variable
+(`problems/point2point.py:187-198`, `basics/optilayer.py:470-490`) plus an index shift of the multipliers; (3) `omgx_batch_solve`
+with a primal-dual warm start.
 
-Passing a host solver object as `ops` (anything with the `solve(template, p, x0, ...)` signature of
-the tests' oracle port binding) runs the same protocol on host arrays instead: that is how the
-parity tests and the CPU baseline of bench.py replay the loop.  This package itself never imports
-the oracle; the default `ops='hip'` is the only product path.
+Layout: `BatchP2P` states that protocol once -- tables and options from the template, `solve_cold`, `step`, `rollout`, the stop rule,
+the log -- and branches on no executor.  Where the [B, *] arrays live and who computes on them sits behind its hooks (`_allocate,
+_predict, _shift, _solve, _cold, _rollout, _norm, _stop_rule, _signals_alloc, _signals_fused, _signals_append_now,
+_signals_summary`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
+being the allocator / stream only; no data leaves HBM between steps) and `HostP2P` (`ops=<a host solver object>`: the same
+statements in numpy, how the parity tests and the CPU baseline of bench.py replay the loop; this package never imports the
+oracle).  `BatchP2P(problem, P, ops=...)` hands out the executor `ops` names.  The clock of a step is `splines.step_clock`, the
+obstacle motion `splines.advance_obstacles`: shared with the formation loops.
 """
 import os
 
 import numpy as np
 
-from .splines import shiftoverknot_T, since_knot
+from .splines import advance_obstacles, shiftoverknot_T, step_clock
 
 
 # solver options of a knot-crossing step (BatchP2P `cross_options`)
@@ -29,16 +28,13 @@ CROSS_OPTIONS = {}
 
 
 def dual_shift_perm(father, extrapolate=True):
-    """perm[r] = row whose multiplier warm-starts row r after the horizon moved by
-    one knot interval (-1: none).  Spline-valued constraint entries are indexed by
-    B-spline coefficients: moving the horizon by one interval drops the first
-    `mult` coefficients (mult = multiplicity of the interior knots of that entry's
-    basis); scalar rows keep their multiplier.  The rows that enter at the end of the horizon
-    have no predecessor: with `extrapolate` they start from the multiplier of the last row that has
-    one (for the terminal-slack rows that is the right magnitude: the objective weight of the last
-    coefficients), otherwise from zero (-1) -- a zero multiplier on a row that is active at the
-    solution removes that row's curvature from the first Newton system, and the first step of the
-    crossing solve is cut to ~1e-6 by the fraction-to-boundary rule."""
+    """perm[r] = row whose multiplier warm-starts row r after the horizon moved by one knot interval (-1: none).  Spline-valued
+    constraint entries are indexed by B-spline coefficients: moving the horizon by one interval drops the first `mult` coefficients
+    (mult = multiplicity of the interior knots of that entry's basis); scalar rows keep their multiplier.  The rows that enter at
+    the end of the horizon have no predecessor: with `extrapolate` they start from the multiplier of the last row that has one (for
+    the terminal-slack rows that is the right magnitude: the objective weight of the last coefficients), otherwise from zero (-1)
+    -- a zero multiplier on a row that is active at the solution removes that row's curvature from the first Newton system, and the
+    first step of the crossing solve is cut to ~1e-6 by the fraction-to-boundary rule."""
     tpl = father.template
     perm = np.arange(tpl.n_con, dtype=np.int64)
     for label, child in father.children.items():
@@ -58,40 +54,43 @@ def dual_shift_perm(father, extrapolate=True):
 
 
 class BatchP2P(object):
+    """The protocol; the module docstring has the layout."""
+
+    def __new__(cls, problem, P, ops='hip', *args, **kw):
+        if cls is BatchP2P:
+            if ops != 'hip' and isinstance(ops, str):
+                raise ValueError("ops must be 'hip' or an injected host solver object (tests / CPU baseline)")
+            cls = DeviceP2P if ops == 'hip' else HostP2P
+        return object.__new__(cls)
 
     def __init__(self, problem, P, ops='hip', device=None, options=None, update_time=0.1,
                  max_iter_step=None, shift_every_spline=True, straggler_first=True, cross_options=None):
-        # max_iter_step: iteration cap of a receding-horizon step (default: the cold-solve cap; an
-        # agent that hits it keeps its last strictly feasible iterate and restarts cold next step).
-        # shift_every_spline: on a knot crossing shift every spline variable like the generated
-        # C++ does (`export/export.py:414-439`); False = the Python rule, names containing 'seg'
-        # only (`optilayer.py:482`), which leaves the stale leading coefficient of g* / eps_* (it
-        # carries no cost just before the crossing, so the barrier parks it far from its bound).
-        # cross_options: solver options of the step right after a knot crossing (the shifted plan sits on the boundary of
-        # the rows that enter the horizon and its multipliers are index-shifted: a wider push into the interior and the
-        # barrier parameter of the shifted point itself)
+        # max_iter_step: iteration cap of a receding-horizon step (default: the cold-solve cap; an agent that hits it keeps its last
+        # strictly feasible iterate and restarts cold next step).  shift_every_spline: on a knot crossing shift every spline variable
+        # like the generated C++ does (`export/export.py:414-439`); False = the Python rule, names containing 'seg' only
+        # (`optilayer.py:482`), which leaves the stale leading coefficient of g* / eps_* (it carries no cost just before the crossing,
+        # so the barrier parks it far from its bound).  cross_options: solver options of the step right after a knot crossing (the
+        # shifted plan sits on the boundary of the rows that enter the horizon and its multipliers are index-shifted: a wider push
+        # into the interior and the barrier parameter of the shifted point itself)
         self.cross_options = dict(cross_options) if cross_options is not None else dict(CROSS_OPTIONS)
         self.problem = problem
         father = problem.father
         self.tpl = tpl = father.template
         if len(problem.vehicles) != 1:
             raise NotImplementedError('BatchP2P drives single-vehicle problems (one agent = one vehicle); '
-                                      'a problem with %d vehicles needs the prediction of each of them'
-                                      % len(problem.vehicles))
+                                      'a problem with %d vehicles needs the prediction of each of them' % len(problem.vehicles))
         veh = problem.vehicles[0]
         self.veh, self.basis = veh, veh.basis
-        self.L, self.n_dim = len(veh.basis), veh.n_dim
+        self.L, self.n_dim, self.n_spl = len(veh.basis), veh.n_dim, veh.n_spl
         self.T = float(problem.options['horizon_time'])
         self.knot_time = float(problem.knot_time)
         self.update_time = float(update_time)
         self.B = P['p'].shape[0]
         self.o_spl = tpl.entry_range(veh.label, 'splines_seg0', 'var')[0]
-        # initial conditions the prediction writes: time derivatives 0, 1, (2) of the plan at the time of the
-        # next solve (`vehicles/holonomic.py:88-89,153-159`: state0, input0; `vehicles/quadrotor.py:76-85,110-114`:
-        # spl0, dspl0, ddspl0)
+        # initial conditions the prediction writes: time derivatives 0, 1, (2) of the plan at the time of the next solve
+        # (`vehicles/holonomic.py:88-89,153-159`: state0, input0; `vehicles/quadrotor.py:76-85,110-114`: spl0, dspl0, ddspl0)
         names = ('spl0', 'dspl0', 'ddspl0') if (veh.label, 'spl0') in tpl.par_layout else ('state0', 'input0')
         self.p_offs = [tpl.entry_range(veh.label, nm, 'par')[0] for nm in names]
-        self.n_spl = veh.n_spl
         self.o_state0, self.o_input0 = self.p_offs[0], self.p_offs[1]
         self.o_t = tpl.entry_range(problem.label, 't', 'par')[0]
         # obstacle motion model between two solves (`environment/obstacle.py:246-264` without bouncing):
@@ -99,9 +98,7 @@ class BatchP2P(object):
         # (`obstacle.py:142-155` reads signals[...][:, -1]; the template extrapolates them back by t)
         self.obst = []
         for obs in problem.environment.obstacles:
-            ox = tpl.entry_range(obs.label, 'x', 'par')
-            ov = tpl.entry_range(obs.label, 'v', 'par')
-            oa = tpl.entry_range(obs.label, 'a', 'par')
+            ox, ov, oa = (tpl.entry_range(obs.label, nm, 'par') for nm in ('x', 'v', 'a'))
             if np.any(P['p'][:, ov[0]:ov[1]] != 0.) or np.any(P['p'][:, oa[0]:oa[1]] != 0.):     # static obstacles: nothing to do
                 self.obst.append((ox[0], ov[0], oa[0], ox[1] - ox[0]))
         # (a problem loaded from a bundle, `omgtools.workloads`, brings the multiplier map of a knot crossing with it)
@@ -129,233 +126,70 @@ class BatchP2P(object):
         from .backend import DEFAULT_OPTIONS
         self._base_extra = dict((k, self.opts.get(k, DEFAULT_OPTIONS[k])) for k in self.cross_options)   # (what a non-crossing step resets them to)
         self.max_iter_step = int(max_iter_step) if max_iter_step else self.max_iter_cold
-        self.kind = 'hip' if ops == 'hip' else 'host'
         self.straggler_first = bool(straggler_first)
-        if ops == 'hip':
-            import torch
-            from .backend import BatchSolver
-            self.torch = torch
-            self.dev = device if device is not None else torch.device('cuda', 0)
-            f64 = dict(dtype=torch.float64, device=self.dev)
-            self.solver = BatchSolver(tpl, self.B, device=self.dev.index or 0, options=self.opts)
-            self.solver.set_stream(torch.cuda.current_stream().cuda_stream)
-            self.p = torch.as_tensor(np.ascontiguousarray(P['p']), **f64)
-            self.x = torch.as_tensor(np.ascontiguousarray(P['x0']), **f64)
-            self.x_new = torch.empty_like(self.x)
-            self.lam = torch.zeros((self.B, tpl.n_con), **f64)
-            self.lb, self.ub = torch.as_tensor(tpl.lb, **f64), torch.as_tensor(tpl.ub, **f64)
-            self.status = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
-            self.iters = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
-            pm = np.maximum(self.perm, 0)
-            self._perm_idx = torch.as_tensor(pm, dtype=torch.int64, device=self.dev)
-            self._perm_ok = torch.as_tensor((self.perm >= 0).astype(np.float64), **f64)
-            self._mask = torch.ones(self.B, dtype=torch.uint8, device=self.dev)
-            self._order = torch.arange(self.B, dtype=torch.int32, device=self.dev)
-        else:
-            if isinstance(ops, str):
-                raise ValueError("ops must be 'hip' or an injected host solver object (tests / CPU baseline)")
-            self.port = ops                          # injected by tests / bench.py's cpu_baseline leg
-            self.n_threads = 1
-            self.pool = None                         # optional: a host solver with `solve(p, x, lam, status, iters, dw,
-            #                                          step=...)` that also runs the step glue per agent (bench.py)
-            self.dw = np.zeros(self.B)            # inertia correction carried between warm solves
-            self.p, self.x = np.ascontiguousarray(P['p'], dtype=float).copy(), np.ascontiguousarray(P['x0'], dtype=float).copy()
-            self.lam = np.zeros((self.B, tpl.n_con))
-            self.status = np.zeros(self.B, dtype=np.int32)
-            self.iters = np.zeros(self.B, dtype=np.int32)
+        self._allocate(P, ops, device)
 
     # -- solves ------------------------------------------------------------------------
-    def _solve(self, warm, events=None, step_desc=None, ordered=False, extra=None):
-        extra = extra or {}
-        if self.kind == 'hip':
-            self.solver.set_options(warm_start=int(warm),
-                                    max_iter=self.max_iter_step if warm else self.max_iter_cold, **dict(self._base_extra, **extra))
-            if not warm:
-                self.lam.zero_()
-                self._x_init = self.x.clone()
-            if warm and self.straggler_first and not ordered:
-                # agents that needed most iterations last time are launched first
-                self.solver.order_by_iters(self.iters, self._order)
-            if events is not None:                 # timing events of the caller (bench.py): on the solve kernel's own dispatch
-                self.solver.set_launch_events(events[0], events[1])
-            self.solver.solve_device(self.p, self.x, self.lb, self.ub, self.x_new, self.lam,
-                                     self.status, self.iters, bounds_shared=True)
-            self.x, self.x_new = self.x_new, self.x
-        elif self.pool is not None:
-            if self.under_way is not None:
-                raise NotImplementedError('stop_at_arrival: not with a host pool (its workers run the step glue themselves)')
-            if self._sig is not None:
-                raise NotImplementedError('record_signals: not with a host pool (its workers run the step glue themselves)')
-            if not warm:
-                self.lam[:] = 0.
-            self.pool.solve(self.p, self.x, self.lam, self.status, self.iters, self.dw, step=step_desc,
-                            **dict(self.opts, warm_start=int(warm), max_iter=self.max_iter_step if warm else self.max_iter_cold, **extra))
-        else:
-            kw = dict(self.opts, max_iter=self.max_iter_step if warm else self.max_iter_cold, **extra)
-            if self.under_way is not None:
-                # the stop rule as the solve kernel applies it: the criterion on p ends an agent's loop for good; the agents
-                # under way are solved as a batch of their own (independent problems: the same results), the others keep
-                # their plan, their multipliers and their status, iters = 0
-                self.under_way &= ~self.arrived(self.stop_tol)
-                idx = np.flatnonzero(self.under_way)
-                self.iters = np.zeros(self.B, dtype=np.int32)
-                if len(idx):
-                    dw = self.dw[idx].copy()
-                    r = self.port.solve(self.tpl, self.p[idx], self.x[idx], lam_g0=self.lam[idx] if warm else None,
-                                        status0=self.status[idx] if warm else None, warm_start=int(warm),
-                                        n_threads=self.n_threads, dw_state=dw, **kw)
-                    self.x[idx], self.lam[idx], self.status[idx], self.iters[idx], self.dw[idx] = r['x'], r['lam_g'], r['status'], r['iters'], dw
-                self._signals_append_host(self.under_way)
-                return
-            r = self.port.solve(self.tpl, self.p, self.x, lam_g0=self.lam if warm else None,
-                                status0=self.status if warm else None, warm_start=int(warm),
-                                n_threads=self.n_threads, dw_state=self.dw, **kw)
-            self.x, self.lam, self.status, self.iters = r['x'], r['lam_g'], r['status'], r['iters']
-            self._signals_append_host(None)
-
     def solve_cold(self, bends=(1.0, -1.0, 2.5, -2.5), fused=True):
-        """Cold solve from the reference's initial guess (`get_init_spline_value`: coefficients on the straight
-        line).  Agents that do not converge from it (phase I stalls: e.g. 5 % of the Quadrotor class with its five
-        moving obstacles) are solved again from the same guess bent sideways by `bends[0]`, then `bends[1]` ... metres
-        at mid-course -- a different side of the obstacles; the reference has no such retry (its user would
-        re-initialise by hand), `bends=()` switches it off.  fused: the restarts run inside the launch of the first
-        attempt (`omgx_batch_set_restarts`), else as separate passes over the failed agents (`restart_failed`) --
-        same guesses, same results.  Returns the largest number of restarts an agent needed."""
-        if self.kind != 'hip':
-            self._solve(False)
-            self._plan_ready = True
-            return 0
+        """Cold solve from the reference's initial guess (`get_init_spline_value`: coefficients on the straight line).  Agents that do
+        not converge from it (phase I stalls: e.g. 5 % of the Quadrotor class with its five moving obstacles) are solved again from the
+        same guess bent sideways by `bends[0]`, then `bends[1]` ... metres at mid-course -- a different side of the obstacles; the
+        reference has no such retry (its user would re-initialise by hand), `bends=()` switches it off.  fused: the restarts run inside
+        the launch of the first attempt (`omgx_batch_set_restarts`), else as separate passes over the failed agents (`restart_failed`)
+        -- same guesses, same results.  Returns the largest number of restarts an agent needed (a host solver object has none: 0)."""
         self._plan_ready = True
-        # the log (record_signals) takes the cold plan ONCE, after the last restart pass: the fused log stays off during the launches
-        # of the cold solve (an agent that a restart solves again must not be logged twice) and one stand-alone append follows
-        if self._sig is not None:
-            self.solver.set_signals(None)
+        # the log (record_signals) takes the cold plan ONCE, after the last restart pass: the log inside the solve stays off during
+        # the cold solve (an agent that a restart solves again must not be logged twice) and one stand-alone append follows
+        log = self._sig is not None
+        if log:
+            self._signals_fused(False)
         try:
-            if not bends:
-                self._solve(False)
-                n_restarts = 0
-            elif not fused:
-                self._solve(False)
-                n_restarts = self.restart_failed(bends)
-            else:
-                t = self.torch
-                alts = t.stack([self._bent(self.x, s) for s in bends]).contiguous()
-                attempts = t.zeros(self.B, dtype=t.int32, device=self.dev)
-                self.solver.set_restarts(alts, attempts)
-                try:
-                    self._solve(False)
-                finally:
-                    self.solver.set_restarts(None)
-                n_restarts = int(attempts.max().item())
+            n_restarts = self._cold(bends, fused)
         finally:
-            if self._sig is not None:
+            if log:
                 self._signals_fused(True)
-        if self._sig is not None:
+        if log:
             self._signals_append_now()
         return n_restarts
 
-    def _bent(self, x_first, s):
-        """The initial guess x_first with its spline coefficients moved sideways (perpendicular to start -> goal in
-        the x-y plane) by s * sin^2(pi * k / (L - 1)) metres."""
-        t = self.torch
-        L, ns = self.L, self.n_spl
-        c = x_first[:, self.o_spl:self.o_spl + ns * L].reshape(self.B, ns, L)
-        d = c[:, :, -1] - c[:, :, 0]
-        d = d / d.norm(dim=1, keepdim=True).clamp_min(1e-12)
-        nrm = t.zeros_like(d)
-        nrm[:, 0], nrm[:, 1] = -d[:, 1], d[:, 0]
-        nrm = nrm / nrm.norm(dim=1, keepdim=True).clamp_min(1e-12)
-        bump = t.sin(t.linspace(0., 1., L, dtype=t.float64, device=self.dev) * np.pi) ** 2
-        alt = x_first.clone()
-        alt[:, self.o_spl:self.o_spl + ns * L] += (float(s) * nrm[:, :, None] * bump[None, None, :]).reshape(self.B, -1)
-        return alt
-
     def restart_failed(self, bends=(1.0, -1.0, 2.5, -2.5)):
         """Restart passes of a cold solve (see solve_cold); returns how many were needed."""
-        passes = 0
-        if self.kind != 'hip' or not bends:
-            return passes
-        for s in bends:
-            if bool((self.status == 0).all()):
-                break
-            alt = self._bent(self._x_init, s)      # (_x_init: the guess the first pass started from)
-            # the solved agents sit in self.x (the output of the last pass): they are skipped and keep it
-            self.solver.set_options(warm_start=0, max_iter=self.max_iter_cold)
-            self.solver.solve_device(self.p, alt, self.lb, self.ub, self.x, self.lam, self.status, self.iters,
-                                     bounds_shared=True, only_failed=True)
-            passes += 1
-        return passes
+        return 0
 
     # -- one receding-horizon step ---------------------------------------------------------
     def step(self, events=None, before_solve=None):
         """before_solve(self): called between the glue of the step (prediction, obstacles, shift: p and x are what the
         solve will read) and the solve -- where a caller with host buffers uploads its parameters (bench.py's pipelined
         host-boundary leg)."""
-        B, L, nd = self.B, self.L, self.n_dim
-        t_prev = self.time
-        t_now = t_prev + self.update_time
-        rel_prev = since_knot(t_prev, self.knot_time)
-        # (1) ideal prediction on the current plan, (2) horizon bookkeeping
-        tau = (rel_prev + self.update_time) / self.T
-        crossed = int(np.round(t_prev / self.knot_time, 6)) < int(np.round(t_now / self.knot_time, 6))
-        t_rel = since_knot(t_now, self.knot_time)
-        if self.kind == 'host' and self.pool is not None:
-            self.time = t_now
-            self._solve(True, step_desc=self._pool_step(tau, t_rel, crossed), extra=self.cross_options if crossed else None)
-            return crossed
-        if self.kind == 'hip':
-            # (asked for before the prediction: its launch then carries the ordering as one more workgroup)
-            if self.straggler_first:
-                self.solver.order_by_iters(self.iters, self._order)
-            # one kernel: the initial conditions from the plan at tau and the new t, all written into p
-            self.solver.predict_ex(self.x, self.p, self.o_spl, self.n_spl, self.basis.degree, self.basis.knots, tau,
-                                   1.0 / self.T, self.p_offs, self.o_t, t_rel)
-        else:
-            c = self.x[:, self.o_spl:self.o_spl + self.n_spl * L].reshape(B, self.n_spl, L)
-            for o, E in enumerate(self._eval_rows(tau)):
-                self.p[:, self.p_offs[o]:self.p_offs[o] + self.n_spl] = c @ E
-            self.p[:, self.o_t] = t_rel
-        # obstacles move on: x <- x + v dt + a dt^2 / 2, v <- v + a dt (a no-op for static obstacles)
-        dt = self.update_time
-        for ox, ov, oa, nd_o in self.obst:
-            px, pv, pa = self.p[:, ox:ox + nd_o], self.p[:, ov:ov + nd_o], self.p[:, oa:oa + nd_o]
-            px += dt * pv + (0.5 * dt * dt) * pa
-            pv += dt * pa
+        t_now, tau, t_rel, crossed = step_clock(self.time, self.update_time, self.knot_time, self.T)
+        # (1) ideal prediction on the current plan, (2) horizon bookkeeping: the initial conditions from the plan at tau and the new t
+        self._predict(tau, t_rel)
+        advance_obstacles(self.p, self.obst, self.update_time)      # (a no-op for static obstacles)
         if crossed:
             self._shift()
         self.time = t_now
         if before_solve is not None:
             before_solve(self)
-        # (3) warm-started solve
-        self._solve(True, events, ordered=self.kind == 'hip' and self.straggler_first, extra=self.cross_options if crossed else None)
+        # (3) warm-started solve (ordered: `_predict` has asked for the launch order already)
+        self._solve(True, events, ordered=True, extra=self.cross_options if crossed else None)
         return crossed
 
     def rollout(self, n_steps, iters_log=None, status_log=None):
-        """`n_steps` receding-horizon steps of every agent in ONE launch (`omgx_batch_rollout`): per agent the statements of
-        `step` -- prediction, obstacles, knot-crossing shift, warm-started solve -- in the same order with the same numbers,
-        without the barrier between the steps of different agents (they are independent problems: each vehicle of the
-        reference runs its own `Deployer.update` loop).  For simulation / evaluation runs with ideal prediction; a deployment
-        that feeds measured states back steps with `step`.  Returns the number of knot crossings."""
-        if self.kind != 'hip':
-            raise NotImplementedError('rollout is a device launch')
-        tau, t_rel, crossed = [], [], []
-        t = self.time
-        for _ in range(int(n_steps)):                      # (the clock of `step`, statement for statement)
-            t_prev, t_now = t, t + self.update_time
-            rel_prev = since_knot(t_prev, self.knot_time)
-            tau.append((rel_prev + self.update_time) / self.T)
-            crossed.append(int(np.round(t_prev / self.knot_time, 6)) < int(np.round(t_now / self.knot_time, 6)))
-            t_rel.append(since_knot(t_now, self.knot_time))
-            t = t_now
-        self.solver.set_options(warm_start=1, max_iter=self.max_iter_step, **self._base_extra)
-        if self.straggler_first:
-            self.solver.order_by_iters(self.iters, self._order)
-        self.solver.rollout(self.p, self.x, self.lb, self.ub, self.lam, self.status, self.iters, tau, t_rel, crossed,
-                            self.o_spl, self.n_spl, self.basis.degree, self.basis.knots, 1.0 / self.T, self.p_offs, self.o_t,
-                            obstacles=self.obst, dt=self.update_time, shift_entries=self.shift_entries, shift_T=self.shift_mats,
-                            lam_perm=self.perm, cross_options=self.cross_options or None, iters_log=iters_log, status_log=status_log)
+        """`n_steps` receding-horizon steps of every agent in ONE launch (`omgx_batch_rollout`): per agent the statements of `step` --
+        prediction, obstacles, knot-crossing shift, warm-started solve -- in the same order with the same numbers, without the barrier
+        between the steps of different agents (they are independent problems: each vehicle of the reference runs its own
+        `Deployer.update` loop).  For simulation / evaluation runs with ideal prediction; a deployment that feeds measured states back
+        steps with `step`.  Returns the number of knot crossings."""
+        clock, t = [], self.time
+        for _ in range(int(n_steps)):
+            t, tau, t_rel, crossed = step_clock(t, self.update_time, self.knot_time, self.T)
+            clock.append((tau, t_rel, crossed))
+        self._rollout(*([c[k] for c in clock] for k in range(3)), iters_log=iters_log, status_log=status_log)
         self.time = t
-        return int(sum(crossed))
+        return int(sum(c[2] for c in clock))
+
+    def _rollout(self, tau, t_rel, crossed, iters_log, status_log):
+        raise NotImplementedError('rollout is a device launch')
 
     def _eval_rows(self, tau):
         """[E_0, E_1, ...]: c @ E_o = o-th time derivative of the plan at tau."""
@@ -365,54 +199,22 @@ class BatchP2P(object):
             rows.append(dbasis.eval_basis([tau])[0] @ Po / self.T ** o)
         return rows
 
-    def _pool_step(self, tau, t_rel, crossed):
-        """Constants of this step for a pool that runs the glue per agent in its workers (field names of the
-        `StepDesc` the pool defines)."""
-        desc = self.pool.step_desc()
-        rows = [np.ascontiguousarray(r) for r in self._eval_rows(tau)]
-        if len(rows) != 2 or self.n_spl != self.n_dim:
-            raise NotImplementedError('the pool step glue carries state0 / input0 only')
-        E, Ed = rows
-        obst = np.ascontiguousarray(np.array(self.obst, dtype=np.int32).reshape(-1, 4))
-        perm = np.ascontiguousarray(self.perm, dtype=np.int64)
-        ents = np.ascontiguousarray(self.shift_entries, dtype=np.int32)
-        mats = np.ascontiguousarray(self.shift_mats, dtype=np.float64)
-        desc._keep = (E, Ed, obst, perm, ents, mats)
-        desc.o_spl, desc.n_dim, desc.L = self.o_spl, self.n_dim, self.L
-        desc.o_state0, desc.o_input0, desc.o_t = self.o_state0, self.o_input0, self.o_t
-        desc.t_rel, desc.dt = t_rel, self.update_time
-        desc.E, desc.Ed = E.ctypes.data, Ed.ctypes.data
-        desc.n_obst, desc.obst = len(self.obst), obst.ctypes.data
-        desc.crossed, desc.n_shift = int(crossed), len(ents)
-        desc.shift_entries, desc.shift_mats, desc.perm = ents.ctypes.data, mats.ctypes.data, perm.ctypes.data
-        return desc
-
-    def _shift(self):
-        if self.kind == 'hip':
-            self.solver.shift(self.x, self._mask, self.shift_entries, self.shift_mats, device=True)
-            self.lam = self.lam.index_select(1, self._perm_idx) * self._perm_ok
-        else:
-            for (lo, rows, cols, _), Tm in self._shift_dense:
-                blk = self.x[:, lo:lo + rows * cols].reshape(self.B, cols, rows)
-                self.x[:, lo:lo + rows * cols] = (blk @ Tm.T).reshape(self.B, -1)
-            self.lam = np.where(self.perm >= 0, self.lam[:, np.maximum(self.perm, 0)], 0.0)
-
     # -- the reference's stop criterion ----------------------------------------------------------
+    def _o_pose(self, who, point_mass=True):
+        """Offset of poseT in p, for the method `who` that reads it (point_mass: and state0 / input0)."""
+        lay, label = self.tpl.par_layout, self.veh.label
+        if (label, 'poseT') not in lay or (point_mass and (label, 'state0') not in lay):
+            raise NotImplementedError('%s(): the class has no %s' % (who, 'state0 / input0 / poseT parameters' if point_mass else 'poseT parameter'))
+        return self.tpl.entry_range(label, 'poseT', 'par')[0]
+
     def arrived(self, stop_tol=1e-3):
         """Per agent: the reference's `stop_criterium` (`problems/point2point.py:98-102` -> `vehicles/holonomic.py:145-151`,
         `holonomic3d.py`: |state - poseT| <= stop_tol and |input| <= stop_tol, Euclidean norms, `stop_tol` = 1e-3 by default,
         `vehicles/vehicle.py:72`) on the state the last prediction wrote into p -- the state the vehicle is in at the time of
         the current update.  Boolean tensor (device loop) / array (host loop); the reference's `Simulator.run` ends a vehicle's
         loop at the first update for which this holds (`execution/simulator.py:39-62`).  Point-mass classes (state0 / input0 / poseT)."""
-        tpl, veh = self.tpl, self.veh
-        if (veh.label, 'poseT') not in tpl.par_layout or (veh.label, 'state0') not in tpl.par_layout:
-            raise NotImplementedError('arrived(): the class has no state0 / input0 / poseT parameters')
-        nd = self.n_dim
-        o_pose = tpl.entry_range(veh.label, 'poseT', 'par')[0]
-        st, inp, pose = (self.p[:, o:o + nd] for o in (self.o_state0, self.o_input0, o_pose))
-        if self.kind == 'hip':
-            return ((st - pose).norm(dim=1) <= stop_tol) & (inp.norm(dim=1) <= stop_tol)
-        return (np.linalg.norm(st - pose, axis=1) <= stop_tol) & (np.linalg.norm(inp, axis=1) <= stop_tol)
+        st, inp, pose = (self.p[:, o:o + self.n_dim] for o in (self.o_state0, self.o_input0, self._o_pose('arrived')))
+        return (self._norm(st - pose) <= stop_tol) & (self._norm(inp) <= stop_tol)
 
     def stop_at_arrival(self, stop_tol=1e-3, on=True):
         """End every agent's loop where the reference's does: from now on an agent for which `arrived(stop_tol)` holds at an update
@@ -421,21 +223,10 @@ class BatchP2P(object):
         the rule is the solve kernel's (`omgx_batch_set_stop`, no launch of its own); `under_way` [B] (int32 tensor / bool array)
         holds who is still running.  The agents under way are solved exactly as without the rule.  `rollout` applies it too: an agent's
         loop inside the launch ends at the step its state meets the criterion (its plan stays as it is at that step)."""
-        if not on:
-            self.under_way = None
-            if self.kind == 'hip':
-                self.solver.set_stop(under_way=None)
-            return
-        tpl, veh = self.tpl, self.veh
-        if (veh.label, 'poseT') not in tpl.par_layout or (veh.label, 'state0') not in tpl.par_layout:
-            raise NotImplementedError('stop_at_arrival(): the class has no state0 / input0 / poseT parameters')
-        self.stop_tol = float(stop_tol)
-        if self.kind == 'hip':
-            self.under_way = self.torch.ones(self.B, dtype=self.torch.int32, device=self.dev)
-            self.solver.set_stop(self.o_state0, self.o_input0, tpl.entry_range(veh.label, 'poseT', 'par')[0], self.n_dim, self.stop_tol,
-                                 self.under_way)
-        else:
-            self.under_way = np.ones(self.B, dtype=bool)
+        o_pose = self._o_pose('stop_at_arrival') if on else None
+        if on:
+            self.stop_tol = float(stop_tol)
+        self._stop_rule(o_pose)
 
     # -- the travelled trajectories ----------------------------------------------------------------
     def record_signals(self, sample_time=0.01, max_updates=200, on=True, cap=None):
@@ -449,12 +240,10 @@ class BatchP2P(object):
         `overflow` (cap=: another number of columns, at least n_samp + 1).  Called after `solve_cold`, the current plan is appended before the call returns: the log always starts with the plan
         the loop starts from.  State, input and dinput (time-derivative orders 0, 1, 2 of the plan) are kept.  on=False drops the log."""
         if not on:
-            if self._sig is not None and self.kind == 'hip':
-                self.solver.set_signals(None)
+            if self._sig is not None:
+                self._signals_fused(False)
             self._sig = None
             return
-        if self.kind == 'host' and self.pool is not None:
-            raise NotImplementedError('record_signals: not with a host pool (its workers run the step glue themselves)')
         n_samp = int(round(self.update_time / float(sample_time), 6))
         if n_samp < 1 or int(max_updates) < 1:
             raise ValueError('record_signals: sample_time must not exceed update_time and max_updates must be positive')
@@ -462,68 +251,12 @@ class BatchP2P(object):
         cap = 1 + n_samp * int(max_updates) if cap is None else int(cap)
         if cap < n_samp + 1:
             raise ValueError('record_signals: cap = %d holds less than the first append (%d columns)' % (cap, n_samp + 1))
-        shape = (self.B, n_der, self.n_spl, cap)
         sig = dict(sample_time=float(sample_time), n_samp=n_samp, cap=cap, n_der=n_der, t_start=self.time)
-        if self.kind == 'hip':
-            t = self.torch
-            sig['log'] = t.zeros(shape, dtype=t.float64, device=self.dev)
-            sig['count'] = t.zeros(self.B, dtype=t.int32, device=self.dev)
-            sig['overflow'] = t.zeros(self.B, dtype=t.int32, device=self.dev)
-        else:
-            sig['log'], sig['count'], sig['overflow'] = np.zeros(shape), np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        sig['log'], sig['count'], sig['overflow'] = self._signals_alloc((self.B, n_der, self.n_spl, cap))
         self._sig = sig
-        if self.kind == 'hip':
-            self._signals_fused(True)
+        self._signals_fused(True)
         if self._plan_ready:
             self._signals_append_now()
-
-    def _signals_args(self):
-        g = self._sig
-        return dict(coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree, knots=self.basis.knots, n_samp=g['n_samp'],
-                    p_t=self.o_t, sample_time=g['sample_time'], inv_T=1.0 / self.T)
-
-    def _signals_fused(self, on):
-        g = self._sig
-        if on:
-            self.solver.set_signals(g['log'], g['count'], g['overflow'], **self._signals_args())
-        else:
-            self.solver.set_signals(None)
-
-    def _signals_append_now(self):
-        """One append of the current plan (x at the time p[:, t]) outside a solve: the stand-alone kernel / the host statements."""
-        if self.kind == 'hip':
-            g = self._sig
-            self.solver.signals_append(self.x, self.p, g['log'], g['count'], g['overflow'], under_way=self.under_way, **self._signals_args())
-        else:
-            self._signals_append_host(self.under_way)
-
-    def _signals_append_host(self, under_way):
-        """`omgx_batch_signals_append` in numpy (host loop): the same semantics, `Basis.eval_basis` / `derivative` as `_eval_rows`."""
-        g = self._sig
-        if g is None:
-            return
-        L, ns, n_samp, cap, st = self.L, self.n_spl, g['n_samp'], g['cap'], g['sample_time']
-        inv_T = 1.0 / self.T
-        for b in range(self.B):
-            if under_way is not None and not under_way[b]:
-                continue
-            cnt = int(g['count'][b])
-            first = 0 if cnt == 0 else 1
-            n_col = n_samp + 1 - first
-            if cnt + n_col > cap:
-                g['overflow'][b] = 1
-                continue
-            t_rel = float(self.p[b, self.o_t])
-            u = (t_rel + np.arange(first, n_samp + 1) * st) * inv_T
-            c = self.x[b, self.o_spl:self.o_spl + ns * L].reshape(ns, L)
-            for o in range(g['n_der']):
-                if o == 0:
-                    E = self.basis.eval_basis(u)
-                else:
-                    dbasis, Po = self.basis.derivative(o)
-                    E = dbasis.eval_basis(u) @ Po * inv_T ** o
-                g['log'][b, o, :, cnt:cnt + n_col] = c @ E.T
-            g['count'][b] = cnt + n_col
 
     def signals(self):
         """The log of `record_signals`: dict with `count` [B] (columns written per agent), `time` [cap] (the time of the first logged
@@ -546,25 +279,291 @@ class BatchP2P(object):
         """[B, 8] per agent, what `problem.final()` would report from its signals: columns, motion time (columns - 1) * sample_time,
         path length, largest |input|, largest |dinput|, |state_last - poseT|, |input_last|, 0 (reserved); Euclidean norms.  Device
         loop: `omgx_batch_signals_reduce` (one launch, fixed summation order); host loop: the same in numpy."""
-        g = self._sig
-        if g is None:
+        if self._sig is None:
             raise RuntimeError('summary(): call record_signals() first')
-        if (self.veh.label, 'poseT') not in self.tpl.par_layout:
-            raise NotImplementedError('summary(): the class has no poseT parameter')
-        o_pose = self.tpl.entry_range(self.veh.label, 'poseT', 'par')[0]
-        if self.kind == 'hip':
-            t = self.torch
-            target = self.p[:, o_pose:o_pose + self.n_spl].contiguous()
-            out = t.zeros((self.B, 8), dtype=t.float64, device=self.dev)
-            a = self._signals_args()
-            self.solver.signals_reduce(g['log'], g['count'], target, out, **a)
-            return out
-        return signals_summary_numpy(g['log'], g['count'], self.p[:, o_pose:o_pose + self.n_spl], g['sample_time'])
+        o_pose = self._o_pose('summary', point_mass=False)
+        return self._signals_summary(self.p[:, o_pose:o_pose + self.n_spl])
 
-    # -- convenience -----------------------------------------------------------------------
     def host(self, name):
         a = getattr(self, name)
-        return a.cpu().numpy() if self.kind == 'hip' else np.asarray(a)
+        return a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)
+
+
+class DeviceP2P(BatchP2P):
+    """The device executor (`ops='hip'`): [B, *] torch tensors as plain attributes, every hook a launch of the library on them."""
+    kind = 'hip'
+
+    def _allocate(self, P, ops, device):
+        import torch
+        from .backend import BatchSolver
+        self.torch = torch
+        self.dev = device if device is not None else torch.device('cuda', 0)
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        self.solver = BatchSolver(self.tpl, self.B, device=self.dev.index or 0, options=self.opts)
+        self.solver.set_stream(torch.cuda.current_stream().cuda_stream)
+        self.p = torch.as_tensor(np.ascontiguousarray(P['p']), **f64)
+        self.x = torch.as_tensor(np.ascontiguousarray(P['x0']), **f64)
+        self.x_new = torch.empty_like(self.x)
+        self.lam = torch.zeros((self.B, self.tpl.n_con), **f64)
+        self.lb, self.ub = torch.as_tensor(self.tpl.lb, **f64), torch.as_tensor(self.tpl.ub, **f64)
+        self.status = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        self.iters = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        self._perm_idx = torch.as_tensor(np.maximum(self.perm, 0), dtype=torch.int64, device=self.dev)
+        self._perm_ok = torch.as_tensor((self.perm >= 0).astype(np.float64), **f64)
+        self._mask = torch.ones(self.B, dtype=torch.uint8, device=self.dev)
+        self._order = torch.arange(self.B, dtype=torch.int32, device=self.dev)
+
+    def _predict(self, tau, t_rel):
+        # (the order is asked for before the prediction: its launch then carries the ordering as one more workgroup)
+        if self.straggler_first:
+            self.solver.order_by_iters(self.iters, self._order)
+        # one kernel: the initial conditions from the plan at tau and the new t, all written into p
+        self.solver.predict_ex(self.x, self.p, self.o_spl, self.n_spl, self.basis.degree, self.basis.knots, tau,
+                               1.0 / self.T, self.p_offs, self.o_t, t_rel)
+
+    def _shift(self):
+        self.solver.shift(self.x, self._mask, self.shift_entries, self.shift_mats, device=True)
+        self.lam = self.lam.index_select(1, self._perm_idx) * self._perm_ok
+
+    def _solve(self, warm, events=None, ordered=False, extra=None):
+        self.solver.set_options(warm_start=int(warm), max_iter=self.max_iter_step if warm else self.max_iter_cold,
+                                **dict(self._base_extra, **(extra or {})))
+        if not warm:
+            self.lam.zero_()
+            self._x_init = self.x.clone()
+        if warm and self.straggler_first and not ordered:
+            # agents that needed most iterations last time are launched first
+            self.solver.order_by_iters(self.iters, self._order)
+        if events is not None:                 # timing events of the caller (bench.py): on the solve kernel's own dispatch
+            self.solver.set_launch_events(events[0], events[1])
+        self.solver.solve_device(self.p, self.x, self.lb, self.ub, self.x_new, self.lam, self.status, self.iters, bounds_shared=True)
+        self.x, self.x_new = self.x_new, self.x
+
+    def _cold(self, bends, fused):
+        if not bends or not fused:
+            self._solve(False)
+            return self.restart_failed(bends)
+        t = self.torch
+        alts = t.stack([self._bent(self.x, s) for s in bends]).contiguous()
+        attempts = t.zeros(self.B, dtype=t.int32, device=self.dev)
+        self.solver.set_restarts(alts, attempts)
+        try:
+            self._solve(False)
+        finally:
+            self.solver.set_restarts(None)
+        return int(attempts.max().item())
+
+    def _bent(self, x_first, s):
+        """The initial guess x_first with its spline coefficients moved sideways (perpendicular to start -> goal in
+        the x-y plane) by s * sin^2(pi * k / (L - 1)) metres."""
+        t = self.torch
+        L, ns = self.L, self.n_spl
+        c = x_first[:, self.o_spl:self.o_spl + ns * L].reshape(self.B, ns, L)
+        d = c[:, :, -1] - c[:, :, 0]
+        d = d / d.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        nrm = t.zeros_like(d)
+        nrm[:, 0], nrm[:, 1] = -d[:, 1], d[:, 0]
+        nrm = nrm / nrm.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        bump = t.sin(t.linspace(0., 1., L, dtype=t.float64, device=self.dev) * np.pi) ** 2
+        alt = x_first.clone()
+        alt[:, self.o_spl:self.o_spl + ns * L] += (float(s) * nrm[:, :, None] * bump[None, None, :]).reshape(self.B, -1)
+        return alt
+
+    def restart_failed(self, bends=(1.0, -1.0, 2.5, -2.5)):
+        passes = 0
+        for s in bends or ():
+            if bool((self.status == 0).all()):
+                break
+            alt = self._bent(self._x_init, s)      # (_x_init: the guess the first pass started from)
+            # the solved agents sit in self.x (the output of the last pass): they are skipped and keep it
+            self.solver.set_options(warm_start=0, max_iter=self.max_iter_cold)
+            self.solver.solve_device(self.p, alt, self.lb, self.ub, self.x, self.lam, self.status, self.iters, bounds_shared=True, only_failed=True)
+            passes += 1
+        return passes
+
+    def _rollout(self, tau, t_rel, crossed, iters_log, status_log):
+        self.solver.set_options(warm_start=1, max_iter=self.max_iter_step, **self._base_extra)
+        if self.straggler_first:
+            self.solver.order_by_iters(self.iters, self._order)
+        self.solver.rollout(self.p, self.x, self.lb, self.ub, self.lam, self.status, self.iters, tau, t_rel, crossed,
+                            self.o_spl, self.n_spl, self.basis.degree, self.basis.knots, 1.0 / self.T, self.p_offs, self.o_t,
+                            obstacles=self.obst, dt=self.update_time, shift_entries=self.shift_entries, shift_T=self.shift_mats,
+                            lam_perm=self.perm, cross_options=self.cross_options or None, iters_log=iters_log, status_log=status_log)
+
+    def _norm(self, a):
+        return a.norm(dim=1)
+
+    def _stop_rule(self, o_pose):
+        """The rule is the solve kernel's: registered with the handle (o_pose None: taken off)."""
+        self.under_way = None if o_pose is None else self.torch.ones(self.B, dtype=self.torch.int32, device=self.dev)
+        where = () if o_pose is None else (self.o_state0, self.o_input0, o_pose, self.n_dim, self.stop_tol)
+        self.solver.set_stop(*where, under_way=self.under_way)
+
+    def _signals_alloc(self, shape):
+        t = self.torch
+        return (t.zeros(shape, dtype=t.float64, device=self.dev), t.zeros(self.B, dtype=t.int32, device=self.dev),
+                t.zeros(self.B, dtype=t.int32, device=self.dev))
+
+    def _signals_args(self):
+        g = self._sig
+        return dict(coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree, knots=self.basis.knots, n_samp=g['n_samp'],
+                    p_t=self.o_t, sample_time=g['sample_time'], inv_T=1.0 / self.T)
+
+    def _signals_fused(self, on):
+        """The append inside the solve / rollout kernel, on or off."""
+        if not on:
+            return self.solver.set_signals(None)
+        g = self._sig
+        self.solver.set_signals(g['log'], g['count'], g['overflow'], **self._signals_args())
+
+    def _signals_append_now(self):
+        """One append of the current plan (x at the time p[:, t]) outside a solve: the stand-alone kernel."""
+        g = self._sig
+        self.solver.signals_append(self.x, self.p, g['log'], g['count'], g['overflow'], under_way=self.under_way, **self._signals_args())
+
+    def _signals_summary(self, target):
+        g, t = self._sig, self.torch
+        out = t.zeros((self.B, 8), dtype=t.float64, device=self.dev)
+        self.solver.signals_reduce(g['log'], g['count'], target.contiguous(), out, **self._signals_args())
+        return out
+
+
+class HostP2P(BatchP2P):
+    """The host executor (`ops=<solver object>`, anything with the `solve(template, p, x0, ...)` signature of the tests' oracle
+    port binding): numpy arrays as plain attributes, the glue in numpy statements, the solves by `port`.  Optionally a `pool`
+    (attached after construction, bench.py's CPU baseline: `solve(p, x, lam, status, iters, dw, step=...)`) whose workers run glue
+    AND solve of a step per agent: `step` then only hands it the clock -- no stop rule, no log."""
+    kind = 'host'
+
+    def _allocate(self, P, ops, device):
+        self.port = ops                          # injected by tests / bench.py's cpu_baseline leg
+        self.n_threads = 1
+        self.pool = None
+        self.dw = np.zeros(self.B)            # inertia correction carried between warm solves
+        self.p, self.x = np.ascontiguousarray(P['p'], dtype=float).copy(), np.ascontiguousarray(P['x0'], dtype=float).copy()
+        self.lam = np.zeros((self.B, self.tpl.n_con))
+        self.status, self.iters = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+        self._log_in_solve = True                # (`_signals_fused`)
+
+    def step(self, events=None, before_solve=None):
+        if self.pool is None:
+            return BatchP2P.step(self, events, before_solve)
+        t_now, tau, t_rel, crossed = step_clock(self.time, self.update_time, self.knot_time, self.T)
+        self.time = t_now
+        self._solve(True, step_desc=self._pool_step(tau, t_rel, crossed), extra=self.cross_options if crossed else None)
+        return crossed
+
+    def _pool_step(self, tau, t_rel, crossed):
+        """Constants of this step for a pool that runs the glue per agent in its workers (field names of the `StepDesc` the pool defines)."""
+        desc = self.pool.step_desc()
+        rows = [np.ascontiguousarray(r) for r in self._eval_rows(tau)]
+        if len(rows) != 2 or self.n_spl != self.n_dim:
+            raise NotImplementedError('the pool step glue carries state0 / input0 only')
+        E, Ed = rows
+        obst = np.ascontiguousarray(np.array(self.obst, dtype=np.int32).reshape(-1, 4))
+        perm = np.ascontiguousarray(self.perm, dtype=np.int64)
+        ents = np.ascontiguousarray(self.shift_entries, dtype=np.int32)
+        mats = np.ascontiguousarray(self.shift_mats, dtype=np.float64)
+        desc._keep = (E, Ed, obst, perm, ents, mats)
+        desc.o_spl, desc.n_dim, desc.L = self.o_spl, self.n_dim, self.L
+        desc.o_state0, desc.o_input0, desc.o_t = self.o_state0, self.o_input0, self.o_t
+        desc.t_rel, desc.dt = t_rel, self.update_time
+        desc.E, desc.Ed = E.ctypes.data, Ed.ctypes.data
+        desc.n_obst, desc.obst = len(self.obst), obst.ctypes.data
+        desc.crossed, desc.n_shift = int(crossed), len(ents)
+        desc.shift_entries, desc.shift_mats, desc.perm = ents.ctypes.data, mats.ctypes.data, perm.ctypes.data
+        return desc
+
+    def _predict(self, tau, t_rel):
+        c = self.x[:, self.o_spl:self.o_spl + self.n_spl * self.L].reshape(self.B, self.n_spl, self.L)
+        for o, E in enumerate(self._eval_rows(tau)):
+            self.p[:, self.p_offs[o]:self.p_offs[o] + self.n_spl] = c @ E
+        self.p[:, self.o_t] = t_rel
+
+    def _shift(self):
+        for (lo, rows, cols, _), Tm in self._shift_dense:
+            blk = self.x[:, lo:lo + rows * cols].reshape(self.B, cols, rows)
+            self.x[:, lo:lo + rows * cols] = (blk @ Tm.T).reshape(self.B, -1)
+        self.lam = np.where(self.perm >= 0, self.lam[:, np.maximum(self.perm, 0)], 0.0)
+
+    def _solve(self, warm, events=None, ordered=False, extra=None, step_desc=None):
+        kw = dict(self.opts, warm_start=int(warm), max_iter=self.max_iter_step if warm else self.max_iter_cold, **(extra or {}))
+        if self.pool is not None:
+            if self.under_way is not None or self._sig is not None:
+                raise NotImplementedError('stop_at_arrival / record_signals: not with a host pool (its workers run the step glue themselves)')
+            if not warm:
+                self.lam[:] = 0.
+            self.pool.solve(self.p, self.x, self.lam, self.status, self.iters, self.dw, step=step_desc, **kw)
+            return
+        if self.under_way is None:
+            r = self.port.solve(self.tpl, self.p, self.x, lam_g0=self.lam if warm else None, status0=self.status if warm else None,
+                                n_threads=self.n_threads, dw_state=self.dw, **kw)
+            self.x, self.lam, self.status, self.iters = r['x'], r['lam_g'], r['status'], r['iters']
+        else:
+            # the stop rule as the solve kernel applies it: the criterion on p ends an agent's loop for good; the agents
+            # under way are solved as a batch of their own (independent problems: the same results), the others keep
+            # their plan, their multipliers and their status, iters = 0
+            self.under_way &= ~self.arrived(self.stop_tol)
+            idx = np.flatnonzero(self.under_way)
+            self.iters = np.zeros(self.B, dtype=np.int32)
+            if len(idx):
+                dw = self.dw[idx].copy()
+                r = self.port.solve(self.tpl, self.p[idx], self.x[idx], lam_g0=self.lam[idx] if warm else None,
+                                    status0=self.status[idx] if warm else None, n_threads=self.n_threads, dw_state=dw, **kw)
+                self.x[idx], self.lam[idx], self.status[idx], self.iters[idx], self.dw[idx] = r['x'], r['lam_g'], r['status'], r['iters'], dw
+        if self._log_in_solve:
+            self._signals_append_host(self.under_way)
+
+    def _cold(self, bends, fused):
+        self._solve(False)
+        return 0
+
+    def _norm(self, a):
+        return np.linalg.norm(a, axis=1)
+
+    def _stop_rule(self, o_pose):
+        """The rule is `_solve`'s: it tests `arrived` and solves the agents under way (o_pose None: taken off)."""
+        self.under_way = None if o_pose is None else np.ones(self.B, dtype=bool)
+
+    def _signals_alloc(self, shape):
+        if self.pool is not None:
+            raise NotImplementedError('record_signals: not with a host pool (its workers run the step glue themselves)')
+        return np.zeros(shape), np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
+
+    def _signals_fused(self, on):
+        """The append at the end of `_solve`, on or off."""
+        self._log_in_solve = bool(on)
+
+    def _signals_append_now(self):
+        self._signals_append_host(self.under_way)
+
+    def _signals_append_host(self, under_way):
+        """`omgx_batch_signals_append` in numpy: the same semantics, `Basis.eval_basis` / `derivative` as `_eval_rows`."""
+        g = self._sig
+        if g is None:
+            return
+        L, ns, n_samp, cap, st = self.L, self.n_spl, g['n_samp'], g['cap'], g['sample_time']
+        inv_T = 1.0 / self.T
+        bases = [(self.basis, None)] + [self.basis.derivative(o) for o in range(1, g['n_der'])]
+        for b in range(self.B):
+            if under_way is not None and not under_way[b]:
+                continue
+            cnt = int(g['count'][b])
+            first = 0 if cnt == 0 else 1
+            n_col = n_samp + 1 - first
+            if cnt + n_col > cap:
+                g['overflow'][b] = 1
+                continue
+            t_rel = float(self.p[b, self.o_t])
+            u = (t_rel + np.arange(first, n_samp + 1) * st) * inv_T
+            c = self.x[b, self.o_spl:self.o_spl + ns * L].reshape(ns, L)
+            for o, (dbasis, Po) in enumerate(bases):
+                E = dbasis.eval_basis(u) if o == 0 else dbasis.eval_basis(u) @ Po * inv_T ** o
+                g['log'][b, o, :, cnt:cnt + n_col] = c @ E.T
+            g['count'][b] = cnt + n_col
+
+    def _signals_summary(self, target):
+        return signals_summary_numpy(self._sig['log'], self._sig['count'], target, self._sig['sample_time'])
 
 
 def signals_summary_numpy(log, count, target, sample_time):
@@ -664,7 +663,7 @@ class StreamedP2P(object):
             Ps = dict(P, p=P['p'][lo:hi], x0=P['x0'][lo:hi])
             st.wait_event(ready)
             with torch.cuda.stream(st):
-                self.parts.append(BatchP2P(problem, Ps, ops='hip', device=self.dev, **kw))
+                self.parts.append(DeviceP2P(problem, Ps, device=self.dev, **kw))
         self.B = B
         self.kind = 'hip'
         self.tpl, self.problem = self.parts[0].tpl, problem

@@ -48,7 +48,7 @@ import numpy as np
 
 from .opti import OptiChild, OptiFather
 from .problems import FixedTPoint2point
-from .splines import shift_knot1_fwd, shiftfirstknot_T, shiftoverknot_T, since_knot
+from .splines import shift_knot1_fwd, shiftfirstknot_T, shiftoverknot_T, since_knot, step_clock
 from .consensus import (coupling_matrix, zupdate_matrices, FormationLayout, circular_neighbors, reverse_slots,      # noqa: F401
                         shift_tables)
 from .symbolic import Poly
@@ -294,15 +294,13 @@ class FormationPoint2point(object):
         import time
         t0 = time.time()
         # knot crossing: shift the warm start of x and the whole consensus state (`admm.py:477-491`)
-        crossing = int(np.round(self._time_prev / self.knot_time, 6)) < int(np.round(current_time / self.knot_time, 6))
-        t_rel = since_knot(current_time, self.knot_time)
+        _, tau, t_rel, crossing = step_clock(self._time_prev, current_time - self._time_prev, self.knot_time,
+                                             float(self.options['horizon_time']), t_now=current_time)
         if self._device_prediction(current_time, update_time, crossing):
             # Nobody disturbs the vehicles (`ideal_prediction`, `vehicles/vehicle.py:323-326`): the initial conditions of this
             # update are the current plan `update_time` ahead -- one launch on the resident plan (`FormationMPC.step`) instead
             # of packing every vehicle's parameter vector on the host.  What the fleet shares (obstacle motion, T) comes from
             # ONE sub-problem's parameters and is written to all rows; rel_pos_c, poseT and rho do not change between updates.
-            rel_prev = since_knot(self._time_prev, self.knot_time)
-            tau = (rel_prev + (current_time - self._time_prev)) / float(self.options['horizon_time'])
             veh = self.vehicles[0]
             self.ops.predict(self._o_plan, veh.n_spl, veh.basis, tau, 1.0 / float(self.options['horizon_time']),
                              [self.lay.p_state0, self.lay.p_input0], self.lay.p_t, t_rel)

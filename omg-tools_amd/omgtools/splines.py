@@ -384,6 +384,32 @@ def since_knot(t, knot_time):
     return 0.0 if knot_time - rel < 1e-9 else rel
 
 
+def step_clock(t_prev, dt, knot_time, T, t_now=None):
+    """The clock of one receding-horizon update from t_prev to t_now = t_prev + dt (a caller that is handed the time of the
+    update instead of forming it passes `t_now` and dt = t_now - t_prev).  Returns (t_now, tau, t_rel, crossed): tau = where on
+    the current plan (in units of the horizon T) the ideal prediction reads the initial conditions of the update; t_rel = the
+    parameter `t` of the update (`since_knot`); crossed = the horizon start passed a knot (`point2point.py:190-193`: shift the
+    warm start).  The one statement of it: the stepwise loop, the rollout's step list and the formation loop demand the same
+    bits from it."""
+    if t_now is None:
+        t_now = t_prev + dt
+    rel_prev = since_knot(t_prev, knot_time)
+    tau = (rel_prev + dt) / T
+    crossed = int(np.round(t_prev / knot_time, 6)) < int(np.round(t_now / knot_time, 6))
+    t_rel = since_knot(t_now, knot_time)
+    return t_now, tau, t_rel, crossed
+
+
+def advance_obstacles(p, obst, dt):
+    """The moving obstacles of `obst` [(o_x, o_v, o_a, n_dim)] advanced by dt in the parameter array p [B, *] (numpy or torch, in
+    place) between two updates: x <- x + v dt + a dt^2 / 2, v <- v + a dt (`environment/obstacle.py:246-264` without bouncing).
+    These statements in this order: the rollout kernel reproduces their rounding."""
+    for ox, ov, oa, nd in obst:
+        px, pv, pa = p[:, ox:ox + nd], p[:, ov:ov + nd], p[:, oa:oa + nd]
+        px += dt * pv + (0.5 * dt * dt) * pa
+        pv += dt * pa
+
+
 def shiftoverknot_T(basis):
     """Warm-start matrix when the horizon start passes the first interior knot:
     the new coefficients describe s(tau + delta) on the same (uniform) knot

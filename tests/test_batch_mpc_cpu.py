@@ -181,6 +181,30 @@ def test_stop_at_arrival_ends_an_agents_loop_like_the_reference():
     assert ruled.under_way is None
 
 
+def test_step_clock_is_the_statements_of_the_step():
+    """`omgtools.splines.step_clock`, the one clock of `BatchP2P.step`, `BatchP2P.rollout` and `FormationMPC.step`: over 200 consecutive
+    updates from 0 (past t = T = 10.0, the case `since_knot` exists for) its four outputs equal -- bit for bit -- the statements the
+    step carried inline before, written out here; a caller that is handed the time of the update (`t_now=`) gets the same."""
+    from omgtools.splines import since_knot, step_clock
+    T = 10.0
+    for knot_time in (0.5, 1.0):
+        for update_time in (0.1, 0.25):
+            t, n_crossed = 0.0, 0
+            for _ in range(200):
+                t_prev = t
+                t_now = t_prev + update_time
+                rel_prev = since_knot(t_prev, knot_time)
+                tau = (rel_prev + update_time) / T
+                crossed = int(np.round(t_prev / knot_time, 6)) < int(np.round(t_now / knot_time, 6))
+                t_rel = since_knot(t_now, knot_time)
+                got = step_clock(t_prev, update_time, knot_time, T)
+                assert got == (t_now, tau, t_rel, crossed) and type(got[3]) is bool
+                assert step_clock(t_prev, t_now - t_prev, knot_time, T, t_now=t_now) == (t_now, (rel_prev + (t_now - t_prev)) / T, t_rel, crossed)
+                n_crossed += crossed
+                t = t_now
+            assert t > T and n_crossed == int(np.round(t / knot_time, 6))
+
+
 def test_the_knot_clock_is_consistent_where_the_reference_statement_is_not():
     """`omgtools.splines.since_knot`: the reference's `np.round(t, 6) % knot_time` (`problems/point2point.py:177`) everywhere but
     where it contradicts the reference's own crossing test (`point2point.py:190-193`): T = 10 s, 11 knot intervals, t = 10.0 -- the
