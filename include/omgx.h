@@ -250,6 +250,14 @@ int  omgx_batch_order_by_iters(omgx_batch* b, const int32_t* iters_device, int32
 int  omgx_batch_set_restarts(omgx_batch* b, const double* x0_alt_device, int32_t n_alt, int32_t* attempts_device);
 /* LDS bytes the solve kernel needs per agent (for diagnostics / DESIGN.md). */
 int  omgx_batch_lds_bytes(const omgx_batch* b);
+/* (OMGX_HAS_LAST_INSTANCE) Which instance of the solve kernel the last omgx_batch_solve launched: 0 = the full one, 1 = the lean
+ * one -- the same solve with the code of the optional features compiled out (register pressure: DESIGN.md §4.1).  The library
+ * picks per launch: lean exactly when the launch uses none of omgx_batch_set_stop, omgx_batch_set_store / set_signals,
+ * omgx_batch_set_center, omgx_batch_set_prepare, OMGX_ONLY_FAILED, omgx_batch_set_restarts (guesses or attempts), compl_inf_tol /
+ * constr_viol_tol > 0 and refine, and the template is of a class that has such an instance (not general, wave path, workspace modes
+ * 0, 4, 5).  The same bits either way; 0 before the first solve.  For tests and diagnostics. */
+#define OMGX_HAS_LAST_INSTANCE 1
+int  omgx_batch_last_instance(const omgx_batch* b);
 /* Workspace placement chosen at create: mode 0 = every per-agent array in LDS; 1 = KKT store in an
  * HBM slab (leaf panels by columns); 2 = + Jacobian values; 3 = + the per-row arrays (the O(n_var)
  * vectors, the matrix descriptors and a copy of the root block stay in LDS); 4 = compact KKT store and row arrays in
@@ -331,7 +339,7 @@ int  omgx_batch_set_prepare(omgx_batch* b, int32_t on);
  * target) before it solves an agent with under_way = 1; if it holds the flag is cleared for good.  An agent whose flag is 0 is not
  * solved: x <- x0 (it keeps its plan), lam_g and status stay as they are, iters = 0, the launch statistics and the fused
  * trajectory store skip it.  The agents under way are solved exactly as without the rule (same bits).  under_way = NULL switches
- * the rule off.  While the rule is on every solve does its own setup (omgx_batch_set_prepare is ignored).  omgx_batch_rollout applies
+ * the rule off.  A negative stop_tol is a rule that never holds: every agent is solved at every update.  While the rule is on every solve does its own setup (omgx_batch_set_prepare is ignored).  omgx_batch_rollout applies
  * the rule at the same place of a step (after prediction, obstacle motion and knot-crossing shift): the agent's loop inside the call
  * ends there -- x, p, lam_g, status stay as they are at that step, the remaining steps log iters 0. */
 int  omgx_batch_set_stop(omgx_batch* b, int32_t o_state0, int32_t o_input0, int32_t o_poseT, int32_t n_dim, double stop_tol,

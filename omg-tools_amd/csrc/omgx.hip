@@ -5,6 +5,11 @@
 //                      solve with every per-agent array resident in LDS
 //                      (<= 160 KiB / CU); only p, x0, bounds are read from HBM and
 //                      x, lam_g, status written back.
+//                      Instances: per workspace mode, general or not, and -- for the benchmark
+//                      classes (wave path, modes 0 / 4 / 5) -- REFINE (refinement of regularised steps)
+//                      and LEAN (every optional block compiled out: stop rule, restarts, prepared
+//                      setup, ADMM centre, fused store / log, absolute tolerances).  omgx_batch_solve
+//                      picks per launch: LEAN exactly when the launch uses none of them.
 //   sample_kernel      post-solve trajectory sampling (reference
 //                      `vehicles/vehicle.py:250-300`, `spline_extra.py:406-410`,
 //                      C++ `Vehicle::sampleSplines` Vehicle.cpp:112-129): the
@@ -280,7 +285,12 @@ signals_reduce_kernel(const double* __restrict__ log, const int32_t* __restrict_
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
-template <int MODE, bool WAVE_ONLY, bool GEN, bool REFINE = false>
+// LEAN: the instance for launches that leave every optional feature off -- no stop rule, no fused store / signals, no ADMM centre, no
+// prepared setup, no restart pass or restart guesses, no absolute tolerances (omgx::CtxT kLean), no refinement: the plain
+// receding-horizon solve of the benchmark classes.  Those blocks are compiled out (the arguments stay: one signature, one launch
+// site); omgx_batch_solve picks the instance per launch from what it is about to pass (lean_launch).  What stays is what such a
+// launch uses: order, stats, dw_state, stagger, prio_iter, warm start, the dynamic slot hand-out, bounds_shared.
+template <int MODE, bool WAVE_ONLY, bool GEN, bool REFINE = false, bool LEAN = false>
 __global__ void __launch_bounds__(512)
 ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
                  const double* __restrict__ p, const double* __restrict__ x0,
@@ -296,7 +306,7 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
   omgx::Work w;
     omgx::work_carve_split<MODE>(w, lds, MODE == omgx::WS_LDS ? nullptr : slabs + (size_t)blockIdx.x * slab_doubles,
                                d, kkt_doubles);
-  omgx::CtxT<omgx::ws_kkt_hbm(MODE), WAVE_ONLY, omgx::ws_root_lds(MODE), GEN, false, REFINE> c; c.red = w.red;
+  omgx::CtxT<omgx::ws_kkt_hbm(MODE), WAVE_ONLY, omgx::ws_root_lds(MODE), GEN, false, REFINE, LEAN> c; c.red = w.red;
 #ifdef OMGX_PROFILE
   __shared__ long long prof_lds[omgx::PH_COUNT];
   c.prof = prof_lds;
@@ -306,9 +316,9 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
   // `prep` (round 6): the setup of every agent's solve -- parameter stage, Jacobian and rows at x0, classification, scaling, start
   // values -- was done for the whole batch by ipm_prepare_kernel ahead of this launch; a solve then starts by loading its record.
   // The matrix descriptors (the same for every agent) are written once per workgroup.
-  double* const jval_own = w.jval;
+  [[maybe_unused]] double* const jval_own = w.jval;      // (the lean instance never rebinds w.jval)
   // (the descriptors are rewritten per solve only where the fused trajectory store may use the space behind a small KKT store as scratch)
-  const bool describe_once = prep != nullptr || stp == nullptr;
+  const bool describe_once = LEAN || prep != nullptr || stp == nullptr;
   if (describe_once) { omgx::Kkt K0; K0.bind(d, T, w.kkt); omgx::kkt_describe(c, d, K0, w, true); }
   // mode 0: one workgroup per agent.  Spill modes: the grid is capped at the number of HBM
   // slabs and every workgroup walks over its agents.
@@ -333,10 +343,11 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
       __syncthreads();
     }
     // restart pass (OMGX_ONLY_FAILED): agents that are solved already keep x, lam_g, status, iters
-    if (only_failed && status[b] == 0) continue;
+    if constexpr (!LEAN) { if (only_failed && status[b] == 0) continue; }
     // stop rule (omgx_batch_set_stop): a vehicle whose loop has ended -- the criterion held at this or an earlier update -- is not
     // solved again: it keeps its plan (x <- x0), its multipliers and its status; iters = 0.  Every thread evaluates the same
     // numbers from the same loads (a thread that reads the flag after thread 0 cleared it takes the same branch).
+    if constexpr (!LEAN)
     if (stop) {
       const StopArgs sa = *stop;
       bool go = sa.under_way[b] != 0;
@@ -359,6 +370,13 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
     // would leave the chip to a handful of them for as long as their slowest solve takes.
     omgx::Result r;
     int attempt = 0;
+    if constexpr (LEAN) {      // (one setup, one iteration: the statements of attempt 0 below without a prepared record)
+      const omgx::Start st = omgx::ipm_setup(c, d, T, o, w, p + (size_t)b * d.n_par, x0 + (size_t)b * d.n_var, lbb, ubb,
+                                             o.warm_start ? lam + (size_t)b * d.n_con : nullptr, o.warm_start ? status[b] : 0, kkt_doubles, false);
+      r = omgx::ipm_iterate(c, d, T, o, w, lbb, ubb, st, kkt_doubles, o.warm_start ? dw_state[b] : 0.0);
+      __builtin_amdgcn_s_setprio(0);
+      __syncthreads();
+    } else
     for (;;) {
       const double* xs = attempt == 0 ? x0 + (size_t)b * d.n_var : x0_alt + ((size_t)(attempt - 1) * n_agents + b) * d.n_var;
       omgx::Start st;
@@ -377,7 +395,7 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
       if (r.status == 0 || o.warm_start || attempt >= n_alt) break;
       ++attempt;
     }
-    if (attempts && threadIdx.x == 0) attempts[b] = attempt;
+    if constexpr (!LEAN) { if (attempts && threadIdx.x == 0) attempts[b] = attempt; }
     for (int i = threadIdx.x; i < d.n_var; i += blockDim.x) x[(size_t)b * d.n_var + i] = w.x[i];
     for (int q = threadIdx.x; q < d.n_con; q += blockDim.x)
       lam[(size_t)b * d.n_con + q] =
@@ -391,6 +409,7 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
         atomicAdd(stats + 3, 1ull);
       }
     }
+    if constexpr (!LEAN)
     if (ctr) {
       // the ADMM x-update's centre (`omgx_admm_center_ex`) from the solution in LDS: no launch of its own
       const CenterArgs ca = *ctr;
@@ -402,6 +421,7 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
         if (slot >= 0) ca.x_send[(size_t)slot * ns + q] = v;
       }
     }
+    if constexpr (!LEAN)
     if (stp) {
       // `Vehicle.store` fused behind the solve (reference `vehicles/vehicle.py:250-300`): the trajectories of
       // this agent straight from the solution in LDS; the KKT store is free now and serves as scratch
@@ -533,13 +553,24 @@ typedef void (*ipm_kernel_t)(omgx::Dims, omgx::Tables, omgx::Opts, int, const do
 // (GEN: the instance that carries the terms with four factors, the cos / sin atoms and the basis rows of any degree --
 // Dims::general; the other one is the kernel of the benchmark classes, free of that code)
 template <bool GEN>
-static ipm_kernel_t ipm_kernel_gen(int mode, int wave_ok, int refine = 0) {
+static ipm_kernel_t ipm_kernel_gen(int mode, int wave_ok, int refine = 0, int lean = 0) {
   // (the refinement of regularised steps -- omgx_options.refine -- has instances of its own: templates on the wave path, not general)
   if (refine && wave_ok && !GEN) {
     switch (mode) {
       case omgx::WS_LDS: return ipm_solve_kernel<omgx::WS_LDS, true, false, true>;
       case omgx::WS_JAC_ONLY: return ipm_solve_kernel<omgx::WS_JAC_ONLY, true, false, true>;
       case omgx::WS_JAC_HV: return ipm_solve_kernel<omgx::WS_JAC_HV, true, false, true>;
+      default: break;
+    }
+  }
+  // (and so have the launches with every optional feature off -- LEAN above: the same three modes; not with the refinement)
+  if (lean && !refine && wave_ok && !GEN) {
+    switch (mode) {
+#ifndef OMGX_ONLY_HEADLINE
+      case omgx::WS_LDS: return ipm_solve_kernel<omgx::WS_LDS, true, false, false, true>;
+      case omgx::WS_JAC_ONLY: return ipm_solve_kernel<omgx::WS_JAC_ONLY, true, false, false, true>;
+#endif
+      case omgx::WS_JAC_HV: return ipm_solve_kernel<omgx::WS_JAC_HV, true, false, false, true>;
       default: break;
     }
   }
@@ -557,8 +588,8 @@ static ipm_kernel_t ipm_kernel_gen(int mode, int wave_ok, int refine = 0) {
   }
 #endif
 }
-static ipm_kernel_t ipm_kernel_for(int mode, int wave_ok, int general, int refine = 0) {
-  return general ? ipm_kernel_gen<true>(mode, wave_ok) : ipm_kernel_gen<false>(mode, wave_ok, refine);
+static ipm_kernel_t ipm_kernel_for(int mode, int wave_ok, int general, int refine = 0, int lean = 0) {
+  return general ? ipm_kernel_gen<true>(mode, wave_ok) : ipm_kernel_gen<false>(mode, wave_ok, refine, lean);
 }
 
 template <typename OutT>
@@ -1109,6 +1140,7 @@ struct omgx_batch {
   StopArgs* d_stop = nullptr;       // omgx_batch_set_stop: device copy of the arguments
   StopArgs stop_host = {};          // (and the host copy: omgx_batch_rollout hands it to its kernel inside RolloutArgs)
   bool stop_on = false;
+  int last_instance = 0;            // solve-kernel instance of the last omgx_batch_solve launch: 0 full, 1 lean (omgx_batch_last_instance)
   CenterArgs* d_center = nullptr;   // omgx_batch_set_center: device copy of the arguments (nullptr: off); the slot map behind it
   int32_t* d_pub_inv = nullptr;
   bool center_on = false;
@@ -1682,6 +1714,11 @@ int omgx_batch_create(const omgx_template* tpl, int32_t n_agents, int32_t device
                           reserved) != hipSuccess) {      // (the instance with the refinement of regularised steps, omgx_options.refine)
     g_err = "cannot reserve dynamic LDS for ipm_solve_kernel"; omgx_batch_destroy(b); return OMGX_E_HIP;
   }
+  if (ipm_kernel_for(b->ws_mode, b->dims.wave_ok, b->dims.general, 0, 1) != ipm_kernel_for(b->ws_mode, b->dims.wave_ok, b->dims.general) &&
+      hipFuncSetAttribute((const void*)ipm_kernel_for(b->ws_mode, b->dims.wave_ok, b->dims.general, 0, 1), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          reserved) != hipSuccess) {      // (the lean instance: launches with every optional feature off)
+    g_err = "cannot reserve dynamic LDS for ipm_solve_kernel"; omgx_batch_destroy(b); return OMGX_E_HIP;
+  }
   if (ipm_rollout_t rk = rollout_kernel_for(b->ws_mode, b->dims.wave_ok, b->dims.general)) {
     if (hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, reserved) != hipSuccess) {
       g_err = "cannot reserve dynamic LDS for ipm_rollout_kernel"; omgx_batch_destroy(b); return OMGX_E_HIP;
@@ -1743,7 +1780,7 @@ int omgx_batch_set_stop(omgx_batch* b, int32_t o_state0, int32_t o_input0, int32
   b->stop_on = false;      // (a failed registration leaves the rule OFF)
   const int np = b->dims.n_par;
   if (n_dim <= 0 || o_state0 < 0 || o_input0 < 0 || o_poseT < 0 || o_state0 + n_dim > np || o_input0 + n_dim > np || o_poseT + n_dim > np ||
-      !(stop_tol >= 0.0)) { g_err = "stop rule: parameter offsets out of range or a negative tolerance"; return OMGX_E_INVALID; }
+      stop_tol != stop_tol) { g_err = "stop rule: parameter offsets out of range or a tolerance that is not a number"; return OMGX_E_INVALID; }      // (a negative tolerance is a rule that never holds: every agent is solved at every update)
   HIPCHK(hipSetDevice(b->device));
   if (!b->d_stop) HIPCHK(hipMalloc((void**)&b->d_stop, sizeof(StopArgs)));
   StopArgs sa;
@@ -1824,6 +1861,8 @@ int omgx_batch_order_by_iters(omgx_batch* b, const int32_t* iters_device, int32_
 }
 
 int omgx_batch_lds_bytes(const omgx_batch* b) { return b ? (int)b->lds_bytes : OMGX_E_INVALID; }
+
+int omgx_batch_last_instance(const omgx_batch* b) { return b ? b->last_instance : OMGX_E_INVALID; }
 
 int omgx_batch_workspace(const omgx_batch* b, int32_t* mode, int64_t* lds_bytes, int64_t* hbm_bytes_per_slab, int32_t* n_slabs) {
   if (!b) return OMGX_E_INVALID;
@@ -1907,14 +1946,26 @@ int omgx_batch_solve(omgx_batch* b, const double* p, const double* x0, const dou
     HIPCHK(hipGetLastError());
     e0 = nullptr;
   }
-  hipExtLaunchKernelGGL(ipm_kernel_for(b->ws_mode, b->dims.wave_ok, b->dims.general, b->opts.refine), dim3(b->n_slabs), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream,
+  // What this launch hands to the optional blocks of the kernel; with all of it null or zero, both absolute tolerances off and no
+  // refinement it runs the lean instance (LEAN of ipm_solve_kernel: those blocks compiled out).  Decided here, per launch, from the
+  // handle's state: switching a feature on or off between two launches switches the instance, nothing else to call.
+  const StoreArgs* k_stp = (b->store.out || b->signals.log) ? &b->d_store->st : nullptr;
+  const int k_only_failed = (flags & OMGX_ONLY_FAILED) ? 1 : 0, k_n_alt = b->d_x0_alt ? b->n_alt : 0;
+  const CenterArgs* k_ctr = b->center_on ? b->d_center : nullptr;
+  double* k_prep = prepared ? b->d_prep : nullptr;
+  const StopArgs* k_stop = b->stop_on ? b->d_stop : nullptr;
+  const bool lean_launch = !k_stp && !k_only_failed && !k_n_alt && !b->d_attempts && !k_ctr && !k_prep && !k_stop &&
+                           !(b->opts.compl_tol > 0.0) && !(b->opts.viol_tol > 0.0) && !b->opts.refine;
+  const ipm_kernel_t kern_full = ipm_kernel_for(b->ws_mode, b->dims.wave_ok, b->dims.general, b->opts.refine);
+  const ipm_kernel_t kern = lean_launch ? ipm_kernel_for(b->ws_mode, b->dims.wave_ok, b->dims.general, 0, 1) : kern_full;
+  b->last_instance = kern != kern_full ? 1 : 0;      // (classes without a lean instance -- general, off the wave path, spill modes -- get the full one back)
+  hipExtLaunchKernelGGL(kern, dim3(b->n_slabs), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream,
                         e0, e1, 0u, d, b->dev,
                         b->opts, b->kkt_doubles, kp, kx0, klb, kub, shared ? 1 : 0, kx, klam, kst, kit, B, b->d_prof,
-                        b->d_slabs, b->slab_doubles, b->d_dw, b->d_order, (const StoreArgs*)((b->store.out || b->signals.log) ? &b->d_store->st : nullptr), (flags & OMGX_ONLY_FAILED) ? 1 : 0,
-                        b->d_next, b->d_x0_alt, b->d_x0_alt ? b->n_alt : 0, b->d_attempts,
+                        b->d_slabs, b->slab_doubles, b->d_dw, b->d_order, k_stp, k_only_failed,
+                        b->d_next, b->d_x0_alt, k_n_alt, b->d_attempts,
                         (unsigned long long*)(b->d_stats ? b->d_stats + 4 * (size_t)(b->stats_launch++ % b->stats_slots) : nullptr),
-                        b->stagger, (const CenterArgs*)(b->center_on ? b->d_center : nullptr),
-                        prepared ? b->d_prep : (double*)nullptr, b->prep_doubles, (const StopArgs*)(b->stop_on ? b->d_stop : nullptr));
+                        b->stagger, k_ctr, k_prep, b->prep_doubles, k_stop);
   HIPCHK(hipGetLastError());
   if (ranged)
     hipLaunchKernelGGL(range_contract_lam, dim3((B * nu + 255) / 256), dim3(256), 0, b->stream, (const double*)b->d_lam, lam_user_dev, B, nu, ni,

@@ -346,7 +346,7 @@ OMGX_HD void work_carve(Work& w, double* base, const Dims& d, int kkt_doubles) {
 // ---------------------------------------------------------------------------
 #ifdef OMGX_HOST_PORT
 struct Ctx {
-  static constexpr bool wave_only = false, hbm = false, no_wave = false, root_lds = false, general = true, prep = false, refine = true;
+  static constexpr bool wave_only = false, hbm = false, no_wave = false, root_lds = false, general = true, prep = false, refine = true, lean = false;
   double* red;
   int tid() const { return 0; }
   int nthr() const { return 1; }
@@ -372,11 +372,17 @@ struct Ctx {
 // memory, no KKT store
 // kRefine: the instance that carries the refinement of regularised steps (Opts::refine): its second solve and its second pass through
 // the step phase cost the instance without them 2.5 % of its cycles per solve through register pressure alone (345.8 k against 337 k)
-template <bool kHbm, bool kWaveOnly = false, bool kRootLds = false, bool kGeneral = false, bool kPrep = false, bool kRefine = false>
+// kLean: the instance for launches that leave the optional features off (picked per launch by omgx_batch_solve): here the absolute
+// tolerances Opts::compl_tol / viol_tol are compile-time zeros -- their tests, the per-row division of the error-measure pass and the
+// nu escalation are not in the code; the solve kernel drops its own optional blocks on the same flag.  Like kRefine, a matter of
+// register pressure: code that is merely present costs the instance that never runs it cycles
+template <bool kHbm, bool kWaveOnly = false, bool kRootLds = false, bool kGeneral = false, bool kPrep = false, bool kRefine = false,
+          bool kLean = false>
 struct CtxT {
   static constexpr bool hbm = kHbm;
   static constexpr bool prep = kPrep;
   static constexpr bool refine = kRefine;
+  static constexpr bool lean = kLean;
   static constexpr bool general = kGeneral;
   static constexpr bool root_lds = kRootLds;      // Work::root holds the root block from the Schur step on (spill modes)
   static constexpr bool wave_only = kWaveOnly;
@@ -2235,6 +2241,11 @@ struct Start { int status, warm, use_t; double mu, zt, f; };
 // a whole batch at once, many workgroups per CU -- as a kernel of its own ahead of it (ipm_prepare_kernel, omgx.hip; C::prep:
 // the row arrays and the Jacobian values then live in the agent's record in global memory, no KKT store, no descriptors):
 // the same statements in the same order either way, the same bits.
+// The absolute tolerances of a solve (Opts::compl_tol, Opts::viol_tol; 0 = off).  The lean instances (CtxT kLean) are launched only
+// with both off: compile-time zeros there, and everything conditioned on them folds to what it computes today with both at 0
+template <class C> OMGX_HD double opt_compl_tol(const Opts& o) { if constexpr (C::lean) return 0.0; else return o.compl_tol; }
+template <class C> OMGX_HD double opt_viol_tol(const Opts& o) { if constexpr (C::lean) return 0.0; else return o.viol_tol; }
+
 template <class C>
 OMGX_FN Start ipm_setup(const C& c, const Dims& d, const Tables& T, const Opts& o, Work& w,
                         const double* p, const double* x0, const double* lb, const double* ub,
@@ -2254,7 +2265,8 @@ OMGX_FN Start ipm_setup(const C& c, const Dims& d, const Tables& T, const Opts& 
   // them are requested here, so that their latencies overlap with each other and with the parameter
   // stage (p is loaded by eval_params; the multipliers wait in w.ds, which is free until the assembly)
   const bool warm_in = o.warm_start && prev_status == 0;
-  const double tol_c = (o.compl_tol > 0.0 && o.compl_tol < o.tol) ? o.compl_tol : o.tol;      // what the complementarity has to reach
+  const double compl_tol = opt_compl_tol<C>(o);
+  const double tol_c = (compl_tol > 0.0 && compl_tol < o.tol) ? compl_tol : o.tol;      // what the complementarity has to reach
   OMGX_PFOR(i, n) w.x[i] = x0[i];
   if constexpr (!C::prep) { if (warm_in) { OMGX_PFOR(r, m) w.ds[r] = lam0[r]; } }
   if (c.tid() == 0) w.x[n] = 1.0;
@@ -2443,10 +2455,11 @@ OMGX_FN Result ipm_iterate(const C& c, const Dims& d, const Tables& T, const Opt
   if (st.status == 3) return res;
   Kkt K; K.bind(d, T, w.kkt);
   const bool warm = st.warm != 0, use_t = st.use_t != 0;
-  const double tol_c = (o.compl_tol > 0.0 && o.compl_tol < o.tol) ? o.compl_tol : o.tol;
+  const double compl_tol = opt_compl_tol<C>(o), viol_tol = opt_viol_tol<C>(o);
+  const double tol_c = (compl_tol > 0.0 && compl_tol < o.tol) ? compl_tol : o.tol;
   const double mu_floor = tol_c / 10.0;
   // (rows are tested scaled, `viol <= tol`; with viol_tol set also unscaled, folded into the same maximum: value / |rho| <= viol_tol)
-  const double viol_fold = o.viol_tol > 0.0 ? o.tol / o.viol_tol : 0.0;
+  const double viol_fold = viol_tol > 0.0 ? o.tol / viol_tol : 0.0;
   double mu = st.mu, nu = o.nu_init, zt = st.zt, f = st.f;
   double t = use_t ? 1.0 : 0.0;
   // a warm start also inherits the inertia correction the previous solve of this agent ended with
@@ -2558,7 +2571,7 @@ OMGX_FN Result ipm_iterate(const C& c, const Dims& d, const Tables& T, const Opt
     const double sd = c.uni(fmax(OMGX_S_MAX, lam_sum / fmax(1.0, cnt)) / OMGX_S_MAX);
     const double err0 = fmax(rd_max / sd, fmax(viol, zh / sd));
     res.f = f; res.mu = mu; res.t = t; res.iters = it;
-    if (err0 <= o.tol && (o.compl_tol <= 0.0 || zh <= o.compl_tol)) { status = 0; break; }
+    if (err0 <= o.tol && (compl_tol <= 0.0 || zh <= compl_tol)) { status = 0; break; }
     if (it == o.max_iter) break;
     // barrier-problem error at a given mu.  Under a heavy inertia correction (concave rows with
     // multipliers ~ mu/s: the negative curvature itself scales with mu) the damped Newton method
@@ -2589,7 +2602,7 @@ OMGX_FN Result ipm_iterate(const C& c, const Dims& d, const Tables& T, const Opt
     // (version 8, constr_viol_tol: everything but the violation of the rows is converged and the barrier parameter sits on its
     // floor -- what is left is t v_i, the shift phase I still holds: the penalty weight takes t down, a factor ten at a time)
     if (use_t && viol_fold > 0.0 && !infeasible && mu <= mu_floor && nu < OMGX_NU_MAX && viol > o.tol &&
-        fmax(rd_max, zh) / sd <= o.tol && (o.compl_tol <= 0.0 || zh <= o.compl_tol)) {
+        fmax(rd_max, zh) / sd <= o.tol && (compl_tol <= 0.0 || zh <= compl_tol)) {
       nu = c.uni(nu * 10.0); zt = c.uni(zt + 0.9 * nu);
     }
     // stall test: phase I must shrink t by at least 10 % over OMGX_STALL_ITERS (20) iterations.

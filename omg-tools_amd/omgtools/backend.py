@@ -279,6 +279,9 @@ def load_library(path=None):
     lib.omgx_batch_set_options.argtypes = [C.c_void_p, C.POINTER(COptions)]
     lib.omgx_batch_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     lib.omgx_batch_lds_bytes.argtypes = [C.c_void_p]
+    if hasattr(lib, 'omgx_batch_last_instance'):      # (OMGX_HAS_LAST_INSTANCE: not in a library built before it)
+        lib.omgx_batch_last_instance.argtypes = [C.c_void_p]
+        lib.omgx_batch_last_instance.restype = C.c_int
     lib.omgx_batch_set_order.argtypes = [C.c_void_p, C.c_void_p]
     lib.omgx_batch_order_by_iters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.omgx_batch_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
@@ -370,12 +373,16 @@ class BatchSolver(object):
 
     def workspace(self):
         """Placement chosen by the library: mode 0 = all per-agent arrays in LDS, 1..3 = KKT /
-        Jacobian / row arrays spilled to an HBM slab per persistent workgroup."""
+        Jacobian / row arrays spilled to an HBM slab per persistent workgroup.  `last_instance`: which instance of the solve
+        kernel the last solve launched (omgx_batch_last_instance: 0 full, 1 lean -- optional features compiled out)."""
         mode, nslab = C.c_int32(), C.c_int32()
         lds, hbm = C.c_int64(), C.c_int64()
         _check(self.lib, self.lib.omgx_batch_workspace(self._h, C.byref(mode), C.byref(lds), C.byref(hbm),
                                                        C.byref(nslab)), 'omgx_batch_workspace')
-        return dict(mode=mode.value, lds_bytes=lds.value, hbm_bytes_per_slab=hbm.value, n_slabs=nslab.value)
+        ws = dict(mode=mode.value, lds_bytes=lds.value, hbm_bytes_per_slab=hbm.value, n_slabs=nslab.value)
+        if hasattr(self.lib, 'omgx_batch_last_instance'):      # (OMGX_HAS_LAST_INSTANCE; an older library given by OMGX_LIB has no such entry)
+            ws['last_instance'] = int(self.lib.omgx_batch_last_instance(self._h))      # solve-kernel instance of the last solve: 0 full, 1 lean
+        return ws
 
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:
