@@ -20,14 +20,10 @@ import os
 
 import numpy as np
 
+from .backend import AdmmLayoutC
 from .distributed import shard_range
 from .consensus import zupdate_matrices, reverse_slots
 from .splines import advance_obstacles, step_clock
-
-
-class AdmmLayoutC(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ('n_dim', 'L', 'n_nghb', 'x_spl', 'p_rel',
-                                         'p_zi', 'p_zji', 'p_li', 'p_lji')]
 
 
 class HaloPlan(object):
@@ -385,20 +381,6 @@ class HipAdmmOps(object):
         self.res = torch.empty((B, 3), **f64)
         self.layc = AdmmLayoutC(layout.n_dim, layout.L, layout.n_nghb, layout.x_spl, layout.p_rel,
                                 layout.p_zi, layout.p_zji, layout.p_li, layout.p_lji)
-        lib = solver.lib
-        lib.omgx_admm_center.argtypes = [C.c_void_p, C.POINTER(AdmmLayoutC)] + [C.c_void_p] * 3
-        lib.omgx_admm_update.argtypes = [C.c_void_p, C.POINTER(AdmmLayoutC)] + [C.c_void_p] * 4 + \
-            [C.c_double] + [C.c_void_p] * 4
-        lib.omgx_admm_update_sums.argtypes = [C.c_void_p, C.POINTER(AdmmLayoutC)] + [C.c_void_p] * 4 + \
-            [C.c_double] + [C.c_void_p] * 5
-        lib.omgx_admm_communicate.argtypes = [C.c_void_p, C.POINTER(AdmmLayoutC)] + [C.c_void_p] * 5
-        lib.omgx_admm_center_ex.argtypes = [C.c_void_p, C.POINTER(AdmmLayoutC)] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]
-        lib.omgx_admm_update_ex.argtypes = [C.c_void_p, C.POINTER(AdmmLayoutC)] + [C.c_void_p] * 4 + [C.c_double] + \
-            [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32]
-        lib.omgx_admm_communicate_ex.argtypes = [C.c_void_p, C.POINTER(AdmmLayoutC)] + [C.c_void_p] * 4 + [C.c_int32] + \
-            [C.c_void_p] * 2 + [C.c_int32, C.c_int32, C.c_void_p]
-        if not os.environ.get('OMGX_NO_FUSED_CENTER'):       # (developer knob: the centre step as its own launch)
-            lib.omgx_batch_set_center.argtypes = [C.c_void_p, C.POINTER(AdmmLayoutC), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         self.zl_stride = self.nn * self.ns             # doubles between the z_ij (l_ij) rows of consecutive agents
         self.fused = False
         self.center_fused = self._xi_fresh = False
@@ -698,8 +680,6 @@ class HipAdmmOps(object):
         state z_i, l_i, z_ji, l_ji (inside p) and z_ij, l_ij (`admm.py:477-491`)."""
         lib, h = self.solver.lib, self.solver._h
         self._xi_fresh = False
-        lib.omgx_shift_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                        C.c_int32, C.c_void_p, C.c_int32]
         for data, stride, (ents, mats) in ((self.x, self.x.shape[1], shift_x), (self.p, self.p.shape[1], shift_p),
                                            (self.z_ij, self.zl_stride, shift_side),
                                            (self.l_ij, self.zl_stride, shift_side)):
@@ -713,8 +693,6 @@ class HipAdmmOps(object):
     def stage_shift(self, shift_x, shift_p, shift_side):
         """The shift tables of `shift` uploaded ahead of the loop (n_rows = 0: nothing launched)."""
         lib, h = self.solver.lib, self.solver._h
-        lib.omgx_shift_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                        C.c_int32, C.c_void_p, C.c_int32]
         for stride, (ents, mats) in ((self.x.shape[1], shift_x), (self.p.shape[1], shift_p), (self.zl_stride, shift_side)):
             ents = np.ascontiguousarray(ents, dtype=np.int32)
             mats = np.ascontiguousarray(mats, dtype=np.float64)

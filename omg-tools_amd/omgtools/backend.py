@@ -208,7 +208,6 @@ def save_template(tpl, path, lib=None):
     reference's exporter does with the generated nlp.so (`export/export.py:236-262`)."""
     lib = lib or load_library()
     ct, keep = make_ctemplate(tpl)
-    lib.omgx_template_write.argtypes = [C.POINTER(CTemplate), C.c_char_p]
     _check(lib, lib.omgx_template_write(C.byref(ct), os.fsencode(path)), 'omgx_template_write')
     return path
 
@@ -217,13 +216,10 @@ def read_template_counts(path, lib=None):
     """The counts of a template file as `omgx_template_read` returns them (the arrays stay in the library)."""
     lib = lib or load_library()
     out = C.POINTER(CTemplate)()
-    lib.omgx_template_read.argtypes = [C.c_char_p, C.POINTER(C.POINTER(CTemplate))]
     _check(lib, lib.omgx_template_read(os.fsencode(path), C.byref(out)), 'omgx_template_read')
     t = out.contents
     counts = {k: int(getattr(t, k)) for k in ('n_var', 'n_par', 'n_con', 'n_atoms', 'n_slots', 'n_terms', 'n_eq', 'n_blocks',
                                                'has_bounds', 'n_lift', 'lift_row0')}
-    lib.omgx_template_free.argtypes = [C.POINTER(CTemplate)]
-    lib.omgx_template_free.restype = None
     lib.omgx_template_free(out)
     return counts
 
@@ -235,7 +231,6 @@ def describe_plan(tpl, lib=None):
     ct, keep = make_ctemplate(tpl)
     info = CPlanInfo()
     order = np.zeros(tpl.n_var + 1, dtype=np.int32)
-    lib.omgx_plan_describe.argtypes = [C.POINTER(CTemplate), C.POINTER(CPlanInfo), C.c_void_p]
     _check(lib, lib.omgx_plan_describe(C.byref(ct), C.byref(info), order.ctypes.data), 'omgx_plan_describe')
     nl = info.n_leaf
     return dict(n_leaf=nl, n_root=info.n_root, n_eq=info.n_eq, nnz_j=info.nnz_j, kkt_doubles=info.kkt_doubles,
@@ -243,6 +238,80 @@ def describe_plan(tpl, lib=None):
                 leaf_sizes=list(info.leaf_size[:nl]), leaf_bw=list(info.leaf_bw[:nl]),
                 leaf_cpl=list(info.leaf_cpl[:nl]), order=order, n_pairs=info.n_pairs,
                 ka_len=info.ka_len, kh_len=info.kh_len, kg_len=info.kg_len)
+
+
+class AdmmLayoutC(C.Structure):
+    """include/omgx.h omgx_admm_layout"""
+    _fields_ = [(n, C.c_int32) for n in ('n_dim', 'L', 'n_nghb', 'x_spl', 'p_rel',
+                                         'p_zi', 'p_zji', 'p_li', 'p_lji')]
+
+
+def _ptr(a):
+    """Address of a torch tensor / numpy array, a raw address as it is, None as the null pointer."""
+    if a is None:
+        return None
+    return a.data_ptr() if hasattr(a, 'data_ptr') else (a.ctypes.data if hasattr(a, 'ctypes') else int(a))
+
+
+# Every entry of include/omgx.h the package calls: name -> (restype, argtypes).  load_library applies the table once; nothing
+# else assigns a prototype (tests/test_binding_prototypes_cpu.py holds the table against the header).
+_I, _D, _P, _H = C.c_int32, C.c_double, C.c_void_p, C.c_void_p      # (_H: the omgx_batch handle)
+_TPL, _LAY, _SIG, _STO = C.POINTER(CTemplate), C.POINTER(AdmmLayoutC), C.POINTER(CSignalsSpec), C.POINTER(CStoreSpec)
+PROTOTYPES = {
+    'omgx_version': (C.c_int, []),
+    'omgx_last_error': (C.c_char_p, []),
+    'omgx_status_string': (C.c_char_p, [_I]),
+    'omgx_default_options': (None, [C.POINTER(COptions)]),
+    'omgx_template_write': (C.c_int, [_TPL, C.c_char_p]),
+    'omgx_template_read': (C.c_int, [C.c_char_p, C.POINTER(_TPL)]),
+    'omgx_template_free': (None, [_TPL]),
+    'omgx_template_n_blocks': (C.c_int, [_TPL, _I]),
+    'omgx_template_block_at': (C.c_int, [_TPL, _I, _I, C.POINTER(C.c_char_p), _P, _P, _P]),
+    'omgx_template_block': (C.c_int, [_TPL, _I, C.c_char_p, _P, _P, _P]),
+    'omgx_plan_describe': (C.c_int, [_TPL, C.POINTER(CPlanInfo), _P]),
+    'omgx_batch_create': (C.c_int, [_TPL, _I, _I, C.POINTER(C.c_void_p)]),
+    'omgx_batch_destroy': (None, [_H]),
+    'omgx_batch_set_options': (C.c_int, [_H, C.POINTER(COptions)]),
+    'omgx_batch_set_stream': (C.c_int, [_H, _P]),
+    'omgx_batch_set_order': (C.c_int, [_H, _P]),
+    'omgx_batch_order_by_iters': (C.c_int, [_H, _P, _P]),
+    'omgx_batch_set_restarts': (C.c_int, [_H, _P, _I, _P]),
+    'omgx_batch_lds_bytes': (C.c_int, [_H]),
+    'omgx_batch_last_instance': (C.c_int, [_H]),
+    'omgx_batch_workspace': (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    'omgx_batch_solve': (C.c_int, [_H] + [_P] * 8 + [_I]),
+    'omgx_batch_sync': (C.c_int, [_H]),
+    'omgx_batch_transfer': (C.c_int, [_H, _I, _P, _P, _P]),
+    'omgx_batch_eval': (C.c_int, [_H] + [_P] * 7),
+    'omgx_batch_set_stats': (C.c_int, [_H, _P, _I]),
+    'omgx_batch_set_launch_events': (C.c_int, [_H, _P, _P]),
+    'omgx_batch_set_timing': (C.c_int, [_H, _I]),
+    'omgx_batch_last_kernel_ms': (C.c_int, [_H, C.POINTER(C.c_double)]),
+    'omgx_batch_set_prepare': (C.c_int, [_H, _I]),
+    'omgx_batch_set_stop': (C.c_int, [_H, _I, _I, _I, _I, _D, _P]),
+    'omgx_batch_shift': (C.c_int, [_H, _P, _P, _P, _I, _P, _I, _I]),
+    'omgx_batch_sample': (C.c_int, [_H, _P, _I, _I, _I, _P, _I, _I, _P, _D, _I, _P, _I, _I]),
+    'omgx_batch_predict': (C.c_int, [_H, _P, _P, _I, _I, _I, _P, _I, _D, _D, _I, _I, _I, _D]),
+    'omgx_batch_predict_ex': (C.c_int, [_H, _P, _P, _I, _I, _I, _P, _I, _D, _D, _I, _P, _I, _D, _I, _P, _I, _D]),
+    'omgx_batch_predict_quadrotor': (C.c_int, [_H, _P, _P, _I, _I, _P, _I, _D, _D, _I, _P, _I, _D, _P, _P, _I, _D, _D]),
+    'omgx_batch_rollout': (C.c_int, [_H, C.POINTER(CRolloutSpec)] + [_P] * 7 + [_I]),
+    'omgx_batch_store': (C.c_int, [_H, _P, _STO]),
+    'omgx_batch_set_store': (C.c_int, [_H, _STO]),
+    'omgx_batch_set_signals': (C.c_int, [_H, _SIG]),
+    'omgx_batch_signals_append': (C.c_int, [_H, _P, _P, _P, _SIG]),
+    'omgx_batch_signals_reduce': (C.c_int, [_H, _SIG, _P, _P]),
+    'omgx_shift_rows': (C.c_int, [_H, _P, _I, _I, _P, _P, _I, _P, _I]),
+    'omgx_admm_center': (C.c_int, [_H, _LAY] + [_P] * 3),
+    'omgx_admm_update': (C.c_int, [_H, _LAY] + [_P] * 4 + [_D] + [_P] * 4),
+    'omgx_admm_update_sums': (C.c_int, [_H, _LAY] + [_P] * 4 + [_D] + [_P] * 5),
+    'omgx_admm_communicate': (C.c_int, [_H, _LAY] + [_P] * 5),
+    'omgx_admm_center_ex': (C.c_int, [_H, _LAY] + [_P] * 4 + [_I, _P]),
+    'omgx_batch_set_center': (C.c_int, [_H, _LAY, _P, _P, _I, _P]),
+    'omgx_admm_update_ex': (C.c_int, [_H, _LAY] + [_P] * 4 + [_D] + [_P] * 3 + [_I] + [_P] * 4 + [_I]),
+    'omgx_admm_communicate_ex': (C.c_int, [_H, _LAY] + [_P] * 4 + [_I] + [_P] * 2 + [_I, _I, _P]),
+}
+# (entries of ABI 8 and 9 and the lean-instance query: a library built before them still loads, calling one raises AttributeError)
+_NEWER_ENTRIES = ('omgx_batch_set_prepare', 'omgx_batch_set_stop', 'omgx_batch_last_instance')
 
 
 _lib = None
@@ -267,48 +336,11 @@ def load_library(path=None):
     except ImportError:
         pass
     lib = C.CDLL(path)
-    lib.omgx_version.restype = C.c_int
-    lib.omgx_last_error.restype = C.c_char_p
-    lib.omgx_status_string.restype = C.c_char_p
-    lib.omgx_status_string.argtypes = [C.c_int32]
-    lib.omgx_default_options.argtypes = [C.POINTER(COptions)]
-    lib.omgx_batch_create.argtypes = [C.POINTER(CTemplate), C.c_int32, C.c_int32,
-                                      C.POINTER(C.c_void_p)]
-    lib.omgx_batch_destroy.argtypes = [C.c_void_p]
-    lib.omgx_batch_destroy.restype = None
-    lib.omgx_batch_set_options.argtypes = [C.c_void_p, C.POINTER(COptions)]
-    lib.omgx_batch_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-    lib.omgx_batch_lds_bytes.argtypes = [C.c_void_p]
-    if hasattr(lib, 'omgx_batch_last_instance'):      # (OMGX_HAS_LAST_INSTANCE: not in a library built before it)
-        lib.omgx_batch_last_instance.argtypes = [C.c_void_p]
-        lib.omgx_batch_last_instance.restype = C.c_int
-    lib.omgx_batch_set_order.argtypes = [C.c_void_p, C.c_void_p]
-    lib.omgx_batch_order_by_iters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.omgx_batch_workspace.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64),
-                                         C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-    lib.omgx_batch_solve.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int32]
-    lib.omgx_batch_sync.argtypes = [C.c_void_p]
-    lib.omgx_batch_transfer.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.omgx_batch_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
-    lib.omgx_batch_shift.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
-    lib.omgx_batch_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                       C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32,
-                                       C.c_int32, C.c_double]
-    lib.omgx_batch_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                      C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_double,
-                                      C.c_int32, C.c_void_p, C.c_int32, C.c_int32]
-    lib.omgx_batch_predict_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
-                                          C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p,
-                                          C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_double]
-    lib.omgx_batch_predict_quadrotor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                                 C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p,
-                                                 C.c_void_p, C.c_int32, C.c_double, C.c_double]
-    lib.omgx_batch_store.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CStoreSpec)]
-    lib.omgx_batch_set_store.argtypes = [C.c_void_p, C.POINTER(CStoreSpec)]
-    lib.omgx_batch_set_signals.argtypes = [C.c_void_p, C.POINTER(CSignalsSpec)]
-    lib.omgx_batch_signals_append.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CSignalsSpec)]
-    lib.omgx_batch_signals_reduce.argtypes = [C.c_void_p, C.POINTER(CSignalsSpec), C.c_void_p, C.c_void_p]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if name in _NEWER_ENTRIES and not hasattr(lib, name):      # (an older library given by OMGX_LIB; any other missing entry raises here)
+            continue
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -428,18 +460,15 @@ class BatchSolver(object):
     def solve_device(self, p, x0, lbg, ubg, x, lam_g, status, iters, bounds_shared=True, only_failed=False):
         """only_failed: restart pass -- agents whose `status` is 0 keep x / lam_g / status / iters, the others are
         solved from x0 (OMGX_ONLY_FAILED)."""
-        def ptr(a):
-            return a.data_ptr() if hasattr(a, 'data_ptr') else int(a)
         flags = PTR_DEVICE | BOUNDS_DEVICE | (BOUNDS_SHARED if bounds_shared else 0) | (ONLY_FAILED if only_failed else 0)
         _check(self.lib, self.lib.omgx_batch_solve(
-            self._h, ptr(p), ptr(x0), ptr(lbg), ptr(ubg), ptr(x), ptr(lam_g), ptr(status),
-            ptr(iters), flags), 'omgx_batch_solve')
+            self._h, _ptr(p), _ptr(x0), _ptr(lbg), _ptr(ubg), _ptr(x), _ptr(lam_g), _ptr(status),
+            _ptr(iters), flags), 'omgx_batch_solve')
 
     def set_restarts(self, x0_alt=None, attempts=None):
         """Restart guesses of the following cold device solves (include/omgx.h omgx_batch_set_restarts): x0_alt
         [n_alt, B, n_var] device tensor or None, attempts [B] int32 device tensor or None.  The caller keeps both
         alive until the solves are done."""
-        self.lib.omgx_batch_set_restarts.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         n_alt = 0 if x0_alt is None else int(x0_alt.shape[0])
         if n_alt and (tuple(x0_alt.shape[1:]) != (self.n_agents, self.template.n_var) or not x0_alt.is_contiguous()):
             raise ValueError("x0_alt must be a contiguous [n_alt, %d, %d] tensor" % (self.n_agents, self.template.n_var))
@@ -452,7 +481,6 @@ class BatchSolver(object):
         """Launch statistics on the device (include/omgx.h omgx_batch_set_stats): stats [n_slots, 4] int64 device
         tensor (zeroed by the caller, kept alive by it) or None; row k % n_slots of the k-th following solve gets
         {solved agents, sum of iterations, largest iteration count, agents solved}."""
-        self.lib.omgx_batch_set_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         if stats is not None and (stats.dim() != 2 or stats.shape[1] != 4 or not stats.is_contiguous() or stats.element_size() != 8):
             raise ValueError('stats must be a contiguous [n_slots, 4] int64 tensor')
         _check(self.lib, self.lib.omgx_batch_set_stats(self._h, stats.data_ptr() if stats is not None else None,
@@ -468,7 +496,6 @@ class BatchSolver(object):
             if not h:
                 raise ValueError('the event has no handle yet: record it once before handing it over')
             return h
-        self.lib.omgx_batch_set_launch_events.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _check(self.lib, self.lib.omgx_batch_set_launch_events(self._h, handle(start), handle(stop)),
                'omgx_batch_set_launch_events')
 
@@ -481,7 +508,6 @@ class BatchSolver(object):
         lam = np.ascontiguousarray(np.asarray(lam_g, float).reshape(B, t.n_con))
         g, f = np.empty((B, t.n_con)), np.empty(B)
         jac, hess = np.empty((B, t.n_con + 1, t.n_var)), np.empty((B, t.n_var, t.n_var))
-        self.lib.omgx_batch_eval.argtypes = [C.c_void_p] * 8
         _check(self.lib, self.lib.omgx_batch_eval(self._h, p.ctypes.data, x.ctypes.data, lam.ctypes.data, g.ctypes.data,
                                                   f.ctypes.data, jac.ctypes.data, hess.ctypes.data), 'omgx_batch_eval')
         return dict(g=g, f=f, jac=jac, hess=hess)
@@ -517,20 +543,17 @@ class BatchSolver(object):
 
     def set_timing(self, on):
         """Event records around every solve kernel (needed by last_kernel_ms; ~20 us of stream time per solve)."""
-        self.lib.omgx_batch_set_timing.argtypes = [C.c_void_p, C.c_int32]
         _check(self.lib, self.lib.omgx_batch_set_timing(self._h, int(bool(on))), 'omgx_batch_set_timing')
 
     def set_prepare(self, on):
         """The setup of every solve as ONE launch for the whole batch ahead of the solve kernel (`omgx_batch_set_prepare`, ABI 8;
         off by default -- measured slower on the benchmark batch): off = every solve does its own setup inside the solve kernel
         (the same statements, the same bits)."""
-        self.lib.omgx_batch_set_prepare.argtypes = [C.c_void_p, C.c_int32]
         _check(self.lib, self.lib.omgx_batch_set_prepare(self._h, int(bool(on))), 'omgx_batch_set_prepare')
 
     def set_stop(self, o_state0=0, o_input0=0, o_poseT=0, n_dim=0, stop_tol=1e-3, under_way=None):
         """The reference's stop criterion inside the solve launch (include/omgx.h omgx_batch_set_stop, ABI 9): under_way [B] int32
         device tensor (kept alive by the caller too), 1 = the agent's loop is running; None switches the rule off."""
-        self.lib.omgx_batch_set_stop.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p]
         if under_way is not None and (under_way.dim() != 1 or under_way.shape[0] != self.n_agents or not under_way.is_contiguous()
                                       or under_way.element_size() != 4 or under_way.is_floating_point()):
             raise ValueError('under_way must be a contiguous [n_agents] int32 device tensor')
@@ -547,11 +570,8 @@ class BatchSolver(object):
     def predict(self, x, p, coeff_off, n_spl, degree, knots, tau, inv_T, p_state0, p_input0, p_t, t_value):
         """Ideal prediction on device-resident x / p (torch tensors or raw device pointers)."""
         knots = np.ascontiguousarray(knots, dtype=np.float64)
-
-        def ptr(a):
-            return a.data_ptr() if hasattr(a, 'data_ptr') else int(a)
         _check(self.lib, self.lib.omgx_batch_predict(
-            self._h, ptr(x), ptr(p), int(coeff_off), int(n_spl), int(degree), knots.ctypes.data, len(knots),
+            self._h, _ptr(x), _ptr(p), int(coeff_off), int(n_spl), int(degree), knots.ctypes.data, len(knots),
             float(tau), float(inv_T), int(p_state0), int(p_input0), int(p_t), float(t_value)),
             'omgx_batch_predict')
 
@@ -562,12 +582,9 @@ class BatchSolver(object):
         (include/omgx.h omgx_batch_predict_ex).  Device-resident tensors / pointers."""
         knots = np.ascontiguousarray(knots, dtype=np.float64)
         off = np.ascontiguousarray(p_off, dtype=np.int32)
-
-        def ptr(a):
-            return None if a is None else (a.data_ptr() if hasattr(a, 'data_ptr') else int(a))
         _check(self.lib, self.lib.omgx_batch_predict_ex(
-            self._h, ptr(x), ptr(p), int(coeff_off), int(n_spl), int(degree), knots.ctypes.data, len(knots),
-            float(tau), float(inv_T), len(off), off.ctypes.data, int(p_t), float(t_value), int(mode), ptr(state_in),
+            self._h, _ptr(x), _ptr(p), int(coeff_off), int(n_spl), int(degree), knots.ctypes.data, len(knots),
+            float(tau), float(inv_T), len(off), off.ctypes.data, int(p_t), float(t_value), int(mode), _ptr(state_in),
             int(n_sub), float(dtau)), 'omgx_batch_predict_ex')
 
     def rollout(self, p, x, lbg, ubg, lam_g, status, iters, tau, t_rel, crossed, coeff_off, n_spl, degree, knots, inv_T, p_off, p_t,
@@ -576,8 +593,6 @@ class BatchSolver(object):
         """n_steps = len(tau) receding-horizon steps of every agent in one launch (include/omgx.h omgx_batch_rollout): device
         tensors p, x, lam_g, status, iters updated in place; tau / t_rel / crossed: per-step host arrays; the rest as
         `predict_ex` / `shift`; obstacles: [(p_x, p_v, p_a, n_dim)] of the ones that move; lam_perm: multiplier map of a crossing."""
-        def ptr(a):
-            return None if a is None else (a.data_ptr() if hasattr(a, 'data_ptr') else int(a))
         keep = dict(tau=np.ascontiguousarray(tau, dtype=np.float64), t_rel=np.ascontiguousarray(t_rel, dtype=np.float64),
                     crossed=np.ascontiguousarray(crossed, dtype=np.uint8), knots=np.ascontiguousarray(knots, dtype=np.float64),
                     p_off=np.ascontiguousarray(p_off, dtype=np.int32),
@@ -597,23 +612,19 @@ class BatchSolver(object):
         if cross_options:
             keep['copt'] = COptions(**dict(self.options, **cross_options))
             sp.cross_options = C.addressof(keep['copt'])
-        sp.iters_log, sp.status_log = ptr(iters_log), ptr(status_log)
-        self.lib.omgx_batch_rollout.argtypes = [C.c_void_p, C.POINTER(CRolloutSpec)] + [C.c_void_p] * 7 + [C.c_int32]
+        sp.iters_log, sp.status_log = _ptr(iters_log), _ptr(status_log)
         flags = PTR_DEVICE | BOUNDS_DEVICE | (BOUNDS_SHARED if bounds_shared else 0)
-        _check(self.lib, self.lib.omgx_batch_rollout(self._h, C.byref(sp), ptr(p), ptr(x), ptr(lbg), ptr(ubg), ptr(lam_g), ptr(status),
-                                                     ptr(iters), flags), 'omgx_batch_rollout')
+        _check(self.lib, self.lib.omgx_batch_rollout(self._h, C.byref(sp), _ptr(p), _ptr(x), _ptr(lbg), _ptr(ubg), _ptr(lam_g), _ptr(status),
+                                                     _ptr(iters), flags), 'omgx_batch_rollout')
 
     def predict_quadrotor(self, x, p, coeff_off, degree, knots, tau, inv_T, p_off, p_t, t_value, state_in, state_out, n_sub, dtau, g=9.81):
         """Non-ideal prediction of the Quadrotor model: state_in [B, 5] integrated over the n_sub sample intervals that end at tau
         with the inputs the plan holds there (include/omgx.h omgx_batch_predict_quadrotor).  Device tensors / pointers."""
         knots = np.ascontiguousarray(knots, dtype=np.float64)
         off = np.ascontiguousarray(p_off, dtype=np.int32)
-
-        def ptr(a):
-            return None if a is None else (a.data_ptr() if hasattr(a, 'data_ptr') else int(a))
         _check(self.lib, self.lib.omgx_batch_predict_quadrotor(
-            self._h, ptr(x), ptr(p), int(coeff_off), int(degree), knots.ctypes.data, len(knots), float(tau), float(inv_T), len(off),
-            off.ctypes.data, int(p_t), float(t_value), ptr(state_in), ptr(state_out), int(n_sub), float(dtau), float(g)),
+            self._h, _ptr(x), _ptr(p), int(coeff_off), int(degree), knots.ctypes.data, len(knots), float(tau), float(inv_T), len(off),
+            off.ctypes.data, int(p_t), float(t_value), _ptr(state_in), _ptr(state_out), int(n_sub), float(dtau), float(g)),
             'omgx_batch_predict_quadrotor')
 
     def _store_spec(self, out, v_tot, t0, coeff_off, n_spl, degree, knots, n_der, n_samp, dt, inv_T):
@@ -696,25 +707,20 @@ class BatchSolver(object):
     def sample(self, x, coeff_off, n_spl, degree, knots, n_der, t0, dt, n_samp,
                out=None, as_f32=False, device=False):
         knots = np.ascontiguousarray(knots, dtype=np.float64)
-
-        def ptr(a):
-            return a.data_ptr() if hasattr(a, 'data_ptr') else a.ctypes.data
         if out is None:
             out = np.empty((self.n_agents, n_der, n_spl, n_samp),
                            dtype=np.float32 if as_f32 else np.float64)
         _check(self.lib, self.lib.omgx_batch_sample(
-            self._h, ptr(x), coeff_off, n_spl, degree, knots.ctypes.data, len(knots), n_der,
-            ptr(t0), float(dt), n_samp, ptr(out), int(as_f32), PTR_DEVICE if device else 0),
+            self._h, _ptr(x), coeff_off, n_spl, degree, knots.ctypes.data, len(knots), n_der,
+            _ptr(t0), float(dt), n_samp, _ptr(out), int(as_f32), PTR_DEVICE if device else 0),
             'omgx_batch_sample')
         return out
 
     def shift(self, x, mask, entries, tmats, device=False):
-        def ptr(a):
-            return a.data_ptr() if hasattr(a, 'data_ptr') else a.ctypes.data
         entries = np.ascontiguousarray(entries, dtype=np.int32)
         tmats = np.ascontiguousarray(tmats, dtype=np.float64)
         _check(self.lib, self.lib.omgx_batch_shift(
-            self._h, ptr(x), ptr(mask), entries.ctypes.data, len(entries), tmats.ctypes.data,
+            self._h, _ptr(x), _ptr(mask), entries.ctypes.data, len(entries), tmats.ctypes.data,
             tmats.size, PTR_DEVICE if device else 0), 'omgx_batch_shift')
 
 
