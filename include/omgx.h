@@ -492,6 +492,59 @@ int  omgx_batch_signals_append(omgx_batch* b, const double* x, const double* p, 
  * fixed order (the same bits in every run). */
 int  omgx_batch_signals_reduce(omgx_batch* b, const omgx_signals_spec* sp, const double* target, double* summary);
 
+/* (OMGX_HAS_PLANT) The plant in the loop: a simulated vehicle next to every plan, as `Simulator.run` keeps one with the reference's
+ * default options `ideal_prediction = False, ideal_update = False` (`vehicles/vehicle.py:73-75`) -- the vehicle travels by its own
+ * `ode` under the plan's inputs plus an optional input disturbance (`Vehicle.simulate`, `vehicle.py:370-390`, `add_disturbance`,
+ * 433-450), and the next solve starts from the state the vehicle had one update ago integrated under the undisturbed inputs
+ * (`Vehicle.predict`, `vehicle.py:326-337`).  Integrator classes only (`ode` = input: Holonomic, Holonomic3D; parameters state0 /
+ * input0 / poseT); no first-order actuator lag.  Per agent the plant carries state [n_spl] (where the vehicle is, at the last
+ * simulated sample), state_prev [n_spl] (where it was one update earlier), input_last [n_spl] (the last applied input) and n_upd
+ * (updates simulated so far; the caller zeroes n_upd and overflow).  n_samp = int(round(update_time / sample_time, 6)).
+ *
+ * simulate -- after the solve of an update; the plan c and t_rel = p[p_t] are those of that solve:
+ *   nominal inputs   u_i = d/dt spline at (t_rel + i sample_time) * inv_T,  i = 0 .. n_samp
+ *   applied inputs   a_i = u_i + dist[b, k, n_upd, i]                       (dist [B, n_spl, max_updates, n_samp + 1]; NULL: none)
+ *   state_prev <- state;  state <- state + sample_time * sum_{i < n_samp} (a_i + a_{i+1}) / 2
+ *     (the exact integral of the reference's linearly interpolated input, `vehicle.py:412-423`, for `ode` = input; the partial
+ *     sums are the state samples 1 .. n_samp); input_last <- a_{n_samp}; n_upd += 1.  On the first simulate (n_upd == 0) state
+ *     starts from the plan's own sample 0 (`vehicle.py:361-364`).
+ *   With a log (an omgx_signals_spec, n_der >= 2, the plant's n_spl / n_samp / sample_time) n_samp columns are appended: row state =
+ *   the integrated samples, row input = a_1 .. a_{n_samp}, row dinput = the plan's, as omgx_batch_signals_append writes it; ahead
+ *   of the first append column 0 from the plan, undisturbed; count, cap and overflow as there.  An update with n_upd >= max_updates
+ *   has no disturbance block left: it writes nothing and sets the plant's overflow[b].
+ * predict -- at the head of the next update, before obstacle motion and the knot-crossing shift; it reads the old plan and the old
+ * p[p_t]:  p[p_state0 + k] <- state_prev + sample_time * sum (u_i + u_{i+1}) / 2 over the same n_samp intervals (nominal inputs),
+ *   p[p_input0 + k] <- d/dt spline at tau, p[p_t] <- t_value.  The vehicle never sees the disturbance of the interval just travelled:
+ *   it shows up one update later through state_prev (`state0 = signals['state'][:, -n_samp-1]`).
+ * stop rule -- tested in the same place as predict: with under_way given, an agent with under_way[b] == 0 is left alone, and one
+ *   whose travelled state and last applied input meet |state - p[p_poseT ..]| <= stop_tol and |input_last| <= stop_tol (Euclidean
+ *   norms over the n_spl entries, `vehicles/holonomic.py:145-151`) gets under_way[b] = 0 and is not predicted.  A stopped agent is
+ *   neither solved, predicted nor simulated again: register the same under_way with omgx_batch_set_stop and a negative tolerance
+ *   (a rule that never holds), so that the solve kernel only honours the flags.
+ * Every sum is taken in one fixed order without fused multiply-adds; the stand-alone launches and the rollout write the same bits.
+ * omgx_batch_plant_simulate / omgx_batch_plant_predict: one launch each on the handle's stream (device pointers x, p; predict
+ * carries a pending omgx_batch_order_by_iters as omgx_batch_predict_ex does).  omgx_batch_set_plant: every following
+ * omgx_batch_rollout runs the plant instance of its kernel -- predict + stop test in place of the ideal prediction, simulate (with
+ * the log given here) after every solve, in place of the append of omgx_batch_set_signals; spec == NULL switches it off.  A class
+ * without such an instance: omgx_batch_rollout returns OMGX_E_INVALID.  The arrays a spec points at must stay valid while it is set. */
+#define OMGX_HAS_PLANT 1
+typedef struct omgx_plant_spec {
+  double*  state;          /* [B, n_spl] device */
+  double*  state_prev;     /* [B, n_spl] device */
+  double*  input_last;     /* [B, n_spl] device */
+  const double* dist;      /* [B, n_spl, max_updates, n_samp + 1] device, or NULL */
+  int32_t* n_upd;          /* [B] device, in/out */
+  int32_t* overflow;       /* [B] device, or NULL */
+  int32_t* under_way;      /* [B] device, or NULL: no stop rule */
+  const double* knots;     /* [n_knots] host, n_knots <= 40 */
+  int32_t coeff_off, n_spl, degree, n_knots, n_samp, max_updates, p_t, p_state0, p_input0, p_poseT;
+  double  sample_time, inv_T, stop_tol;
+} omgx_plant_spec;
+int  omgx_batch_plant_simulate(omgx_batch* b, const double* x, const double* p, const omgx_plant_spec* sp,
+                               const omgx_signals_spec* log_sp);
+int  omgx_batch_plant_predict(omgx_batch* b, const double* x, double* p, double tau, double t_value, const omgx_plant_spec* sp);
+int  omgx_batch_set_plant(omgx_batch* b, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp);
+
 /* Same shift on any device-resident row-major array (stride doubles per row, n_rows rows):
  * used for the ADMM consensus state on a knot crossing (`problems/admm.py:477-491`).
  * The handle keeps the table sets it has seen on the device (16, found again by content): a loop that shifts with the

@@ -32,12 +32,12 @@ constexpr int kLdsHalf = kLdsLimit / 2 - 512;      // two workgroups per CU (the
 }  // namespace
 
 // The kernel instances of a handle's template class, resolved once per handle (omgx_batch_create) through the selectors of omgx_kernels.h:
-// the one place where a workspace mode maps to a template instance.  refine / lean / rollout are null where the class has no
+// the one place where a workspace mode maps to a template instance.  refine / lean / rollout / rollout_plant are null where the class has no
 // such instance (the general instance, classes off the wave path, the spill modes).
 struct Instances {
   ipm_kernel_t full = nullptr, refine = nullptr, lean = nullptr;
   ipm_eval_kernel_t eval = nullptr;
-  ipm_rollout_t rollout = nullptr;
+  ipm_rollout_t rollout = nullptr, rollout_plant = nullptr;      // (rollout_plant: the instance with the plant in the loop, omgx_batch_set_plant)
   decltype(&ipm_prepare_kernel<true>) prepare = nullptr;
 };
 static Instances instances_for(int mode, int wave_ok, int general) {
@@ -48,6 +48,7 @@ static Instances instances_for(int mode, int wave_ok, int general) {
   if (lean != in.full) in.lean = lean;
   in.eval = ipm_eval_kernel_for(mode, wave_ok, general);
   in.rollout = rollout_kernel_for(mode, wave_ok, general);
+  in.rollout_plant = rollout_kernel_for(mode, wave_ok, general, 1);
   in.prepare = general ? ipm_prepare_kernel<true> : ipm_prepare_kernel<false>;
   return in;
 }
@@ -100,6 +101,10 @@ struct omgx_batch {
   RolloutArgs* d_rollout = nullptr; int32_t* d_ro_perm = nullptr;      // omgx_batch_rollout
   DevBuf ro_steps; int ro_steps_cap = 0;      // (its step table grows with the longest rollout asked for)
   std::vector<int32_t> ro_perm_host;
+  PlantBlock plant_host = {};       // omgx_batch_set_plant: the plant and its log as the rollout's plant instance reads them ...
+  PlantBlock* d_plant = nullptr;    // ... their copy in device memory ...
+  PlantBlock* d_plant_call = nullptr;      // ... and the copy of what a stand-alone omgx_batch_plant_simulate / _predict call was given
+  bool plant_on = false;
   StopArgs* d_stop = nullptr;       // omgx_batch_set_stop: device copy of the arguments
   StopArgs stop_host = {};          // (and the host copy: omgx_batch_rollout hands it to its kernel inside RolloutArgs)
   bool stop_on = false;
@@ -631,10 +636,11 @@ int create_batch(omgx_batch* b, const omgx_template* tpl) {
   static int lds_reserved[4 * omgx::WS_MODES] = {0};
   int& reserved = lds_reserved[4 * b->ws_mode + (d.wave_ok ? 1 : 0) + (d.general ? 2 : 0)];
   if ((int)b->lds_bytes > reserved) reserved = (int)b->lds_bytes;
-  const void* const launched[4] = {(const void*)b->inst.full, (const void*)b->inst.refine, (const void*)b->inst.lean, (const void*)b->inst.rollout};
+  const void* const launched[5] = {(const void*)b->inst.full, (const void*)b->inst.refine, (const void*)b->inst.lean, (const void*)b->inst.rollout,
+                                   (const void*)b->inst.rollout_plant};
   for (const void* k : launched)
     if (k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, reserved) != hipSuccess) {
-      g_err = k == (const void*)b->inst.rollout ? "cannot reserve dynamic LDS for ipm_rollout_kernel" : "cannot reserve dynamic LDS for ipm_solve_kernel";
+      g_err = (k == (const void*)b->inst.rollout || k == (const void*)b->inst.rollout_plant) ? "cannot reserve dynamic LDS for ipm_rollout_kernel" : "cannot reserve dynamic LDS for ipm_solve_kernel";
       return OMGX_E_HIP;
     }
   {
@@ -1242,6 +1248,105 @@ int omgx_batch_signals_reduce(omgx_batch* b, const omgx_signals_spec* sp, const 
   return OMGX_OK;
 }
 
+namespace {
+// A plant specification and the log that goes with it -> the block the kernels read.  The checks that need no handle come first
+// (null handle, n_knots, n_samp ... are refused without a device).
+int fill_plant(omgx_batch* b, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp, PlantBlock* blk) {
+  char buf[200];
+  if (!sp) { g_err = "null argument"; return OMGX_E_INVALID; }
+  if (!sp->state || !sp->state_prev || !sp->input_last || !sp->n_upd || !sp->knots) { g_err = "plant: null state / state_prev / input_last / n_upd / knots"; return OMGX_E_INVALID; }
+  if (sp->degree < 1 || sp->degree > 5) { g_err = "plant: degree outside 1 .. 5"; return OMGX_E_INVALID; }
+  if (sp->n_knots > 40 || sp->n_knots < 2 * sp->degree + 2) {
+    snprintf(buf, sizeof buf, "plant: n_knots = %d outside %d .. 40", sp->n_knots, 2 * sp->degree + 2);
+    g_err = buf; return OMGX_E_INVALID;
+  }
+  if (sp->n_samp < 1) { snprintf(buf, sizeof buf, "plant: n_samp = %d, at least one sample interval per update is needed", sp->n_samp); g_err = buf; return OMGX_E_INVALID; }
+  if (sp->n_spl <= 0 || sp->n_spl > 64 || sp->max_updates < 1 || !(sp->sample_time > 0.0) || !(sp->inv_T > 0.0) || sp->stop_tol != sp->stop_tol) {
+    g_err = "plant: n_spl (1 .. 64), max_updates, sample_time and inv_T must be positive, stop_tol a number"; return OMGX_E_INVALID;
+  }
+  if (log_sp) {
+    const int rc = check_signals_spec(log_sp);
+    if (rc != OMGX_OK) return rc;
+    if (log_sp->n_spl != sp->n_spl || log_sp->n_samp != sp->n_samp || log_sp->degree != sp->degree || log_sp->n_knots != sp->n_knots ||
+        log_sp->coeff_off != sp->coeff_off || log_sp->sample_time != sp->sample_time || log_sp->inv_T != sp->inv_T || log_sp->n_der < 2) {
+      g_err = "plant: the log must be one of the plant's plan (coeff_off, n_spl, degree, n_knots, n_samp, sample_time, inv_T) with n_der >= 2";
+      return OMGX_E_INVALID;
+    }
+  }
+  if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
+  const omgx::Dims& d = b->dims;
+  const int L = sp->n_knots - sp->degree - 1;
+  if (sp->coeff_off < 0 || sp->coeff_off + sp->n_spl * L > d.n_var) { g_err = "plant: coefficients outside x"; return OMGX_E_INVALID; }
+  const int32_t offs[4] = {sp->p_state0, sp->p_input0, sp->p_poseT, sp->p_t};
+  for (int q = 0; q < 4; ++q)
+    if (offs[q] < 0 || offs[q] + (q < 3 ? sp->n_spl : 1) > d.n_par) { g_err = "plant: p_state0 / p_input0 / p_poseT / p_t outside p"; return OMGX_E_INVALID; }
+  PlantArgs& pl = blk->pl;
+  pl.state = sp->state; pl.state_prev = sp->state_prev; pl.input_last = sp->input_last; pl.dist = sp->dist; pl.n_upd = sp->n_upd;
+  pl.overflow = sp->overflow; pl.under_way = sp->under_way;
+  pl.coeff_off = sp->coeff_off; pl.n_spl = sp->n_spl; pl.degree = sp->degree; pl.n_knots = sp->n_knots; pl.n_samp = sp->n_samp;
+  pl.max_updates = sp->max_updates; pl.p_t = sp->p_t; pl.p_state0 = sp->p_state0; pl.p_input0 = sp->p_input0; pl.p_poseT = sp->p_poseT;
+  pl.sample_time = sp->sample_time; pl.inv_T = sp->inv_T; pl.stop_tol = sp->stop_tol;
+  fill_knots(pl.knots, sp->knots, sp->n_knots);
+  blk->sg = SignalArgs{};
+  return log_sp ? fill_signals(b, log_sp, &blk->sg) : OMGX_OK;
+}
+// LDS doubles of a simulate: the log's sampling scratch (when there is a log) and the staged knots and plan behind it
+size_t plant_lds_doubles(const PlantBlock& blk) {
+  return (blk.sg.log ? sample_scratch_doubles(blk.sg.n_spl, blk.sg.degree, blk.sg.n_knots, blk.sg.n_der) : 0) +
+         plant_stage_doubles(blk.pl.n_spl, blk.pl.degree, blk.pl.n_knots);
+}
+}  // namespace
+
+int omgx_batch_set_plant(omgx_batch* b, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp) {
+  if (!sp) {
+    if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
+    b->plant_on = false;
+    return OMGX_OK;
+  }
+  PlantBlock blk;
+  const int rc = fill_plant(b, sp, log_sp, &blk);
+  if (rc != OMGX_OK) return rc;
+  b->plant_on = false;      // (a failed registration leaves the plant OFF)
+  if (plant_lds_doubles(blk) > (size_t)b->kkt_doubles) {
+    g_err = "plant: the per-agent scratch (staged plan, log) does not fit the KKT store"; return OMGX_E_TOOLARGE;
+  }
+  HIPCHK(hipSetDevice(b->device));
+  b->plant_host = blk;
+  { const int rcp = push_args(b, &b->d_plant, b->plant_host); if (rcp != OMGX_OK) return rcp; }
+  b->plant_on = true;
+  return OMGX_OK;
+}
+
+int omgx_batch_plant_simulate(omgx_batch* b, const double* x, const double* p, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp) {
+  PlantBlock blk;
+  const int rc = fill_plant(b, sp, log_sp, &blk);
+  if (rc != OMGX_OK) return rc;
+  if (!x || !p) { g_err = "null argument"; return OMGX_E_INVALID; }
+  const size_t lds = plant_lds_doubles(blk) * sizeof(double);
+  if (lds > 64 * 1024) { g_err = "plant: the per-agent scratch (staged plan, log) exceeds 64 KiB of LDS"; return OMGX_E_TOOLARGE; }
+  HIPCHK(hipSetDevice(b->device));
+  { const int rcp = push_args(b, &b->d_plant_call, blk); if (rcp != OMGX_OK) return rcp; }
+  hipLaunchKernelGGL(plant_simulate_kernel, dim3(b->n_agents), dim3(256), lds, b->stream, x, b->dims.n_var, p, b->dims.n_par,
+                     (const PlantBlock*)b->d_plant_call);
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
+int omgx_batch_plant_predict(omgx_batch* b, const double* x, double* p, double tau, double t_value, const omgx_plant_spec* sp) {
+  PlantBlock blk;
+  const int rc = fill_plant(b, sp, nullptr, &blk);
+  if (rc != OMGX_OK) return rc;
+  if (!x || !p || tau != tau) { g_err = "null argument"; return OMGX_E_INVALID; }
+  HIPCHK(hipSetDevice(b->device));
+  { const int rcp = push_args(b, &b->d_plant_call, blk); if (rcp != OMGX_OK) return rcp; }
+  const int32_t* oi = b->pend_iters; int32_t* oo = b->pend_order;
+  b->pend_iters = nullptr; b->pend_order = nullptr;
+  hipLaunchKernelGGL(plant_predict_kernel, dim3(b->n_agents + (oi ? 1 : 0)), dim3(64), plant_stage_doubles(blk.pl.n_spl, blk.pl.degree, blk.pl.n_knots) * sizeof(double), b->stream, x, b->dims.n_var, p, b->dims.n_par, b->n_agents,
+                     (const PlantBlock*)b->d_plant_call, tau, t_value, oi, oo, (const double*)(b->order_dw ? b->d_dw : nullptr));
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
 int omgx_batch_set_store(omgx_batch* b, const omgx_store_spec* sp) {
   if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
   if (!sp) { b->store = StoreArgs{}; return b->signals.log ? upload_store_block(b) : OMGX_OK; }
@@ -1295,6 +1400,16 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   const omgx::Dims& d = b->dims;
   if (!b->inst.rollout || b->n_range > 0 || !b->d_next) {
     g_err = "rollout: not available for this template class (spill modes, general instance, two-sided rows): step with omgx_batch_solve";
+    return OMGX_E_INVALID;
+  }
+  if (b->plant_on && (!b->inst.rollout_plant || !b->d_plant)) {
+    g_err = "rollout: a plant is set (omgx_batch_set_plant) but this template class has no plant instance of the rollout kernel: step with "
+            "omgx_batch_plant_predict / omgx_batch_solve / omgx_batch_plant_simulate";
+    return OMGX_E_INVALID;
+  }
+  if (b->plant_on && (sp->coeff_off != b->plant_host.pl.coeff_off || sp->n_spl != b->plant_host.pl.n_spl || sp->degree != b->plant_host.pl.degree ||
+                      sp->n_knots != b->plant_host.pl.n_knots || sp->p_t != b->plant_host.pl.p_t)) {
+    g_err = "rollout: the plan of the specification (coeff_off, n_spl, degree, n_knots, p_t) is not the one the plant was set with";
     return OMGX_E_INVALID;
   }
   if (sp->n_steps <= 0 || !sp->tau || !sp->t_rel || !sp->crossed || !sp->knots || !sp->p_off || sp->n_knots > 40 || sp->degree > 5 ||
@@ -1364,6 +1479,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
     b->stats_launch += sp->n_steps;
   }
   a.iters_log = sp->iters_log; a.status_log = sp->status_log;
+  a.plant = b->plant_on ? b->d_plant : nullptr;
   // Two small copies per call (one call is n_steps steps of the whole batch), ORDERED ON THE HANDLE'S STREAM: the persistent
   // kernel of a previous rollout reads these tables for its whole run, and on a non-blocking caller stream a null-stream
   // hipMemcpy would overwrite them under it (pageable sources: staged before the calls return, executed in stream order).
@@ -1374,7 +1490,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   hipEvent_t e0 = b->ext_ev0, e1 = b->ext_ev0 ? b->ext_ev1 : nullptr;
   b->ext_ev0 = b->ext_ev1 = nullptr;
   b->timed = false;
-  hipExtLaunchKernelGGL(b->inst.rollout, dim3(b->n_slabs < b->n_agents ? b->n_slabs : b->n_agents), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream, e0, e1, 0u,
+  hipExtLaunchKernelGGL(b->plant_on ? b->inst.rollout_plant : b->inst.rollout, dim3(b->n_slabs < b->n_agents ? b->n_slabs : b->n_agents), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream, e0, e1, 0u,
                         d, b->dev, b->opts, b->kkt_doubles, p, x, lbg, ubg, shared ? 1 : 0, lam_g, status, iters, b->n_agents,
                         b->d_slabs, b->slab_doubles, b->d_dw, b->d_next, (const RolloutArgs*)b->d_rollout, b->stagger, b->d_order,
                         (const StoreArgs*)((b->store.out || b->signals.log) ? &b->d_store->st : nullptr));

@@ -792,6 +792,189 @@ shift_kernel(double* __restrict__ x, int x_stride, const uint8_t* __restrict__ m
 }
 
 // ---------------------------------------------------------------------------
+// The plant in the loop (omgx_batch_set_plant; include/omgx.h states the semantics): a simulated integrator vehicle per agent --
+// `Vehicle.simulate` / `Vehicle.predict` of the reference with its default options (`vehicles/vehicle.py:326-337, 370-390`),
+// `ode` = input (Holonomic, Holonomic3D).  Two routines, called by the whole workgroup of an agent with the same arguments;
+// thread k < n_spl owns spline k and adds its samples up in index order, every product and sum rounded on its own: the
+// stand-alone kernels and the rollout kernel write the same bits.
+// ---------------------------------------------------------------------------
+struct PlantArgs {
+  double* state; double* state_prev; double* input_last;      // [B, n_spl]
+  const double* dist;                                         // [B, n_spl, max_updates, n_samp + 1] or nullptr
+  int32_t* n_upd; int32_t* overflow; int32_t* under_way;      // [B]; overflow / under_way may be nullptr
+  int coeff_off, n_spl, degree, n_knots, n_samp, max_updates, p_t, p_state0, p_input0, p_poseT;
+  double sample_time, inv_T, stop_tol;
+  KnotArg knots;
+};
+// what the rollout kernel's plant instance reads from device memory: the plant and the log its simulate writes (sg.log == nullptr: none)
+struct PlantBlock { PlantArgs pl; SignalArgs sg; };
+
+// LDS doubles the two routines stage the knots and the plan in (the de Boor recursions then read LDS, not device memory)
+__host__ __device__ inline size_t plant_stage_doubles(int n_spl, int degree, int n_knots) {
+  return (size_t)n_knots + (size_t)n_spl * (n_knots - degree - 1);
+}
+// knots -> stage[0 .. n_knots), coefficients [n_spl][L] -> behind them; every thread of the workgroup, a barrier at the end
+__device__ __forceinline__ void plant_stage(const PlantArgs& pl, const double* coeffs, double* stage) {
+  const int n_c = pl.n_spl * (pl.n_knots - pl.degree - 1);
+  for (int i = threadIdx.x; i < pl.n_knots; i += blockDim.x) stage[i] = pl.knots.k[i];
+  for (int i = threadIdx.x; i < n_c; i += blockDim.x) stage[pl.n_knots + i] = coeffs[i];
+  __syncthreads();
+}
+
+// nominal input of spline c (time derivative of the plan) at sample i of the update solved at t_rel; kk: the knots
+__device__ __forceinline__ double plant_input_at(const PlantArgs& pl, const double* kk, const double* c, double t_rel, int i) {
+#pragma clang fp contract(off)
+  const double u = (t_rel + i * pl.sample_time) * pl.inv_T;
+  return spline_der_at(c, kk, pl.degree, span_of(kk, pl.degree, pl.n_knots, u), u, 1) * pl.inv_T;
+}
+
+// simulate: the vehicle of agent b travels the update just solved (coeffs [n_spl][L]: its plan, global memory or LDS; t_rel = p[p_t]
+// of that solve).  sg (or nullptr): the log that takes the travelled samples; scratch (LDS): sample_scratch_doubles() doubles when sg
+// is given, and plant_stage_doubles() behind them.  Barriers inside.
+__device__ __noinline__ void plant_simulate_agent(const PlantArgs& pl, const SignalArgs* sg, int b, const double* coeffs, double t_rel,
+                                                  double* scratch) {
+  __syncthreads();      // (every thread reads n_upd[b] / count[b] before thread 0 moves them; the scratch may still be read by the fused store)
+  const int nu = pl.n_upd[b];
+  if (nu < 0 || nu >= pl.max_updates) {      // (the same branch in every thread) no disturbance block left
+    if (threadIdx.x == 0 && pl.overflow) pl.overflow[b] = 1;
+    return;
+  }
+  const int n_samp = pl.n_samp, L = pl.n_knots - pl.degree - 1;
+  int cnt = 0, first = 1, n_col = 0;
+  bool log_on = sg != nullptr;
+  if (log_on) {
+    cnt = sg->count[b];
+    first = cnt == 0 ? 0 : 1;
+    n_col = n_samp + 1 - first;
+    if (cnt < 0 || cnt > sg->cap - n_col) {      // the log is full: this append is dropped as a whole, the vehicle travels on
+      if (threadIdx.x == 0 && sg->overflow) sg->overflow[b] = 1;
+      log_on = false;
+    }
+  }
+  double* stage = scratch + (sg ? sample_scratch_doubles(sg->n_spl, sg->degree, sg->n_knots, sg->n_der) : 0);
+  plant_stage(pl, coeffs, stage);
+  double* lg = nullptr;
+  if (log_on) {
+    // the plan's own columns, as signals_append_agent writes them: column 0 ahead of the first append and the dinput row stay
+    lg = sg->log + (size_t)b * sg->n_der * sg->n_spl * sg->cap + (cnt - first);
+    sample_agent<double>(coeffs, scratch, sg->n_spl, sg->degree, sg->knots, sg->n_knots, sg->n_der, t_rel * sg->inv_T, sg->sample_time * sg->inv_T,
+                         sg->inv_T, sg->cap, first, n_samp + 1, lg, (double*)nullptr);
+    __syncthreads();
+  }
+  if ((int)threadIdx.x < pl.n_spl) {
+#pragma clang fp contract(off)
+    const int k = threadIdx.x;
+    const double* kk = stage;
+    const double* c = stage + pl.n_knots + k * L;
+    const double* db = pl.dist ? pl.dist + (((size_t)b * pl.n_spl + k) * pl.max_updates + nu) * (size_t)(n_samp + 1) : nullptr;
+    double s0;
+    if (nu == 0) {      // the first simulate starts from the plan's own sample 0
+      const double u0 = t_rel * pl.inv_T;
+      s0 = spline_der_at(c, kk, pl.degree, span_of(kk, pl.degree, pl.n_knots, u0), u0, 0);
+    } else s0 = pl.state[(size_t)b * pl.n_spl + k];
+    double a0 = plant_input_at(pl, kk, c, t_rel, 0);
+    if (db) a0 = a0 + db[0];
+    double acc = 0.0, s = s0;
+    for (int i = 1; i <= n_samp; ++i) {
+      double a1 = plant_input_at(pl, kk, c, t_rel, i);
+      if (db) a1 = a1 + db[i];
+      const double h = (a0 + a1) / 2.0;
+      acc = acc + h;
+      const double m = pl.sample_time * acc;
+      s = s0 + m;
+      if (lg) {
+        lg[(size_t)k * sg->cap + i] = s;
+        if (sg->n_der >= 2) lg[((size_t)sg->n_spl + k) * sg->cap + i] = a1;
+      }
+      a0 = a1;
+    }
+    pl.state_prev[(size_t)b * pl.n_spl + k] = s0;
+    pl.state[(size_t)b * pl.n_spl + k] = s;
+    pl.input_last[(size_t)b * pl.n_spl + k] = a0;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    pl.n_upd[b] = nu + 1;
+    if (log_on) sg->count[b] = cnt + n_col;
+  }
+}
+
+// predict + stop test at the head of an update: reads the OLD plan (coeffs, global memory) and the OLD p[p_t], writes state0 / input0 /
+// t into p.  Returns false when the agent's loop has ended (under_way[b] == 0 on entry, or the travelled state meets the criterion now:
+// the flag is cleared) -- p is left as it is then.  Every thread computes the same numbers from the same loads.  stage (LDS):
+// plant_stage_doubles() doubles.  Barriers inside.
+__device__ __noinline__ bool plant_predict_agent(const PlantArgs& pl, int b, const double* coeffs, double* pb, double tau, double t_value,
+                                                 double* stage) {
+  const int nu = pl.n_upd[b];
+  if (pl.under_way) {
+    bool go = pl.under_way[b] != 0;
+    if (go && nu >= 1) {
+#pragma clang fp contract(off)
+      double e2 = 0.0, u2 = 0.0;
+      for (int k = 0; k < pl.n_spl; ++k) {
+        const double e = pl.state[(size_t)b * pl.n_spl + k] - pb[pl.p_poseT + k], u = pl.input_last[(size_t)b * pl.n_spl + k];
+        const double ee = e * e, uu = u * u;
+        e2 = e2 + ee; u2 = u2 + uu;
+      }
+      if (sqrt(e2) <= pl.stop_tol && sqrt(u2) <= pl.stop_tol) go = false;
+    }
+    __syncthreads();      // (a thread that read the flag after thread 0 cleared it would take the same branch; the barrier keeps the loads ahead anyway)
+    if (!go) {
+      if (threadIdx.x == 0) pl.under_way[b] = 0;
+      return false;
+    }
+  }
+  const double t_rel = pb[pl.p_t];      // (the time the plan was solved at: read by every thread before thread 0 writes the new one)
+  plant_stage(pl, coeffs, stage);
+  if ((int)threadIdx.x < pl.n_spl) {
+#pragma clang fp contract(off)
+    const int k = threadIdx.x, L = pl.n_knots - pl.degree - 1;
+    const double* kk = stage;
+    const double* c = stage + pl.n_knots + k * L;
+    double s0;
+    if (nu <= 0) {      // (no simulate yet: the vehicle stands at the plan's own sample 0)
+      const double u0 = t_rel * pl.inv_T;
+      s0 = spline_der_at(c, kk, pl.degree, span_of(kk, pl.degree, pl.n_knots, u0), u0, 0);
+    } else s0 = pl.state_prev[(size_t)b * pl.n_spl + k];
+    double u_a = plant_input_at(pl, kk, c, t_rel, 0), acc = 0.0;
+    for (int i = 1; i <= pl.n_samp; ++i) {
+      const double u_b = plant_input_at(pl, kk, c, t_rel, i);
+      const double h = (u_a + u_b) / 2.0;
+      acc = acc + h;
+      u_a = u_b;
+    }
+    const double m = pl.sample_time * acc;
+    pb[pl.p_state0 + k] = s0 + m;
+    pb[pl.p_input0 + k] = spline_der_at(c, kk, pl.degree, span_of(kk, pl.degree, pl.n_knots, tau), tau, 1) * pl.inv_T;
+    if (k == 0) pb[pl.p_t] = t_value;
+  }
+  return true;
+}
+
+// stand-alone launches (omgx_batch_plant_simulate / omgx_batch_plant_predict): one workgroup per agent; an agent whose loop the stop
+// rule has ended is not simulated.  The predict launch carries the launch order of the next solve as predict_kernel does.
+__global__ void __launch_bounds__(256)
+plant_simulate_kernel(const double* __restrict__ x, int n_var, const double* __restrict__ p, int n_par, const PlantBlock* __restrict__ pb) {
+  extern __shared__ __align__(16) double lds[];
+  const int b = blockIdx.x;
+  const PlantArgs& pl = pb->pl;
+  if (pl.under_way && pl.under_way[b] == 0) return;
+  plant_simulate_agent(pl, pb->sg.log ? &pb->sg : nullptr, b, x + (size_t)b * n_var + pl.coeff_off, p[(size_t)b * n_par + pl.p_t], lds);
+}
+
+__global__ void __launch_bounds__(256)
+plant_predict_kernel(const double* __restrict__ x, int n_var, double* __restrict__ p, int n_par, int B, const PlantBlock* __restrict__ pb,
+                     double tau, double t_value, const int32_t* __restrict__ ord_iters, int32_t* __restrict__ ord_out,
+                     const double* __restrict__ ord_dw) {
+  extern __shared__ __align__(16) double lds[];
+  if (ord_iters && blockIdx.x == gridDim.x - 1) { order_block(ord_iters, ord_dw, ord_out, B); return; }
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  const PlantArgs& pl = pb->pl;
+  (void)plant_predict_agent(pl, b, x + (size_t)b * n_var + pl.coeff_off, p + (size_t)b * n_par, tau, t_value, lds);
+}
+
+// ---------------------------------------------------------------------------
 // Rollout: K receding-horizon steps of every agent in ONE launch (omgx_batch_rollout).  Agents of a point-to-point batch
 // are independent, so nothing in the protocol asks for a barrier between the steps of different agents: a persistent
 // workgroup takes an agent and runs its whole loop -- ideal prediction from the current plan, obstacles advanced, the
@@ -813,9 +996,12 @@ struct RolloutArgs {
   unsigned long long* stats;            // [K][4] {solved, sum of iterations, max, agents} or nullptr
   int32_t* iters_log; int32_t* status_log;     // [K][n_agents] or nullptr
   StopArgs stop; int stop_on;           // omgx_batch_set_stop: an agent's loop ends at the step its state meets the criterion
+  const PlantBlock* plant;              // omgx_batch_set_plant: read by the PLANT instance only
 };
 
-template <int MODE, bool WAVE_ONLY, bool GEN>
+// PLANT (omgx_batch_set_plant): step (1) is the plant's predict + stop test on the travelled state, and after the solve the plant's
+// simulate takes the place of the log append; every other statement is the same one.
+template <int MODE, bool WAVE_ONLY, bool GEN, bool PLANT = false>
 __global__ void __launch_bounds__(512)
 ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, double* __restrict__ p, double* __restrict__ x,
                    const double* __restrict__ lb, const double* __restrict__ ub, int bounds_shared, double* __restrict__ lam,
@@ -848,7 +1034,20 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
     for (int k = 0; k < K; ++k) {
       const RolloutStep st = rop->steps[k];
       // (1) ideal prediction (predict_kernel): the plan and its time derivatives at tau, the new t
-      {
+      if constexpr (PLANT) {
+        // the plant's: state0 from the state the vehicle had one update ago, the stop rule on the travelled state -- an agent that
+        // has arrived ends its loop here, ahead of the glue of the step: plan, multipliers and status stay as they are
+        if (!plant_predict_agent(rop->plant->pl, b, xb + rop->plant->pl.coeff_off, pb, st.tau, st.t_rel, w.kkt)) {      // (the KKT store is idle between two solves: scratch)
+          if (threadIdx.x == 0) {
+            iters[b] = 0;
+            for (int k2 = k; k2 < K; ++k2) {
+              if (rop->iters_log) rop->iters_log[(size_t)k2 * n_agents + b] = 0;
+              if (rop->status_log) rop->status_log[(size_t)k2 * n_agents + b] = status[b];
+            }
+          }
+          break;
+        }
+      } else {
         const int n_spl = rop->n_spl, degree = rop->degree, n_knots = rop->n_knots, n_out = rop->n_out;
         const int L = n_knots - degree - 1;
         if ((int)threadIdx.x < n_spl) {
@@ -935,8 +1134,15 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
                                st2.v_tot ? st2.v_tot + (size_t)b * st2.n_samp : nullptr);
         }
         // the travelled trajectory of this step (omgx_batch_set_signals): every update of the manoeuvre is logged inside the launch
+        if constexpr (!PLANT) {
         const SignalArgs& sg = reinterpret_cast<const StoreBlock*>(stp)->sg;
         if (sg.log) signals_append_agent(sg, b, w.x + sg.coeff_off, pb[sg.p_t], w.kkt);
+        }
+      }
+      // the vehicle travels this update (plant_simulate_agent): the travelled samples go to the plant's own log
+      if constexpr (PLANT) {
+        const PlantBlock* pk = rop->plant;
+        plant_simulate_agent(pk->pl, pk->sg.log ? &pk->sg : nullptr, b, w.x + pk->pl.coeff_off, pb[pk->pl.p_t], w.kkt);
       }
       __syncthreads();
     }
@@ -1079,8 +1285,16 @@ __global__ void admm_comm_kernel(omgx_admm_layout lay, const int32_t* __restrict
 typedef void (*ipm_rollout_t)(omgx::Dims, omgx::Tables, omgx::Opts, int, double*, double*, const double*, const double*, int, double*,
                               int32_t*, int32_t*, int, double*, size_t, double*, int*, const RolloutArgs*, int, const int32_t*, const StoreArgs*);
 // (the classes of the wave path without quartic terms / cos / sin atoms: the receding-horizon classes that fit LDS)
-static ipm_rollout_t rollout_kernel_for(int mode, int wave_ok, int general) {
+static ipm_rollout_t rollout_kernel_for(int mode, int wave_ok, int general, int plant = 0) {
   if (!wave_ok || general) return nullptr;
+  if (plant) {      // (the plant instances: the same three modes)
+    switch (mode) {
+      case omgx::WS_LDS: return ipm_rollout_kernel<omgx::WS_LDS, true, false, true>;
+      case omgx::WS_JAC_ONLY: return ipm_rollout_kernel<omgx::WS_JAC_ONLY, true, false, true>;
+      case omgx::WS_JAC_HV: return ipm_rollout_kernel<omgx::WS_JAC_HV, true, false, true>;
+      default: return nullptr;
+    }
+  }
   switch (mode) {
     case omgx::WS_LDS: return ipm_rollout_kernel<omgx::WS_LDS, true, false>;
     case omgx::WS_JAC_ONLY: return ipm_rollout_kernel<omgx::WS_JAC_ONLY, true, false>;

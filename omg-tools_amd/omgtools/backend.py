@@ -199,6 +199,16 @@ class CSignalsSpec(C.Structure):
                 ('sample_time', C.c_double), ('inv_T', C.c_double)]
 
 
+class CPlantSpec(C.Structure):
+    """include/omgx.h omgx_plant_spec"""
+    _fields_ = [('state', C.c_void_p), ('state_prev', C.c_void_p), ('input_last', C.c_void_p), ('dist', C.c_void_p),
+                ('n_upd', C.c_void_p), ('overflow', C.c_void_p), ('under_way', C.c_void_p), ('knots', C.c_void_p),
+                ('coeff_off', C.c_int32), ('n_spl', C.c_int32), ('degree', C.c_int32), ('n_knots', C.c_int32),
+                ('n_samp', C.c_int32), ('max_updates', C.c_int32), ('p_t', C.c_int32), ('p_state0', C.c_int32),
+                ('p_input0', C.c_int32), ('p_poseT', C.c_int32), ('sample_time', C.c_double), ('inv_T', C.c_double),
+                ('stop_tol', C.c_double)]
+
+
 PREDICT_IDEAL, PREDICT_RK4 = 0, 1
 ONLY_FAILED = 8
 
@@ -257,6 +267,7 @@ def _ptr(a):
 # else assigns a prototype (tests/test_binding_prototypes_cpu.py holds the table against the header).
 _I, _D, _P, _H = C.c_int32, C.c_double, C.c_void_p, C.c_void_p      # (_H: the omgx_batch handle)
 _TPL, _LAY, _SIG, _STO = C.POINTER(CTemplate), C.POINTER(AdmmLayoutC), C.POINTER(CSignalsSpec), C.POINTER(CStoreSpec)
+_PLA = C.POINTER(CPlantSpec)
 PROTOTYPES = {
     'omgx_version': (C.c_int, []),
     'omgx_last_error': (C.c_char_p, []),
@@ -300,6 +311,9 @@ PROTOTYPES = {
     'omgx_batch_set_signals': (C.c_int, [_H, _SIG]),
     'omgx_batch_signals_append': (C.c_int, [_H, _P, _P, _P, _SIG]),
     'omgx_batch_signals_reduce': (C.c_int, [_H, _SIG, _P, _P]),
+    'omgx_batch_plant_simulate': (C.c_int, [_H, _P, _P, _PLA, _SIG]),
+    'omgx_batch_plant_predict': (C.c_int, [_H, _P, _P, _D, _D, _PLA]),
+    'omgx_batch_set_plant': (C.c_int, [_H, _PLA, _SIG]),
     'omgx_shift_rows': (C.c_int, [_H, _P, _I, _I, _P, _P, _I, _P, _I]),
     'omgx_admm_center': (C.c_int, [_H, _LAY] + [_P] * 3),
     'omgx_admm_update': (C.c_int, [_H, _LAY] + [_P] * 4 + [_D] + [_P] * 4),
@@ -703,6 +717,55 @@ class BatchSolver(object):
         sp = self._signals_spec(log, count, None, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T)
         _check(self.lib, self.lib.omgx_batch_signals_reduce(self._h, C.byref(sp), target.data_ptr(), summary.data_ptr()),
                'omgx_batch_signals_reduce')
+
+    def _plant_spec(self, state, state_prev, input_last, n_upd, overflow, dist, under_way, coeff_off, n_spl, degree, knots, n_samp,
+                    max_updates, p_t, p_state0, p_input0, p_poseT, sample_time, inv_T, stop_tol):
+        """omgx_plant_spec from device tensors: state / state_prev / input_last [B, n_spl] fp64, n_upd / overflow / under_way [B] int32
+        (overflow, under_way may be None), dist [B, n_spl, max_updates, n_samp + 1] fp64 or None."""
+        for nm, a in (('state', state), ('state_prev', state_prev), ('input_last', input_last)):
+            if a.dim() != 2 or tuple(a.shape) != (self.n_agents, int(n_spl)) or not a.is_contiguous() or a.element_size() != 8 or not a.is_floating_point():
+                raise ValueError('%s must be a contiguous [n_agents, n_spl] float64 device tensor' % nm)
+        for nm, a in (('n_upd', n_upd), ('overflow', overflow), ('under_way', under_way)):
+            if a is None and nm != 'n_upd':
+                continue
+            if a is None or a.dim() != 1 or a.shape[0] != self.n_agents or not a.is_contiguous() or a.element_size() != 4 or a.is_floating_point():
+                raise ValueError('%s must be a contiguous [n_agents] int32 device tensor' % nm)
+        if dist is not None and (tuple(dist.shape) != (self.n_agents, int(n_spl), int(max_updates), int(n_samp) + 1) or not dist.is_contiguous()
+                                 or dist.element_size() != 8 or not dist.is_floating_point()):
+            raise ValueError('dist must be a contiguous [n_agents, n_spl, max_updates, n_samp + 1] float64 device tensor')
+        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        sp = CPlantSpec(state.data_ptr(), state_prev.data_ptr(), input_last.data_ptr(), _ptr(dist), n_upd.data_ptr(), _ptr(overflow),
+                        _ptr(under_way), knots.ctypes.data, int(coeff_off), int(n_spl), int(degree), len(knots), int(n_samp),
+                        int(max_updates), int(p_t), int(p_state0), int(p_input0), int(p_poseT), float(sample_time), float(inv_T),
+                        float(stop_tol))
+        sp._keep = (knots, state, state_prev, input_last, n_upd, overflow, dist, under_way)
+        return sp
+
+    def plant_simulate(self, x, p, plant, log=None):
+        """The vehicles travel the update just solved (include/omgx.h omgx_batch_plant_simulate): x, p device tensors, plant: the
+        keyword arguments of `_plant_spec`, log: those of `_signals_spec` (the log that takes the travelled samples) or None."""
+        sp = self._plant_spec(**plant)
+        lg = self._signals_spec(**log) if log is not None else None
+        _check(self.lib, self.lib.omgx_batch_plant_simulate(self._h, x.data_ptr(), p.data_ptr(), C.byref(sp), C.byref(lg) if lg is not None else None),
+               'omgx_batch_plant_simulate')
+
+    def plant_predict(self, x, p, tau, t_value, plant):
+        """Initial conditions of the next solve from the plant, and its stop test (include/omgx.h omgx_batch_plant_predict)."""
+        sp = self._plant_spec(**plant)
+        _check(self.lib, self.lib.omgx_batch_plant_predict(self._h, x.data_ptr(), p.data_ptr(), float(tau), float(t_value), C.byref(sp)),
+               'omgx_batch_plant_predict')
+
+    def set_plant(self, plant=None, log=None):
+        """Every following `rollout` runs with the plant in the loop (include/omgx.h omgx_batch_set_plant; plant=None: off).  The
+        tensors are kept alive here while it is set."""
+        if plant is None:
+            self._plant = None
+            _check(self.lib, self.lib.omgx_batch_set_plant(self._h, None, None), 'omgx_batch_set_plant')
+            return
+        sp = self._plant_spec(**plant)
+        lg = self._signals_spec(**log) if log is not None else None
+        _check(self.lib, self.lib.omgx_batch_set_plant(self._h, C.byref(sp), C.byref(lg) if lg is not None else None), 'omgx_batch_set_plant')
+        self._plant = (sp, lg)
 
     def sample(self, x, coeff_off, n_spl, degree, knots, n_der, t0, dt, n_samp,
                out=None, as_f32=False, device=False):

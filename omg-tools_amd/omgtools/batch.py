@@ -10,11 +10,15 @@ with a primal-dual warm start.
 Layout: `BatchP2P` states that protocol once -- tables and options from the template, `solve_cold`, `step`, `rollout`, the stop rule,
 the log -- and branches on no executor.  Where the [B, *] arrays live and who computes on them sits behind its hooks (`_allocate,
 _predict, _shift, _solve, _cold, _rollout, _norm, _stop_rule, _signals_alloc, _signals_fused, _signals_append_now,
-_signals_summary`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
+_signals_summary, _plant_alloc, _plant_predict, _plant_simulate, _plant_rollout`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
 being the allocator / stream only; no data leaves HBM between steps) and `HostP2P` (`ops=<a host solver object>`: the same
 statements in numpy, how the parity tests and the CPU baseline of bench.py replay the loop; this package never imports the
 oracle).  `BatchP2P(problem, P, ops=...)` hands out the executor `ops` names.  The clock of a step is `splines.step_clock`, the
 obstacle motion `splines.advance_obstacles`: shared with the formation loops.
+
+`BatchP2P.plant` puts a simulated vehicle into the loop (the reference's default `ideal_prediction=False, ideal_update=False`, with an
+optional input disturbance): step (1) then starts the solve from the state the vehicle had one update ago integrated under the planned
+inputs, and after step (3) the vehicle travels the update under the applied inputs (include/omgx.h OMGX_HAS_PLANT has the statements).
 """
 import os
 
@@ -25,6 +29,23 @@ from .splines import advance_obstacles, shiftoverknot_T, step_clock
 
 # solver options of a knot-crossing step (BatchP2P `cross_options`)
 CROSS_OPTIONS = {}
+
+
+def input_disturbance(B, n_in, n_updates, n_samp, n_horizon, fc, stdev, mean=None, seed=0):
+    """A realisation of the reference's input disturbance for `BatchP2P.plant`: [B, n_in, n_updates, n_samp + 1].  The reference's
+    recipe (`Vehicle.add_disturbance`, `vehicles/vehicle.py:433-448`) per agent, input and update: normal noise (mean, stdev) of the
+    length of the planned horizon (`n_horizon` samples), low-pass filtered forwards and backwards by a third-order Butterworth filter
+    with cut-off `fc` (as a fraction of the Nyquist frequency); of it the vehicle meets the samples 0 .. n_samp of the update.  Drawn
+    from a seeded numpy generator: the same array for the same arguments.  stdev / mean: scalars or one value per input."""
+    from scipy.signal import butter, filtfilt
+    stdev = np.broadcast_to(np.asarray(stdev, dtype=float), (int(n_in),))
+    mean = np.zeros(int(n_in)) if mean is None else np.broadcast_to(np.asarray(mean, dtype=float), (int(n_in),))
+    if int(n_horizon) < int(n_samp) + 1:
+        raise ValueError('input_disturbance: the horizon (%d samples) is shorter than an update (%d)' % (n_horizon, n_samp + 1))
+    rng = np.random.default_rng(seed)
+    noise = rng.normal(mean[None, :, None, None], stdev[None, :, None, None], (int(B), int(n_in), int(n_updates), int(n_horizon)))
+    num, den = butter(3, fc, 'low')
+    return np.ascontiguousarray(filtfilt(num, den, noise, axis=-1)[..., :int(n_samp) + 1])
 
 
 def dual_shift_perm(father, extrapolate=True):
@@ -116,6 +137,7 @@ class BatchP2P(object):
         self.time = 0.0
         self.under_way, self.stop_tol = None, 1e-3        # (stop_at_arrival)
         self._sig = None                                  # (record_signals)
+        self._pl = None                                   # (plant)
         self._plan_ready = False                          # (solve_cold has run: x holds a plan)
         # (warm_mu_factor 0.1: a step starts at the barrier parameter the previous solve of the agent ended with, tol / 10,
         # unless the shifted point is far off that central path -- a tenth of its average complementarity then: at tol 1e-3
@@ -140,7 +162,7 @@ class BatchP2P(object):
         self._plan_ready = True
         # the log (record_signals) takes the cold plan ONCE, after the last restart pass: the log inside the solve stays off during
         # the cold solve (an agent that a restart solves again must not be logged twice) and one stand-alone append follows
-        log = self._sig is not None
+        log = self._sig is not None and self._pl is None      # (with the plant in the loop the fused log is off anyway: its simulate writes the log)
         if log:
             self._signals_fused(False)
         try:
@@ -150,6 +172,8 @@ class BatchP2P(object):
                 self._signals_fused(True)
         if log:
             self._signals_append_now()
+        if self._pl is not None:
+            self._plant_simulate()                          # the vehicle travels the first update, from the plan's own sample 0
         return n_restarts
 
     def restart_failed(self, bends=(1.0, -1.0, 2.5, -2.5)):
@@ -163,7 +187,11 @@ class BatchP2P(object):
         host-boundary leg)."""
         t_now, tau, t_rel, crossed = step_clock(self.time, self.update_time, self.knot_time, self.T)
         # (1) ideal prediction on the current plan, (2) horizon bookkeeping: the initial conditions from the plan at tau and the new t
-        self._predict(tau, t_rel)
+        # (with the plant in the loop: from the state the vehicle had one update ago, and the stop test on the travelled state)
+        if self._pl is None:
+            self._predict(tau, t_rel)
+        else:
+            self._plant_predict(tau, t_rel)
         advance_obstacles(self.p, self.obst, self.update_time)      # (a no-op for static obstacles)
         if crossed:
             self._shift()
@@ -172,14 +200,17 @@ class BatchP2P(object):
             before_solve(self)
         # (3) warm-started solve (ordered: `_predict` has asked for the launch order already)
         self._solve(True, events, ordered=True, extra=self.cross_options if crossed else None)
+        if self._pl is not None:
+            self._plant_simulate()                          # (4) the vehicle travels the update
         return crossed
 
     def rollout(self, n_steps, iters_log=None, status_log=None):
         """`n_steps` receding-horizon steps of every agent in ONE launch (`omgx_batch_rollout`): per agent the statements of `step` --
         prediction, obstacles, knot-crossing shift, warm-started solve -- in the same order with the same numbers, without the barrier
         between the steps of different agents (they are independent problems: each vehicle of the reference runs its own
-        `Deployer.update` loop).  For simulation / evaluation runs with ideal prediction; a deployment that feeds measured states back
-        steps with `step`.  Returns the number of knot crossings."""
+        `Deployer.update` loop).  After `plant` the vehicle of every agent is simulated inside the launch too -- prediction from the
+        travelled state, input disturbance, stop test on the travelled state: a disturbance study of a whole fleet in one launch.  A
+        deployment that feeds states measured outside back steps with `step`.  Returns the number of knot crossings."""
         clock, t = [], self.time
         for _ in range(int(n_steps)):
             t, tau, t_rel, crossed = step_clock(t, self.update_time, self.knot_time, self.T)
@@ -211,9 +242,12 @@ class BatchP2P(object):
         """Per agent: the reference's `stop_criterium` (`problems/point2point.py:98-102` -> `vehicles/holonomic.py:145-151`,
         `holonomic3d.py`: |state - poseT| <= stop_tol and |input| <= stop_tol, Euclidean norms, `stop_tol` = 1e-3 by default,
         `vehicles/vehicle.py:72`) on the state the last prediction wrote into p -- the state the vehicle is in at the time of
-        the current update.  Boolean tensor (device loop) / array (host loop); the reference's `Simulator.run` ends a vehicle's
+        the current update -- or, after `plant`, on the travelled state and the last applied input.  Boolean tensor (device loop) / array (host loop); the reference's `Simulator.run` ends a vehicle's
         loop at the first update for which this holds (`execution/simulator.py:39-62`).  Point-mass classes (state0 / input0 / poseT)."""
         st, inp, pose = (self.p[:, o:o + self.n_dim] for o in (self.o_state0, self.o_input0, self._o_pose('arrived')))
+        pl = getattr(self, '_pl', None)
+        if pl is not None:      # (with the plant in the loop: the travelled state and the last applied input, `signals[...][:, -1]`)
+            st, inp = pl['state'], pl['input_last']
         return (self._norm(st - pose) <= stop_tol) & (self._norm(inp) <= stop_tol)
 
     def stop_at_arrival(self, stop_tol=1e-3, on=True):
@@ -247,6 +281,11 @@ class BatchP2P(object):
         n_samp = int(round(self.update_time / float(sample_time), 6))
         if n_samp < 1 or int(max_updates) < 1:
             raise ValueError('record_signals: sample_time must not exceed update_time and max_updates must be positive')
+        if self._pl is not None:
+            if self._pl['sample_time'] != float(sample_time):
+                raise ValueError('record_signals: the plant is simulated with sample_time %g' % self._pl['sample_time'])
+            if self._plan_ready:
+                raise RuntimeError('record_signals: with the plant in the loop the log starts with the first plan -- call it before solve_cold')
         n_der = min(3, self.basis.degree + 1)
         cap = 1 + n_samp * int(max_updates) if cap is None else int(cap)
         if cap < n_samp + 1:
@@ -254,9 +293,66 @@ class BatchP2P(object):
         sig = dict(sample_time=float(sample_time), n_samp=n_samp, cap=cap, n_der=n_der, t_start=self.time)
         sig['log'], sig['count'], sig['overflow'] = self._signals_alloc((self.B, n_der, self.n_spl, cap))
         self._sig = sig
+        if self._pl is not None:
+            return                                          # (the plant's simulate writes the log: the fused spline log stays off)
         self._signals_fused(True)
         if self._plan_ready:
             self._signals_append_now()
+
+    # -- the plant in the loop --------------------------------------------------------------------
+    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True):
+        """Put a simulated vehicle into every agent's loop, as the reference's `Simulator.run` keeps one with its default options
+        `ideal_prediction=False, ideal_update=False` (`vehicles/vehicle.py:73-75`).  From now on, after every solve (`solve_cold`,
+        `step`, every step inside a `rollout` launch) the vehicle travels the update under the plan's inputs plus `disturbance`
+        (`Vehicle.simulate`: the exact integral of the linearly interpolated applied input; n_samp = update_time / sample_time samples),
+        and the next solve starts from the state the vehicle had ONE UPDATE AGO integrated under the undisturbed inputs
+        (`Vehicle.predict`): a disturbance enters the loop one update late, as in the reference.  disturbance: array / tensor
+        [B, n_spl, max_updates, n_samp + 1] added to the inputs (`input_disturbance` draws the reference's), None: none; an update beyond
+        `max_updates` is not simulated and sets the plant's `overflow`.  `arrived` / `stop_at_arrival` test the travelled state and the
+        last applied input; with `record_signals` the log takes the travelled state and the applied input (dinput: the plan's).  Call
+        before `solve_cold`: the vehicle starts from the first plan's own sample 0.  Integrator classes (`ode` = input: Holonomic,
+        Holonomic3D) without the first-order actuator lag.  on=False takes the plant out again."""
+        if not on:
+            if self._pl is not None:
+                self._pl = None
+                self._plant_rollout()
+                if self.under_way is not None:
+                    self._stop_rule(self._o_pose('stop_at_arrival'))
+                if self._sig is not None:
+                    self._signals_fused(True)
+            return
+        lay, label = self.tpl.par_layout, self.veh.label
+        cls_name = type(self.veh).__name__ if hasattr(self.veh, 'ode') else label
+        if any((label, nm) not in lay for nm in ('state0', 'input0', 'poseT')) or self.n_spl != self.n_dim:
+            raise NotImplementedError('plant(): %s is not an integrator class (ode = input: Holonomic, Holonomic3D, parameters state0 / '
+                                      'input0 / poseT); its own model is not simulated in the batched loop' % cls_name)
+        if getattr(self.veh, 'options', {}).get('1storder_delay'):
+            raise NotImplementedError("plant(): %s has '1storder_delay' set; the first-order actuator lag is not simulated in the batched loop" % cls_name)
+        if self._plan_ready:
+            raise RuntimeError('plant(): the vehicle starts from the first plan -- call it before solve_cold')
+        n_samp = int(round(self.update_time / float(sample_time), 6))
+        if n_samp < 1 or int(max_updates) < 1:
+            raise ValueError('plant: sample_time must not exceed update_time and max_updates must be positive')
+        if self._sig is not None and self._sig['sample_time'] != float(sample_time):
+            raise ValueError('plant: the log is kept with sample_time %g' % self._sig['sample_time'])
+        shape = (self.B, self.n_spl, int(max_updates), n_samp + 1)
+        if disturbance is not None and tuple(disturbance.shape) != shape:
+            raise ValueError('plant: disturbance must be [B, n_spl, max_updates, n_samp + 1] = %s, got %s' % (shape, tuple(disturbance.shape)))
+        pl = dict(sample_time=float(sample_time), n_samp=n_samp, max_updates=int(max_updates), o_pose=self._o_pose('plant'))
+        pl.update(self._plant_alloc(disturbance))
+        self._pl = pl
+        if self._sig is not None:
+            self._signals_fused(False)
+        if self.under_way is not None:
+            self._stop_rule(pl['o_pose'])                   # (the rule moves from the predicted to the travelled state)
+
+    def plant_state(self):
+        """dict `state`, `state_prev`, `input_last` [B, n_spl] (where every vehicle is at its last simulated sample, where it was one
+        update earlier, the last applied input), `n_upd` [B] (updates simulated), `overflow` [B] (1: an update beyond `max_updates` was
+        asked for).  Device tensors on the device loop, arrays on the host loop."""
+        if self._pl is None:
+            raise RuntimeError('plant_state(): call plant() first')
+        return dict((nm, self._pl[nm]) for nm in ('state', 'state_prev', 'input_last', 'n_upd', 'overflow'))
 
     def signals(self):
         """The log of `record_signals`: dict with `count` [B] (columns written per agent), `time` [cap] (the time of the first logged
@@ -322,6 +418,12 @@ class DeviceP2P(BatchP2P):
                                1.0 / self.T, self.p_offs, self.o_t, t_rel)
 
     def _shift(self):
+        if self._pl is not None and self.under_way is not None:
+            # (with the plant an agent's loop ends ahead of the glue of the step: a stopped agent keeps plan and multipliers as they are)
+            go = self.under_way != 0
+            self.solver.shift(self.x, go.to(self.torch.uint8), self.shift_entries, self.shift_mats, device=True)
+            self.lam = self.torch.where(go[:, None], self.lam.index_select(1, self._perm_idx) * self._perm_ok, self.lam)
+            return
         self.solver.shift(self.x, self._mask, self.shift_entries, self.shift_mats, device=True)
         self.lam = self.lam.index_select(1, self._perm_idx) * self._perm_ok
 
@@ -382,6 +484,7 @@ class DeviceP2P(BatchP2P):
         return passes
 
     def _rollout(self, tau, t_rel, crossed, iters_log, status_log):
+        self._plant_rollout()
         self.solver.set_options(warm_start=1, max_iter=self.max_iter_step, **self._base_extra)
         if self.straggler_first:
             self.solver.order_by_iters(self.iters, self._order)
@@ -396,7 +499,9 @@ class DeviceP2P(BatchP2P):
     def _stop_rule(self, o_pose):
         """The rule is the solve kernel's: registered with the handle (o_pose None: taken off)."""
         self.under_way = None if o_pose is None else self.torch.ones(self.B, dtype=self.torch.int32, device=self.dev)
-        where = () if o_pose is None else (self.o_state0, self.o_input0, o_pose, self.n_dim, self.stop_tol)
+        # (with the plant in the loop the criterion is the plant's, on the travelled state: the solve kernel gets a rule that never
+        # holds -- a negative tolerance -- and only honours the flags)
+        where = () if o_pose is None else (self.o_state0, self.o_input0, o_pose, self.n_dim, self.stop_tol if self._pl is None else -1.0)
         self.solver.set_stop(*where, under_way=self.under_way)
 
     def _signals_alloc(self, shape):
@@ -420,6 +525,40 @@ class DeviceP2P(BatchP2P):
         """One append of the current plan (x at the time p[:, t]) outside a solve: the stand-alone kernel."""
         g = self._sig
         self.solver.signals_append(self.x, self.p, g['log'], g['count'], g['overflow'], under_way=self.under_way, **self._signals_args())
+
+    def _plant_alloc(self, disturbance):
+        t = self.torch
+        f64 = dict(dtype=t.float64, device=self.dev)
+        out = dict((nm, t.zeros((self.B, self.n_spl), **f64)) for nm in ('state', 'state_prev', 'input_last'))
+        out.update((nm, t.zeros(self.B, dtype=t.int32, device=self.dev)) for nm in ('n_upd', 'overflow'))
+        out['dist'] = None if disturbance is None else t.as_tensor(disturbance, **f64).contiguous()
+        return out
+
+    def _plant_args(self):
+        g = self._pl
+        return dict(state=g['state'], state_prev=g['state_prev'], input_last=g['input_last'], n_upd=g['n_upd'], overflow=g['overflow'],
+                    dist=g['dist'], under_way=self.under_way, coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree,
+                    knots=self.basis.knots, n_samp=g['n_samp'], max_updates=g['max_updates'], p_t=self.o_t, p_state0=self.o_state0,
+                    p_input0=self.o_input0, p_poseT=g['o_pose'], sample_time=g['sample_time'], inv_T=1.0 / self.T, stop_tol=self.stop_tol)
+
+    def _plant_log_args(self):
+        g = self._sig
+        return None if g is None else dict(log=g['log'], count=g['count'], overflow=g['overflow'], **self._signals_args())
+
+    def _plant_predict(self, tau, t_rel):
+        # (as `_predict`: the launch carries the ordering of the next solve as one more workgroup)
+        if self.straggler_first:
+            self.solver.order_by_iters(self.iters, self._order)
+        self.solver.plant_predict(self.x, self.p, tau, t_rel, self._plant_args())
+
+    def _plant_simulate(self):
+        self.solver.plant_simulate(self.x, self.p, self._plant_args(), self._plant_log_args())
+
+    def _plant_rollout(self):
+        """The plant (and the log its simulate writes) as the rollout kernel reads it, registered with the handle; taken off without one."""
+        if self._pl is None:
+            return self.solver.set_plant(None)
+        self.solver.set_plant(self._plant_args(), self._plant_log_args())
 
     def _signals_summary(self, target):
         g, t = self._sig, self.torch
@@ -481,10 +620,12 @@ class HostP2P(BatchP2P):
         self.p[:, self.o_t] = t_rel
 
     def _shift(self):
+        # (with the plant an agent's loop ends ahead of the glue of the step: a stopped agent keeps plan and multipliers as they are)
+        go = self.under_way.copy() if self._pl is not None and self.under_way is not None else np.ones(self.B, dtype=bool)
         for (lo, rows, cols, _), Tm in self._shift_dense:
             blk = self.x[:, lo:lo + rows * cols].reshape(self.B, cols, rows)
-            self.x[:, lo:lo + rows * cols] = (blk @ Tm.T).reshape(self.B, -1)
-        self.lam = np.where(self.perm >= 0, self.lam[:, np.maximum(self.perm, 0)], 0.0)
+            self.x[go, lo:lo + rows * cols] = (blk @ Tm.T).reshape(self.B, -1)[go]
+        self.lam = np.where(go[:, None], np.where(self.perm >= 0, self.lam[:, np.maximum(self.perm, 0)], 0.0), self.lam)
 
     def _solve(self, warm, events=None, ordered=False, extra=None, step_desc=None):
         kw = dict(self.opts, warm_start=int(warm), max_iter=self.max_iter_step if warm else self.max_iter_cold, **(extra or {}))
@@ -503,7 +644,8 @@ class HostP2P(BatchP2P):
             # the stop rule as the solve kernel applies it: the criterion on p ends an agent's loop for good; the agents
             # under way are solved as a batch of their own (independent problems: the same results), the others keep
             # their plan, their multipliers and their status, iters = 0
-            self.under_way &= ~self.arrived(self.stop_tol)
+            if self._pl is None:                 # (with the plant in the loop `_plant_predict` has tested the travelled state)
+                self.under_way &= ~self.arrived(self.stop_tol)
             idx = np.flatnonzero(self.under_way)
             self.iters = np.zeros(self.B, dtype=np.int32)
             if len(idx):
@@ -542,25 +684,88 @@ class HostP2P(BatchP2P):
         g = self._sig
         if g is None:
             return
+        for b in range(self.B):
+            if under_way is None or under_way[b]:
+                self._signals_append_agent(b)
+
+    def _signals_append_agent(self, b):
+        """One append for agent b; returns the column of its sample 0 (written or not), None when the append did not fit."""
+        g = self._sig
         L, ns, n_samp, cap, st = self.L, self.n_spl, g['n_samp'], g['cap'], g['sample_time']
         inv_T = 1.0 / self.T
         bases = [(self.basis, None)] + [self.basis.derivative(o) for o in range(1, g['n_der'])]
+        cnt = int(g['count'][b])
+        first = 0 if cnt == 0 else 1
+        n_col = n_samp + 1 - first
+        if cnt + n_col > cap:
+            g['overflow'][b] = 1
+            return None
+        t_rel = float(self.p[b, self.o_t])
+        u = (t_rel + np.arange(first, n_samp + 1) * st) * inv_T
+        c = self.x[b, self.o_spl:self.o_spl + ns * L].reshape(ns, L)
+        for o, (dbasis, Po) in enumerate(bases):
+            E = dbasis.eval_basis(u) if o == 0 else dbasis.eval_basis(u) @ Po * inv_T ** o
+            g['log'][b, o, :, cnt:cnt + n_col] = c @ E.T
+        g['count'][b] = cnt + n_col
+        return cnt - first
+
+    # -- the plant: `omgx_batch_plant_simulate / _predict` in numpy, the same statements in the same summation order ---------------
+    def _plant_alloc(self, disturbance):
+        if self.pool is not None:
+            raise NotImplementedError('plant: not with a host pool (its workers run the step glue themselves)')
+        out = dict((nm, np.zeros((self.B, self.n_spl))) for nm in ('state', 'state_prev', 'input_last'))
+        out.update((nm, np.zeros(self.B, dtype=np.int32)) for nm in ('n_upd', 'overflow'))
+        out['dist'] = None if disturbance is None else np.ascontiguousarray(disturbance, dtype=float).copy()
+        return out
+
+    def _plant_plan(self, b):
+        """(c, t_rel, u): the plan of agent b [n_spl, L], the time it was solved at, and its inputs (time derivative) at the samples
+        0 .. n_samp of the update [n_spl, n_samp + 1]."""
+        g = self._pl
+        inv_T = 1.0 / self.T
+        c = self.x[b, self.o_spl:self.o_spl + self.n_spl * self.L].reshape(self.n_spl, self.L)
+        t_rel = float(self.p[b, self.o_t])
+        dbasis, P1 = self.basis.derivative(1)
+        tau = (t_rel + np.arange(g['n_samp'] + 1) * g['sample_time']) * inv_T
+        return c, t_rel, c @ (dbasis.eval_basis(tau) @ P1 * inv_T).T
+
+    def _plant_simulate(self):
+        g, sig = self._pl, self._sig
         for b in range(self.B):
-            if under_way is not None and not under_way[b]:
+            if self.under_way is not None and not self.under_way[b]:
                 continue
-            cnt = int(g['count'][b])
-            first = 0 if cnt == 0 else 1
-            n_col = n_samp + 1 - first
-            if cnt + n_col > cap:
+            nu = int(g['n_upd'][b])
+            if nu >= g['max_updates']:
                 g['overflow'][b] = 1
                 continue
-            t_rel = float(self.p[b, self.o_t])
-            u = (t_rel + np.arange(first, n_samp + 1) * st) * inv_T
-            c = self.x[b, self.o_spl:self.o_spl + ns * L].reshape(ns, L)
-            for o, (dbasis, Po) in enumerate(bases):
-                E = dbasis.eval_basis(u) if o == 0 else dbasis.eval_basis(u) @ Po * inv_T ** o
-                g['log'][b, o, :, cnt:cnt + n_col] = c @ E.T
-            g['count'][b] = cnt + n_col
+            c, t_rel, u = self._plant_plan(b)
+            a = u + g['dist'][b, :, nu, :] if g['dist'] is not None else u
+            s0 = c @ self.basis.eval_basis([t_rel / self.T])[0] if nu == 0 else g['state'][b].copy()
+            samples = s0[:, None] + g['sample_time'] * np.cumsum((a[:, :-1] + a[:, 1:]) / 2.0, axis=1)
+            if sig is not None:
+                col = self._signals_append_agent(b)             # (the plan's own columns: column 0 and the dinput row stay)
+                if col is not None:
+                    sig['log'][b, 0, :, col + 1:col + 1 + g['n_samp']] = samples
+                    sig['log'][b, 1, :, col + 1:col + 1 + g['n_samp']] = a[:, 1:]
+            g['state_prev'][b], g['state'][b], g['input_last'][b] = s0, samples[:, -1], a[:, -1]
+            g['n_upd'][b] = nu + 1
+
+    def _plant_predict(self, tau, t_rel):
+        g = self._pl
+        if self.under_way is not None:
+            self.under_way &= ~(self.arrived(self.stop_tol) & (g['n_upd'] >= 1))
+        Ed = self._eval_rows(tau)[1]
+        for b in range(self.B):
+            if self.under_way is not None and not self.under_way[b]:
+                continue
+            c, t_old, u = self._plant_plan(b)
+            s0 = g['state_prev'][b] if g['n_upd'][b] >= 1 else c @ self.basis.eval_basis([t_old / self.T])[0]
+            self.p[b, self.o_state0:self.o_state0 + self.n_spl] = s0 + g['sample_time'] * np.cumsum((u[:, :-1] + u[:, 1:]) / 2.0, axis=1)[:, -1]
+            self.p[b, self.o_input0:self.o_input0 + self.n_spl] = c @ Ed
+            self.p[b, self.o_t] = t_rel
+
+    def _plant_rollout(self):
+        pass
 
     def _signals_summary(self, target):
         return signals_summary_numpy(self._sig['log'], self._sig['count'], target, self._sig['sample_time'])
@@ -698,6 +903,18 @@ class StreamedP2P(object):
     def record_signals(self, sample_time=0.01, max_updates=200, on=True, cap=None):
         """`BatchP2P.record_signals` for every sub-batch (each logs on its own stream)."""
         self._each(lambda m: m.record_signals(sample_time, max_updates, on, cap))
+
+    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True):
+        """`BatchP2P.plant` for every sub-batch, each with its rows of the disturbance."""
+        for (lo, hi), m, st in zip(self.bounds, self.parts, self.streams):
+            with self.torch.cuda.stream(st):
+                m.plant(sample_time, max_updates, None if disturbance is None else disturbance[lo:hi], on)
+
+    def plant_state(self):
+        """`BatchP2P.plant_state` of the whole batch, joined and concatenated like `signals`."""
+        parts = [m.plant_state() for m in self.parts]
+        self.join()
+        return dict((key, self.torch.cat([q[key] for q in parts])) for key in parts[0])
 
     def signals(self):
         """`BatchP2P.signals` of the whole batch: the sub-batches' logs joined and concatenated, like `gather`."""
