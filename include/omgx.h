@@ -357,7 +357,7 @@ int  omgx_batch_shift(omgx_batch* b, double* x, const uint8_t* mask,
  * `spline_extra.py:406-410`, C++ `Vehicle::sampleSplines` Vehicle.cpp:112-129):
  * out[b, d, k, i] = (d-th derivative of spline k of agent b)(t0[b] + i*dt), time
  * in units of the spline domain [0,1]; coeffs [B, n_spl, L] = a slice of x.
- * out is [B, n_der, n_spl, n_samp] fp64 (or fp32 when as_f32 != 0).  knots: host pointer, n_knots <= 40.
+ * out is [B, n_der, n_spl, n_samp] fp64 (or fp32 when as_f32 != 0).  knots: host pointer; the plan: the rule above omgx_store_spec.
  * With OMGX_PTR_DEVICE the call is asynchronous on the handle's stream (omgx_batch_sync to wait). */
 int  omgx_batch_sample(omgx_batch* b, const double* x, int32_t coeff_off,
                        int32_t n_spl, int32_t degree, const double* knots, int32_t n_knots,
@@ -369,7 +369,7 @@ int  omgx_batch_sample(omgx_batch* b, const double* x, int32_t coeff_off,
  * `Vehicle::predict` Vehicle.cpp:61-80; `problems/point2point.py:174-198`): for every agent and
  * spline k < n_spl,  p[p_state0+k] <- spline_k(tau),  p[p_input0+k] <- spline_k'(tau) * inv_T
  * (tau in the spline domain [0,1], inv_T = 1/horizon_time), and p[p_t] <- t_value (p_t < 0: skip).
- * knots: host pointer, n_knots <= 40.  Asynchronous on the handle's stream. */
+ * knots: host pointer; the plan: the rule above omgx_store_spec.  Asynchronous on the handle's stream. */
 int  omgx_batch_predict(omgx_batch* b, const double* x, double* p, int32_t coeff_off, int32_t n_spl,
                         int32_t degree, const double* knots, int32_t n_knots, double tau, double inv_T,
                         int32_t p_state0, int32_t p_input0, int32_t p_t, double t_value);
@@ -422,7 +422,7 @@ typedef struct omgx_rollout_spec {
   const double* tau;            /* [n_steps] host: spline-domain time of the prediction */
   const double* t_rel;          /* [n_steps] host: value written to p[p_t] (time since the last knot) */
   const uint8_t* crossed;       /* [n_steps] host: 1 = the step crosses a knot (shift before its solve) */
-  int32_t coeff_off, n_spl, degree, n_knots, n_out;      /* the plan: as omgx_batch_predict_ex */
+  int32_t coeff_off, n_spl, degree, n_knots, n_out;      /* the plan (the rule above omgx_store_spec, n_spl <= 64); n_out as omgx_batch_predict_ex */
   const double* knots;          /* [n_knots] host */
   const int32_t* p_off;         /* [n_out] host: p offset of the o-th time derivative (-1: skip) */
   int32_t p_t; double inv_T;
@@ -445,12 +445,25 @@ int  omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, d
  * identity on it.  omgx_batch_store samples a given x; omgx_batch_set_store makes every following
  * omgx_batch_solve write the same outputs for the solution it just found, inside the solve kernel (the
  * solution is still in LDS there; sp == NULL switches it off again).  The arrays a spec points at must stay
- * valid while it is set. */
+ * valid while it is set.
+ *
+ * THE PLAN.  coeff_off, n_spl, degree, knots, n_knots and, where time derivatives are taken, inv_T say which coefficients of x
+ * are the vehicle's splines and on which basis.  Every entry that takes them -- omgx_batch_sample, _store / _set_store,
+ * _set_signals / _signals_append / _signals_reduce, _set_plant / _plant_simulate / _plant_predict, _predict / _predict_ex /
+ * _predict_quadrotor, _rollout -- holds them to one rule:
+ *   knots is not null;
+ *   min_degree <= degree <= 5, min_degree = 0 for omgx_batch_sample, 3 for omgx_batch_predict_quadrotor, 1 elsewhere;
+ *   2 * degree + 2 <= n_knots <= 40 (a clamped basis with at least one span; the kernels take the knots by value);
+ *   1 <= n_spl, and n_spl <= 64 where a thread owns a spline (the plant entries, omgx_batch_rollout);
+ *   coeff_off >= 0;  inv_T > 0 wherever the entry carries one;
+ *   coeff_off + n_spl * (n_knots - degree - 1) <= n_var.
+ * A call that breaks it returns OMGX_E_INVALID before anything is launched, and omgx_last_error() names the entry and the field.
+ * All but the last line are judged without a handle, ahead of the "null handle" answer; then come the entry's own limits. */
 typedef struct omgx_store_spec {
   double* out;            /* [B, n_der, n_spl, n_samp] device */
   double* v_tot;          /* [B, n_samp] device, or NULL */
   const double* t0;       /* [B] device: first sample, spline domain */
-  const double* knots;    /* [n_knots] host, n_knots <= 40 */
+  const double* knots;    /* [n_knots] host */
   int32_t coeff_off, n_spl, degree, n_knots, n_der, n_samp;
   double  dt, inv_T;
 } omgx_store_spec;
@@ -479,7 +492,7 @@ typedef struct omgx_signals_spec {
   double*  log;            /* [B, n_der, n_spl, cap] device */
   int32_t* count;          /* [B] device, in/out */
   int32_t* overflow;       /* [B] device, or NULL */
-  const double* knots;     /* [n_knots] host, n_knots <= 40 */
+  const double* knots;     /* [n_knots] host; the plan: the rule above omgx_store_spec */
   int32_t coeff_off, n_spl, degree, n_knots, n_der, n_samp, cap, p_t;
   double  sample_time, inv_T;
 } omgx_signals_spec;
@@ -536,7 +549,7 @@ typedef struct omgx_plant_spec {
   int32_t* n_upd;          /* [B] device, in/out */
   int32_t* overflow;       /* [B] device, or NULL */
   int32_t* under_way;      /* [B] device, or NULL: no stop rule */
-  const double* knots;     /* [n_knots] host, n_knots <= 40 */
+  const double* knots;     /* [n_knots] host; the plan: the rule above omgx_store_spec */
   int32_t coeff_off, n_spl, degree, n_knots, n_samp, max_updates, p_t, p_state0, p_input0, p_poseT;
   double  sample_time, inv_T, stop_tol;
 } omgx_plant_spec;

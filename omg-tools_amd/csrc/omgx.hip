@@ -2,6 +2,7 @@
 // argument structs and the selectors of their template instances are in omgx_kernels.h.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,6 +25,19 @@ thread_local std::string g_err;
       return OMGX_E_HIP;                                                          \
     }                                                                             \
   } while (0)
+
+// a refused call: the message (built on this path only) and the code to return; bad(...): a refused argument
+__attribute__((format(printf, 2, 3))) int fail(int code, const char* fmt, ...) {
+  char buf[256];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+#define bad(...) fail(OMGX_E_INVALID, __VA_ARGS__)
+#define TRY(call) do { const int rc_ = (call); if (rc_ != OMGX_OK) return rc_; } while (0)
 
 constexpr int kThreads = 512;
 constexpr int kLdsLimit = 160 * 1024;
@@ -165,7 +179,7 @@ template <typename T>
 int upload(omgx_batch* b, const T* src, size_t n, const T** dst) {
   void* ptr = nullptr;
   const size_t bytes = (n > 0 ? n : 1) * sizeof(T);
-  { const int rc = arena_alloc(b, bytes, &ptr); if (rc != OMGX_OK) return rc; }
+  TRY(arena_alloc(b, bytes, &ptr));
   if (n > 0) HIPCHK(hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice));
   *dst = (const T*)ptr;
   return OMGX_OK;
@@ -184,19 +198,55 @@ int dalloc(omgx_batch* b, size_t n, T** dst) {
 // handle's stream behind the launches that still read the previous contents (pageable source: staged before the call returns)
 template <typename T>
 int push_args(omgx_batch* b, T** dev, const T& host) {
-  if (!*dev) { const int rc = dalloc(b, (size_t)1, dev); if (rc != OMGX_OK) return rc; }
+  if (!*dev) TRY(dalloc(b, (size_t)1, dev));
   HIPCHK(hipMemcpyAsync(*dev, &host, sizeof(T), hipMemcpyHostToDevice, b->stream));
   return OMGX_OK;
 }
 
-// a knot vector as the kernels take it by value (callers check n_knots <= 40 with their own message)
+// The plan: which coefficients of x are the vehicle's splines and on which basis.  Every glue entry that reads it builds this one
+// value from its arguments or its specification (plan_of), has it judged by check_plan / check_plan_in_x -- the one rule, written
+// out above omgx_store_spec in include/omgx.h -- and copies it into its kernel-argument struct with put_plan.
+struct Plan { int coeff_off, n_spl, degree, n_knots; double inv_T; const double* knots; };
+template <class Spec> Plan plan_of(const Spec& sp) { return {sp.coeff_off, sp.n_spl, sp.degree, sp.n_knots, sp.inv_T, sp.knots}; }
+
+constexpr int kAnySpl = 0x7fffffff, kOwnedSpl = 64;      // max_spl: unlimited / a thread of one wave owns a spline (plant, rollout)
+
+// what can be judged without a handle (`who`: the entry, for the message)
+int check_plan(const char* who, const Plan& pl, int min_degree = 1, int max_spl = kAnySpl, bool has_inv_T = true) {
+  if (!pl.knots) return bad("%s: null knots", who);
+  if (pl.degree < min_degree || pl.degree > 5) return bad("%s: degree = %d outside %d .. 5", who, pl.degree, min_degree);
+  if (pl.n_knots < 2 * pl.degree + 2 || pl.n_knots > 40) return bad("%s: n_knots = %d outside %d .. 40", who, pl.n_knots, 2 * pl.degree + 2);
+  if (pl.n_spl < 1) return bad("%s: n_spl = %d must be positive", who, pl.n_spl);
+  if (pl.n_spl > max_spl) return bad("%s: n_spl = %d outside 1 .. %d", who, pl.n_spl, max_spl);
+  if (pl.coeff_off < 0) return bad("%s: coeff_off = %d is negative", who, pl.coeff_off);
+  if (has_inv_T && !(pl.inv_T > 0.0)) return bad("%s: inv_T = %g must be positive", who, pl.inv_T);
+  return OMGX_OK;
+}
+// ... and what needs one: the n_spl splines of L = n_knots - degree - 1 coefficients lie inside x
+int check_plan_in_x(const omgx_batch* b, const char* who, const Plan& pl) {
+  const int L = pl.n_knots - pl.degree - 1;
+  if (pl.coeff_off + (long long)pl.n_spl * L > b->dims.n_var)
+    return bad("%s: coefficients outside x (coeff_off = %d, %d splines of %d, n_var = %d)", who, pl.coeff_off, pl.n_spl, L, b->dims.n_var);
+  return OMGX_OK;
+}
+// `width` parameters from offset `off` lie inside p
+bool in_p(const omgx_batch* b, int off, int width) { return off >= 0 && off + (long long)width <= b->dims.n_par; }
+
+// a knot vector as the kernels take it by value (n_knots <= 40: check_plan)
 void fill_knots(KnotArg& k, const double* knots, int n_knots) {
   for (int i = 0; i < 40; ++i) k.k[i] = i < n_knots ? knots[i] : 0.0;
 }
+template <class Args> void put_plan(Args& a, const Plan& pl) {
+  a.coeff_off = pl.coeff_off; a.n_spl = pl.n_spl; a.degree = pl.degree; a.n_knots = pl.n_knots; a.inv_T = pl.inv_T;
+  fill_knots(a.knots, pl.knots, pl.n_knots);
+}
+// two specifications or argument structs describe one plan (knot values apart)
+template <class A, class B> bool same_plan(const A& a, const B& b) {
+  return a.coeff_off == b.coeff_off && a.n_spl == b.n_spl && a.degree == b.degree && a.n_knots == b.n_knots;
+}
 
 #define UP(field, count)                                          \
-  do { int rc_ = upload(b, H.field, (size_t)(count), &b->dev.field); \
-       if (rc_ != OMGX_OK) return rc_; } while (0)
+  TRY(upload(b, H.field, (size_t)(count), &b->dev.field))
 
 // smallest spill mode whose LDS part fits one CU (WS_MODES: none does)
 int pick_mode(const omgx::Dims& d, int kkt_doubles, size_t* lds_doubles, size_t* hbm_doubles) {
@@ -273,12 +323,9 @@ int check_template(const omgx_template* t) {
       const int k = t->block_kind[i];
       const long long n = k == OMGX_BLOCK_VAR ? t->n_var : (k == OMGX_BLOCK_PAR ? t->n_par : (k == OMGX_BLOCK_CON ? t->n_con : -1));
       const long long off = t->block_off[i], sz = (long long)t->block_rows[i] * t->block_cols[i];
-      if (n < 0 || off < 0 || t->block_rows[i] < 0 || t->block_cols[i] < 0 || off + sz > n) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "bad template: block %d (kind %d, offset %lld, %d x %d) reaches outside its vector of %lld", i, k, off,
-                 t->block_rows[i], t->block_cols[i], n);
-        g_err = buf; return OMGX_E_INVALID;
-      }
+      if (n < 0 || off < 0 || t->block_rows[i] < 0 || t->block_cols[i] < 0 || off + sz > n)
+        return bad("bad template: block %d (kind %d, offset %lld, %d x %d) reaches outside its vector of %lld", i, k, off, t->block_rows[i],
+                   t->block_cols[i], n);
     }
   }
   return OMGX_OK;
@@ -331,12 +378,7 @@ int build_batch(omgx_batch* b, const omgx_template* t) {
   if (!plan_for_mode(plan, *t, &mode, &nl, &ng, &b->per_cu)) { g_err = "inconsistent template: " + plan.error; return OMGX_E_INVALID; }
   b->dims = plan.dims;
   b->kkt_doubles = plan.kkt_doubles;
-  if (mode == omgx::WS_MODES) {
-    char buf[160];
-    snprintf(buf, sizeof buf, "per-agent O(n_var) vectors (%zu B) exceed the %d B LDS of one CU", nl * sizeof(double), kLdsLimit);
-    g_err = buf;
-    return OMGX_E_TOOLARGE;
-  }
+  if (mode == omgx::WS_MODES) return fail(OMGX_E_TOOLARGE, "per-agent O(n_var) vectors (%zu B) exceed the %d B LDS of one CU", nl * sizeof(double), kLdsLimit);
   b->ws_mode = mode; b->lds_bytes = nl * sizeof(double); b->slab_doubles = ng;
   b->threads = b->per_cu >= 2 ? 256 : kThreads;
   if (const char* e = getenv("OMGX_THREADS")) { const int t2 = atoi(e); if (t2 == 256 || (t2 == 512 && b->per_cu < 2)) b->threads = t2; }      // (developer knob; the workspace of two per CU is sized for four waves)
@@ -361,9 +403,9 @@ int build_batch(omgx_batch* b, const omgx_template* t) {
   // (packed monomial records: 16-byte MonoRec or, with 5..8 atoms per monomial, 24-byte MonoRec8 behind the same pointers)
   if (d.mono_packed == 2) {
     const omgx::MonoRec8* dev8 = nullptr;
-    int rc8 = upload(b, plan.pm_rec8.data(), plan.pm_rec8.size(), &dev8); if (rc8 != OMGX_OK) return rc8;
+    TRY(upload(b, plan.pm_rec8.data(), plan.pm_rec8.size(), &dev8));
     b->dev.pm_rec = (const omgx::MonoRec*)dev8;
-    rc8 = upload(b, plan.sl_ell8.data(), plan.sl_ell8.size(), &dev8); if (rc8 != OMGX_OK) return rc8;
+    TRY(upload(b, plan.sl_ell8.data(), plan.sl_ell8.size(), &dev8));
     b->dev.sl_ell = (const omgx::MonoRec*)dev8;
   } else { UP(pm_rec, plan.pm_rec.size()); UP(sl_ell, plan.sl_ell.size()); }
   UP(row_ptr, d.n_con + 2); UP(t_coef, d.n_terms); UP(t_slot, d.n_terms); UP(t_var, OMGX_TERM_VARS * d.n_terms);
@@ -412,8 +454,7 @@ const char* omgx_status_string(int32_t s) {
 
 int omgx_plan_describe(const omgx_template* tpl, omgx_plan_info* info, int32_t* order) {
   if (!info) { g_err = "null argument"; return OMGX_E_INVALID; }
-  int rc = check_template(tpl);
-  if (rc != OMGX_OK) return rc;
+  TRY(check_template(tpl));
   omgx::HostPlan plan;
   size_t nl = 0, ng = 0;
   int mode = 0, per_cu = 1;
@@ -462,8 +503,7 @@ size_t tpl_fields(const omgx_template& t, omgx_template* m, TplField* f, int ter
 }  // namespace
 
 int omgx_template_write(const omgx_template* tpl, const char* path) {
-  int rc = check_template(tpl);
-  if (rc != OMGX_OK) return rc;
+  TRY(check_template(tpl));
   if (!path) { g_err = "null path"; return OMGX_E_INVALID; }
   FILE* fp = fopen(path, "wb");
   if (!fp) { g_err = std::string("cannot write ") + path; return OMGX_E_INVALID; }
@@ -674,7 +714,7 @@ int create_batch(omgx_batch* b, const omgx_template* tpl) {
 
 int omgx_batch_create(const omgx_template* tpl, int32_t n_agents, int32_t device, omgx_batch** out) {
   if (!tpl || !out || n_agents <= 0 || device < 0) { g_err = "bad argument"; return OMGX_E_INVALID; }
-  { const int rc0 = check_template(tpl); if (rc0 != OMGX_OK) return rc0; }
+  TRY(check_template(tpl));
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device >= count) {
     g_err = "no usable HIP device (the solve path has no CPU fallback)";
@@ -695,8 +735,7 @@ int omgx_batch_set_prepare(omgx_batch* b, int32_t on) {
   if (b->prep_lds > (size_t)kLdsLimit) { g_err = "the setup kernel's LDS (atoms, knots, slots, x) does not fit one CU for this template"; return OMGX_E_INVALID; }
   if (!b->d_prep) {      // the records: allocated when the kernel is first asked for
     HIPCHK(hipSetDevice(b->device));
-    const int rc = dalloc(b, (size_t)b->n_agents * b->prep_doubles, &b->d_prep);
-    if (rc != OMGX_OK) return rc;
+    TRY(dalloc(b, (size_t)b->n_agents * b->prep_doubles, &b->d_prep));
     static int prep_reserved[2] = {0, 0};
     int& res = prep_reserved[b->dims.general ? 1 : 0];
     if ((int)b->prep_lds > res) res = (int)b->prep_lds;
@@ -716,7 +755,7 @@ int omgx_batch_set_stop(omgx_batch* b, int32_t o_state0, int32_t o_input0, int32
   HIPCHK(hipSetDevice(b->device));
   StopArgs sa;
   sa.o_state = o_state0; sa.o_input = o_input0; sa.o_pose = o_poseT; sa.n_dim = n_dim; sa.tol = stop_tol; sa.under_way = under_way;
-  { const int rc = push_args(b, &b->d_stop, sa); if (rc != OMGX_OK) return rc; }
+  TRY(push_args(b, &b->d_stop, sa));
   HIPCHK(hipStreamSynchronize(b->stream));
   b->stop_host = sa;
   b->stop_on = true;
@@ -842,7 +881,7 @@ int omgx_batch_solve(omgx_batch* b, const double* p, const double* x0, const dou
                        (const int32_t*)b->d_range_src, (const int32_t*)b->d_range_dup);
     klb = b->d_lb; kub = b->d_ub;
   }
-  { const int rc_o = flush_order(b); if (rc_o != OMGX_OK) return rc_o; }
+  TRY(flush_order(b));
   // Timing events ride on the dispatch packet of the solve kernel (hipExtLaunchKernelGGL: the packet's own begin / end
   // stamps) -- separate hipEventRecord calls around it cost two more packets, ~25 us of stream time per solve.
   // The caller's pair (omgx_batch_set_launch_events, one launch) goes first, else the handle's own when timing is on.
@@ -926,7 +965,7 @@ int omgx_batch_transfer(omgx_batch* b, int32_t n_seg, const void* const* src, vo
 
 int omgx_batch_sync(omgx_batch* b) {
   if (!b) return OMGX_E_INVALID;
-  { const int rc_o = flush_order(b); if (rc_o != OMGX_OK) return rc_o; }      // (a deferred omgx_batch_order_by_iters)
+  TRY(flush_order(b));      // (a deferred omgx_batch_order_by_iters)
   HIPCHK(hipStreamSynchronize(b->stream));
   return OMGX_OK;
 }
@@ -1057,14 +1096,13 @@ int omgx_batch_shift(omgx_batch* b, double* x, const uint8_t* mask, const int32_
   const int B = b->n_agents;
   const bool dev = flags & OMGX_PTR_DEVICE;
   int max_elems = 0;
-  int rc = stage_shift_tables(b, entries, n_ent, Tmats, n_tmat, d.n_var, &max_elems);
-  if (rc != OMGX_OK) return rc;
+  TRY(stage_shift_tables(b, entries, n_ent, Tmats, n_tmat, d.n_var, &max_elems));
   const uint8_t* d_mask = mask; double* d_xx = x;
   if (!dev) {
     HIPCHK(hipMemcpyAsync(b->d_x, x, (size_t)B * d.n_var * sizeof(double), hipMemcpyHostToDevice, b->stream));
     d_xx = b->d_x;
     if (mask) {
-      if (!b->d_mask) { rc = dalloc(b, (size_t)B, &b->d_mask); if (rc != OMGX_OK) return rc; }      // (one size for the life of the handle)
+      if (!b->d_mask) TRY(dalloc(b, (size_t)B, &b->d_mask));      // (one size for the life of the handle)
       HIPCHK(hipMemcpyAsync(b->d_mask, mask, B, hipMemcpyHostToDevice, b->stream));
       d_mask = b->d_mask;
     }
@@ -1082,11 +1120,13 @@ int omgx_batch_shift(omgx_batch* b, double* x, const uint8_t* mask, const int32_
 int omgx_batch_sample(omgx_batch* b, const double* x, int32_t coeff_off, int32_t n_spl, int32_t degree,
                       const double* knots, int32_t n_knots, int32_t n_der, const double* t0, double dt,
                       int32_t n_samp, void* out, int32_t as_f32, int32_t flags) {
-  if (!b || !x || !knots || !t0 || !out || degree < 0 || degree > 5 || n_der < 1 || n_der > degree + 1 || n_samp <= 0 ||
-      n_spl <= 0 || n_knots < 2 * (degree + 1) || n_knots > 40 || coeff_off < 0 ||
-      coeff_off + n_spl * (n_knots - degree - 1) > b->dims.n_var) {
-    g_err = "bad argument"; return OMGX_E_INVALID;
-  }
+  if (!x || !t0 || !out) return bad("sample: null x / t0 / out");
+  const Plan pl{coeff_off, n_spl, degree, n_knots, 0.0, knots};
+  TRY(check_plan("sample", pl, 0, kAnySpl, false));
+  if (n_der < 1 || n_der > degree + 1) return bad("sample: n_der = %d outside 1 .. degree + 1 = %d", n_der, degree + 1);
+  if (n_samp <= 0) return bad("sample: n_samp = %d must be positive", n_samp);
+  if (!b) return bad("null handle");
+  TRY(check_plan_in_x(b, "sample", pl));
   HIPCHK(hipSetDevice(b->device));
   const omgx::Dims& d = b->dims;
   const int B = b->n_agents;
@@ -1128,27 +1168,25 @@ int omgx_batch_sample(omgx_batch* b, const double* x, int32_t coeff_off, int32_t
 }
 
 namespace {
-int fill_store(omgx_batch* b, const omgx_store_spec* sp, StoreArgs* st) {
-  if (!sp->out || !sp->t0 || !sp->knots || sp->degree < 1 || sp->degree > 5 || sp->n_der < 1 || sp->n_der > sp->degree + 1 ||
-      sp->n_samp <= 0 || sp->n_spl <= 0 || sp->n_knots > 40 || sp->n_knots < 2 * sp->degree + 2 || !(sp->inv_T > 0.0) ||
-      (sp->v_tot && sp->n_der < 2)) {
-    g_err = "bad store specification"; return OMGX_E_INVALID;
-  }
-  const int L = sp->n_knots - sp->degree - 1;
-  if (sp->coeff_off < 0 || sp->coeff_off + sp->n_spl * L > b->dims.n_var) { g_err = "store: coefficients outside x"; return OMGX_E_INVALID; }
-  st->out = sp->out; st->v_tot = sp->v_tot; st->t0 = sp->t0;
-  st->coeff_off = sp->coeff_off; st->n_spl = sp->n_spl; st->degree = sp->degree; st->n_knots = sp->n_knots;
-  st->n_der = sp->n_der; st->n_samp = sp->n_samp; st->dt = sp->dt; st->inv_T = sp->inv_T;
-  fill_knots(st->knots, sp->knots, sp->n_knots);
+int fill_store(const omgx_batch* b, const omgx_store_spec* sp, StoreArgs* st) {
+  if (!sp->out || !sp->t0) return bad("store: null out / t0");
+  const Plan pl = plan_of(*sp);
+  TRY(check_plan("store", pl));
+  if (sp->n_der < 1 || sp->n_der > sp->degree + 1) return bad("store: n_der = %d outside 1 .. degree + 1 = %d", sp->n_der, sp->degree + 1);
+  if (sp->n_samp <= 0) return bad("store: n_samp = %d must be positive", sp->n_samp);
+  if (sp->v_tot && sp->n_der < 2) return bad("store: v_tot needs n_der >= 2");
+  if (!b) return bad("null handle");
+  TRY(check_plan_in_x(b, "store", pl));
+  put_plan(*st, pl);
+  st->out = sp->out; st->v_tot = sp->v_tot; st->t0 = sp->t0; st->n_der = sp->n_der; st->n_samp = sp->n_samp; st->dt = sp->dt;
   return OMGX_OK;
 }
 }  // namespace
 
 int omgx_batch_store(omgx_batch* b, const double* x, const omgx_store_spec* sp) {
-  if (!b || !x || !sp) { g_err = "null argument"; return OMGX_E_INVALID; }
+  if (!x || !sp) return bad("null argument");
   StoreArgs st;
-  int rc = fill_store(b, sp, &st);
-  if (rc != OMGX_OK) return rc;
+  TRY(fill_store(b, sp, &st));
   HIPCHK(hipSetDevice(b->device));
   const dim3 grid((st.n_samp + OMGX_SAMPLE_CHUNK - 1) / OMGX_SAMPLE_CHUNK, b->n_agents), block(256);
   const size_t lds = sample_scratch_doubles(st.n_spl, st.degree, st.n_knots, st.n_der) * sizeof(double);
@@ -1169,65 +1207,45 @@ int upload_store_block(omgx_batch* b) {
 
 // the part of a log specification that can be judged without a handle
 int check_signals_spec(const omgx_signals_spec* sp) {
-  char buf[200];
-  if (!sp->log || !sp->count || !sp->knots) { g_err = "signals: null log / count / knots"; return OMGX_E_INVALID; }
-  if (sp->degree < 1 || sp->degree > 5) { g_err = "signals: degree outside 1 .. 5"; return OMGX_E_INVALID; }
-  if (sp->n_knots > 40 || sp->n_knots < 2 * sp->degree + 2) {
-    snprintf(buf, sizeof buf, "signals: n_knots = %d outside %d .. 40", sp->n_knots, 2 * sp->degree + 2);
-    g_err = buf; return OMGX_E_INVALID;
-  }
-  if (sp->n_der < 1 || sp->n_der > sp->degree + 1) {
-    snprintf(buf, sizeof buf, "signals: n_der = %d outside 1 .. degree + 1 = %d", sp->n_der, sp->degree + 1);
-    g_err = buf; return OMGX_E_INVALID;
-  }
-  if (sp->n_spl <= 0 || sp->n_samp <= 0 || !(sp->sample_time > 0.0) || !(sp->inv_T > 0.0)) {
-    g_err = "signals: n_spl, n_samp, sample_time and inv_T must be positive"; return OMGX_E_INVALID;
-  }
-  if (sp->cap < sp->n_samp + 1) {
-    snprintf(buf, sizeof buf, "signals: cap = %d holds less than the first append (n_samp + 1 = %d columns)", sp->cap, sp->n_samp + 1);
-    g_err = buf; return OMGX_E_INVALID;
-  }
-  if (sp->p_t < 0 || sp->coeff_off < 0) { g_err = "signals: p_t / coeff_off out of range"; return OMGX_E_INVALID; }
+  if (!sp->log || !sp->count) return bad("signals: null log / count");
+  TRY(check_plan("signals", plan_of(*sp)));
+  if (sp->n_der < 1 || sp->n_der > sp->degree + 1) return bad("signals: n_der = %d outside 1 .. degree + 1 = %d", sp->n_der, sp->degree + 1);
+  if (sp->n_samp <= 0 || !(sp->sample_time > 0.0)) return bad("signals: n_samp and sample_time must be positive");
+  if (sp->cap < sp->n_samp + 1) return bad("signals: cap = %d holds less than the first append (n_samp + 1 = %d columns)", sp->cap, sp->n_samp + 1);
+  if (sp->p_t < 0) return bad("signals: p_t = %d is negative", sp->p_t);
   return OMGX_OK;
 }
 
-int fill_signals(omgx_batch* b, const omgx_signals_spec* sp, SignalArgs* sg) {
-  if (!sp) { g_err = "null argument"; return OMGX_E_INVALID; }
-  const int rc = check_signals_spec(sp);
-  if (rc != OMGX_OK) return rc;
-  if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
-  const int L = sp->n_knots - sp->degree - 1;
-  if (sp->coeff_off + sp->n_spl * L > b->dims.n_var) { g_err = "signals: coefficients outside x"; return OMGX_E_INVALID; }
-  if (sp->p_t >= b->dims.n_par) { g_err = "signals: p_t out of range"; return OMGX_E_INVALID; }
+int fill_signals(const omgx_batch* b, const omgx_signals_spec* sp, SignalArgs* sg) {
+  if (!sp) return bad("null argument");
+  TRY(check_signals_spec(sp));
+  if (!b) return bad("null handle");
+  TRY(check_plan_in_x(b, "signals", plan_of(*sp)));
+  if (!in_p(b, sp->p_t, 1)) return bad("signals: p_t = %d outside p", sp->p_t);
+  put_plan(*sg, plan_of(*sp));
   sg->log = sp->log; sg->count = sp->count; sg->overflow = sp->overflow;
-  sg->coeff_off = sp->coeff_off; sg->n_spl = sp->n_spl; sg->degree = sp->degree; sg->n_knots = sp->n_knots; sg->n_der = sp->n_der;
-  sg->n_samp = sp->n_samp; sg->cap = sp->cap; sg->p_t = sp->p_t; sg->sample_time = sp->sample_time; sg->inv_T = sp->inv_T;
-  fill_knots(sg->knots, sp->knots, sp->n_knots);
+  sg->n_der = sp->n_der; sg->n_samp = sp->n_samp; sg->cap = sp->cap; sg->p_t = sp->p_t; sg->sample_time = sp->sample_time;
   return OMGX_OK;
 }
 }  // namespace
 
 int omgx_batch_set_signals(omgx_batch* b, const omgx_signals_spec* sp) {
   if (!sp) {
-    if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
+    if (!b) return bad("null handle");
     b->signals = SignalArgs{};
     return b->store.out ? upload_store_block(b) : OMGX_OK;
   }
   SignalArgs sg;
-  const int rc = fill_signals(b, sp, &sg);
-  if (rc != OMGX_OK) return rc;
-  if (sample_scratch_doubles(sg.n_spl, sg.degree, sg.n_knots, sg.n_der) > (size_t)b->kkt_doubles) {
-    g_err = "signals: the per-agent scratch does not fit the KKT store"; return OMGX_E_TOOLARGE;
-  }
+  TRY(fill_signals(b, sp, &sg));
+  if (sample_scratch_doubles(sg.n_spl, sg.degree, sg.n_knots, sg.n_der) > (size_t)b->kkt_doubles) return fail(OMGX_E_TOOLARGE, "signals: the per-agent scratch does not fit the KKT store");
   b->signals = sg;
   return upload_store_block(b);
 }
 
 int omgx_batch_signals_append(omgx_batch* b, const double* x, const double* p, const int32_t* under_way, const omgx_signals_spec* sp) {
   SignalArgs sg;
-  const int rc = fill_signals(b, sp, &sg);
-  if (rc != OMGX_OK) return rc;
-  if (!x || !p) { g_err = "null argument"; return OMGX_E_INVALID; }
+  TRY(fill_signals(b, sp, &sg));
+  if (!x || !p) return bad("null argument");
   HIPCHK(hipSetDevice(b->device));
   const size_t lds = sample_scratch_doubles(sg.n_spl, sg.degree, sg.n_knots, sg.n_der) * sizeof(double);
   if (lds > 64 * 1024) { g_err = "signals: the per-agent scratch exceeds 64 KiB of LDS"; return OMGX_E_TOOLARGE; }
@@ -1238,9 +1256,8 @@ int omgx_batch_signals_append(omgx_batch* b, const double* x, const double* p, c
 
 int omgx_batch_signals_reduce(omgx_batch* b, const omgx_signals_spec* sp, const double* target, double* summary) {
   SignalArgs sg;
-  const int rc = fill_signals(b, sp, &sg);
-  if (rc != OMGX_OK) return rc;
-  if (!target || !summary) { g_err = "null argument"; return OMGX_E_INVALID; }
+  TRY(fill_signals(b, sp, &sg));
+  if (!target || !summary) return bad("null argument");
   HIPCHK(hipSetDevice(b->device));
   hipLaunchKernelGGL(signals_reduce_kernel, dim3(b->n_agents), dim3(64), 0, b->stream, (const double*)sg.log, (const int32_t*)sg.count, target,
                      summary, sg.n_der, sg.n_spl, sg.cap, sg.sample_time);
@@ -1251,42 +1268,29 @@ int omgx_batch_signals_reduce(omgx_batch* b, const omgx_signals_spec* sp, const 
 namespace {
 // A plant specification and the log that goes with it -> the block the kernels read.  The checks that need no handle come first
 // (null handle, n_knots, n_samp ... are refused without a device).
-int fill_plant(omgx_batch* b, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp, PlantBlock* blk) {
-  char buf[200];
-  if (!sp) { g_err = "null argument"; return OMGX_E_INVALID; }
-  if (!sp->state || !sp->state_prev || !sp->input_last || !sp->n_upd || !sp->knots) { g_err = "plant: null state / state_prev / input_last / n_upd / knots"; return OMGX_E_INVALID; }
-  if (sp->degree < 1 || sp->degree > 5) { g_err = "plant: degree outside 1 .. 5"; return OMGX_E_INVALID; }
-  if (sp->n_knots > 40 || sp->n_knots < 2 * sp->degree + 2) {
-    snprintf(buf, sizeof buf, "plant: n_knots = %d outside %d .. 40", sp->n_knots, 2 * sp->degree + 2);
-    g_err = buf; return OMGX_E_INVALID;
-  }
-  if (sp->n_samp < 1) { snprintf(buf, sizeof buf, "plant: n_samp = %d, at least one sample interval per update is needed", sp->n_samp); g_err = buf; return OMGX_E_INVALID; }
-  if (sp->n_spl <= 0 || sp->n_spl > 64 || sp->max_updates < 1 || !(sp->sample_time > 0.0) || !(sp->inv_T > 0.0) || sp->stop_tol != sp->stop_tol) {
-    g_err = "plant: n_spl (1 .. 64), max_updates, sample_time and inv_T must be positive, stop_tol a number"; return OMGX_E_INVALID;
-  }
+int fill_plant(const omgx_batch* b, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp, PlantBlock* blk) {
+  if (!sp) return bad("null argument");
+  if (!sp->state || !sp->state_prev || !sp->input_last || !sp->n_upd) return bad("plant: null state / state_prev / input_last / n_upd");
+  const Plan plan = plan_of(*sp);
+  TRY(check_plan("plant", plan, 1, kOwnedSpl));
+  if (sp->n_samp < 1) return bad("plant: n_samp = %d, at least one sample interval per update is needed", sp->n_samp);
+  if (sp->max_updates < 1 || !(sp->sample_time > 0.0) || sp->stop_tol != sp->stop_tol)
+    return bad("plant: max_updates and sample_time must be positive, stop_tol a number");
   if (log_sp) {
-    const int rc = check_signals_spec(log_sp);
-    if (rc != OMGX_OK) return rc;
-    if (log_sp->n_spl != sp->n_spl || log_sp->n_samp != sp->n_samp || log_sp->degree != sp->degree || log_sp->n_knots != sp->n_knots ||
-        log_sp->coeff_off != sp->coeff_off || log_sp->sample_time != sp->sample_time || log_sp->inv_T != sp->inv_T || log_sp->n_der < 2) {
-      g_err = "plant: the log must be one of the plant's plan (coeff_off, n_spl, degree, n_knots, n_samp, sample_time, inv_T) with n_der >= 2";
-      return OMGX_E_INVALID;
-    }
+    TRY(check_signals_spec(log_sp));
+    if (!same_plan(*log_sp, *sp) || log_sp->inv_T != sp->inv_T || log_sp->n_samp != sp->n_samp || log_sp->sample_time != sp->sample_time || log_sp->n_der < 2)
+      return bad("plant: the log must be one of the plant's plan (coeff_off, n_spl, degree, n_knots, n_samp, sample_time, inv_T) with n_der >= 2");
   }
-  if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
-  const omgx::Dims& d = b->dims;
-  const int L = sp->n_knots - sp->degree - 1;
-  if (sp->coeff_off < 0 || sp->coeff_off + sp->n_spl * L > d.n_var) { g_err = "plant: coefficients outside x"; return OMGX_E_INVALID; }
-  const int32_t offs[4] = {sp->p_state0, sp->p_input0, sp->p_poseT, sp->p_t};
-  for (int q = 0; q < 4; ++q)
-    if (offs[q] < 0 || offs[q] + (q < 3 ? sp->n_spl : 1) > d.n_par) { g_err = "plant: p_state0 / p_input0 / p_poseT / p_t outside p"; return OMGX_E_INVALID; }
+  if (!b) return bad("null handle");
+  TRY(check_plan_in_x(b, "plant", plan));
+  if (!in_p(b, sp->p_state0, sp->n_spl) || !in_p(b, sp->p_input0, sp->n_spl) || !in_p(b, sp->p_poseT, sp->n_spl) || !in_p(b, sp->p_t, 1))
+    return bad("plant: p_state0 / p_input0 / p_poseT / p_t outside p");
   PlantArgs& pl = blk->pl;
+  put_plan(pl, plan);
   pl.state = sp->state; pl.state_prev = sp->state_prev; pl.input_last = sp->input_last; pl.dist = sp->dist; pl.n_upd = sp->n_upd;
-  pl.overflow = sp->overflow; pl.under_way = sp->under_way;
-  pl.coeff_off = sp->coeff_off; pl.n_spl = sp->n_spl; pl.degree = sp->degree; pl.n_knots = sp->n_knots; pl.n_samp = sp->n_samp;
-  pl.max_updates = sp->max_updates; pl.p_t = sp->p_t; pl.p_state0 = sp->p_state0; pl.p_input0 = sp->p_input0; pl.p_poseT = sp->p_poseT;
-  pl.sample_time = sp->sample_time; pl.inv_T = sp->inv_T; pl.stop_tol = sp->stop_tol;
-  fill_knots(pl.knots, sp->knots, sp->n_knots);
+  pl.overflow = sp->overflow; pl.under_way = sp->under_way; pl.n_samp = sp->n_samp; pl.max_updates = sp->max_updates;
+  pl.p_t = sp->p_t; pl.p_state0 = sp->p_state0; pl.p_input0 = sp->p_input0; pl.p_poseT = sp->p_poseT;
+  pl.sample_time = sp->sample_time; pl.stop_tol = sp->stop_tol;
   blk->sg = SignalArgs{};
   return log_sp ? fill_signals(b, log_sp, &blk->sg) : OMGX_OK;
 }
@@ -1299,33 +1303,29 @@ size_t plant_lds_doubles(const PlantBlock& blk) {
 
 int omgx_batch_set_plant(omgx_batch* b, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp) {
   if (!sp) {
-    if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
+    if (!b) return bad("null handle");
     b->plant_on = false;
     return OMGX_OK;
   }
   PlantBlock blk;
-  const int rc = fill_plant(b, sp, log_sp, &blk);
-  if (rc != OMGX_OK) return rc;
+  TRY(fill_plant(b, sp, log_sp, &blk));
   b->plant_on = false;      // (a failed registration leaves the plant OFF)
-  if (plant_lds_doubles(blk) > (size_t)b->kkt_doubles) {
-    g_err = "plant: the per-agent scratch (staged plan, log) does not fit the KKT store"; return OMGX_E_TOOLARGE;
-  }
+  if (plant_lds_doubles(blk) > (size_t)b->kkt_doubles) return fail(OMGX_E_TOOLARGE, "plant: the per-agent scratch (staged plan, log) does not fit the KKT store");
   HIPCHK(hipSetDevice(b->device));
   b->plant_host = blk;
-  { const int rcp = push_args(b, &b->d_plant, b->plant_host); if (rcp != OMGX_OK) return rcp; }
+  TRY(push_args(b, &b->d_plant, b->plant_host));
   b->plant_on = true;
   return OMGX_OK;
 }
 
 int omgx_batch_plant_simulate(omgx_batch* b, const double* x, const double* p, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp) {
   PlantBlock blk;
-  const int rc = fill_plant(b, sp, log_sp, &blk);
-  if (rc != OMGX_OK) return rc;
-  if (!x || !p) { g_err = "null argument"; return OMGX_E_INVALID; }
+  TRY(fill_plant(b, sp, log_sp, &blk));
+  if (!x || !p) return bad("null argument");
   const size_t lds = plant_lds_doubles(blk) * sizeof(double);
   if (lds > 64 * 1024) { g_err = "plant: the per-agent scratch (staged plan, log) exceeds 64 KiB of LDS"; return OMGX_E_TOOLARGE; }
   HIPCHK(hipSetDevice(b->device));
-  { const int rcp = push_args(b, &b->d_plant_call, blk); if (rcp != OMGX_OK) return rcp; }
+  TRY(push_args(b, &b->d_plant_call, blk));
   hipLaunchKernelGGL(plant_simulate_kernel, dim3(b->n_agents), dim3(256), lds, b->stream, x, b->dims.n_var, p, b->dims.n_par,
                      (const PlantBlock*)b->d_plant_call);
   HIPCHK(hipGetLastError());
@@ -1334,11 +1334,10 @@ int omgx_batch_plant_simulate(omgx_batch* b, const double* x, const double* p, c
 
 int omgx_batch_plant_predict(omgx_batch* b, const double* x, double* p, double tau, double t_value, const omgx_plant_spec* sp) {
   PlantBlock blk;
-  const int rc = fill_plant(b, sp, nullptr, &blk);
-  if (rc != OMGX_OK) return rc;
-  if (!x || !p || tau != tau) { g_err = "null argument"; return OMGX_E_INVALID; }
+  TRY(fill_plant(b, sp, nullptr, &blk));
+  if (!x || !p || tau != tau) return bad("null argument");
   HIPCHK(hipSetDevice(b->device));
-  { const int rcp = push_args(b, &b->d_plant_call, blk); if (rcp != OMGX_OK) return rcp; }
+  TRY(push_args(b, &b->d_plant_call, blk));
   const int32_t* oi = b->pend_iters; int32_t* oo = b->pend_order;
   b->pend_iters = nullptr; b->pend_order = nullptr;
   hipLaunchKernelGGL(plant_predict_kernel, dim3(b->n_agents + (oi ? 1 : 0)), dim3(64), plant_stage_doubles(blk.pl.n_spl, blk.pl.degree, blk.pl.n_knots) * sizeof(double), b->stream, x, b->dims.n_var, p, b->dims.n_par, b->n_agents,
@@ -1348,33 +1347,42 @@ int omgx_batch_plant_predict(omgx_batch* b, const double* x, double* p, double t
 }
 
 int omgx_batch_set_store(omgx_batch* b, const omgx_store_spec* sp) {
-  if (!b) { g_err = "null handle"; return OMGX_E_INVALID; }
-  if (!sp) { b->store = StoreArgs{}; return b->signals.log ? upload_store_block(b) : OMGX_OK; }
-  HIPCHK(hipSetDevice(b->device));
-  StoreArgs st;
-  int rc = fill_store(b, sp, &st);
-  if (rc != OMGX_OK) return rc;
-  if (sample_scratch_doubles(st.n_spl, st.degree, st.n_knots, st.n_der) > (size_t)b->kkt_doubles) {
-    g_err = "store: the per-agent scratch does not fit the KKT store"; return OMGX_E_TOOLARGE;
+  if (!sp) {
+    if (!b) return bad("null handle");
+    b->store = StoreArgs{};
+    return b->signals.log ? upload_store_block(b) : OMGX_OK;
   }
+  StoreArgs st;
+  TRY(fill_store(b, sp, &st));
+  if (sample_scratch_doubles(st.n_spl, st.degree, st.n_knots, st.n_der) > (size_t)b->kkt_doubles) return fail(OMGX_E_TOOLARGE, "store: the per-agent scratch does not fit the KKT store");
   b->store = st;
   return upload_store_block(b);
 }
 
 namespace {
-// What the two predict entries share: offsets checked against x / p (n_spl splines per output), then the argument block
-int fill_predict(const omgx_batch* b, PredictArgs& a, int coeff_off, int n_spl, int degree, const double* knots, int n_knots, double tau,
-                 double inv_T, int n_out, const int32_t* p_off, int p_t, double t_value, int mode, const double* state_in, int n_sub, double dtau) {
-  const omgx::Dims& d = b->dims;
-  const int L = n_knots - degree - 1;
-  if (coeff_off < 0 || coeff_off + n_spl * L > d.n_var || p_t >= d.n_par) { g_err = "predict: offsets outside x / p"; return OMGX_E_INVALID; }
+// What the predict entries and the rollout share.  Without a handle: the plan and the outputs asked for ...
+int check_predict(const char* who, const Plan& pl, int min_degree, int max_spl, const void* x, const void* p, const int32_t* p_off, int n_out) {
+  if (!x || !p || !p_off) return bad("%s: null x / p / p_off", who);
+  TRY(check_plan(who, pl, min_degree, max_spl));
+  if (n_out < 1 || n_out > 4 || n_out > pl.degree + 1) return bad("%s: n_out = %d outside 1 .. min(4, degree + 1)", who, n_out);
+  return OMGX_OK;
+}
+// ... with one: the plan inside x, the offsets inside p (n_spl parameters per output; a negative offset or p_t: skipped), into a.p_off
+int check_predict_in_xp(const omgx_batch* b, const char* who, const Plan& pl, int n_out, const int32_t* p_off, int p_t, int* a_p_off) {
+  TRY(check_plan_in_x(b, who, pl));
+  if (p_t >= 0 && !in_p(b, p_t, 1)) return bad("%s: p_t = %d outside p", who, p_t);
   for (int o = 0; o < 4; ++o) {
-    a.p_off[o] = o < n_out ? p_off[o] : -1;
-    if (a.p_off[o] >= 0 && a.p_off[o] + n_spl > d.n_par) { g_err = "predict: offsets outside p"; return OMGX_E_INVALID; }
+    a_p_off[o] = o < n_out ? p_off[o] : -1;
+    if (a_p_off[o] >= 0 && !in_p(b, a_p_off[o], pl.n_spl)) return bad("%s: p_off[%d] = %d outside p", who, o, a_p_off[o]);
   }
-  fill_knots(a.kn, knots, n_knots);
-  a.coeff_off = coeff_off; a.n_spl = n_spl; a.degree = degree; a.n_knots = n_knots; a.n_out = n_out;
-  a.tau = tau; a.inv_T = inv_T; a.p_t = p_t; a.t_value = t_value; a.mode = mode; a.state_in = state_in; a.n_sub = n_sub; a.dtau = dtau;
+  return OMGX_OK;
+}
+int fill_predict(const omgx_batch* b, const char* who, PredictArgs& a, const Plan& pl, double tau, int n_out, const int32_t* p_off, int p_t,
+                 double t_value, int mode, const double* state_in, int n_sub, double dtau) {
+  if (!b) return bad("null handle");
+  TRY(check_predict_in_xp(b, who, pl, n_out, p_off, p_t, a.p_off));
+  put_plan(a, pl);
+  a.n_out = n_out; a.tau = tau; a.p_t = p_t; a.t_value = t_value; a.mode = mode; a.state_in = state_in; a.n_sub = n_sub; a.dtau = dtau;
   return OMGX_OK;
 }
 }  // namespace
@@ -1382,11 +1390,11 @@ int fill_predict(const omgx_batch* b, PredictArgs& a, int coeff_off, int n_spl, 
 int omgx_batch_predict_quadrotor(omgx_batch* b, const double* x, double* p, int32_t coeff_off, int32_t degree, const double* knots,
                                  int32_t n_knots, double tau, double inv_T, int32_t n_out, const int32_t* p_off, int32_t p_t,
                                  double t_value, const double* state_in, double* state_out, int32_t n_sub, double dtau, double g) {
-  if (!b || !x || !p || !knots || !p_off || !state_in || n_knots > 40 || degree > 5 || degree < 3 || n_out < 1 || n_out > 4 ||
-      n_out > degree + 1 || n_sub < 1 || !(dtau > 0.0) || !(g > 0.0)) { g_err = "bad argument"; return OMGX_E_INVALID; }
+  const Plan pl{coeff_off, 2, degree, n_knots, inv_T, knots};
+  TRY(check_predict("predict_quadrotor", pl, 3, kAnySpl, x, p, p_off, n_out));
+  if (!state_in || n_sub < 1 || !(dtau > 0.0) || !(g > 0.0)) return bad("predict_quadrotor: state_in is null, or n_sub, dtau or g not positive");
   PredictArgs a;
-  const int rc = fill_predict(b, a, coeff_off, 2, degree, knots, n_knots, tau, inv_T, n_out, p_off, p_t, t_value, OMGX_PREDICT_RK4, state_in, n_sub, dtau);
-  if (rc != OMGX_OK) return rc;
+  TRY(fill_predict(b, "predict_quadrotor", a, pl, tau, n_out, p_off, p_t, t_value, OMGX_PREDICT_RK4, state_in, n_sub, dtau));
   HIPCHK(hipSetDevice(b->device));
   hipLaunchKernelGGL(predict_quadrotor_kernel, dim3((b->n_agents + 255) / 256), dim3(256), 0, b->stream, x, b->dims.n_var, p, b->dims.n_par, b->n_agents, a, g, state_out);
   HIPCHK(hipGetLastError());
@@ -1395,45 +1403,32 @@ int omgx_batch_predict_quadrotor(omgx_batch* b, const double* x, double* p, int3
 
 int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, double* x, const double* lbg, const double* ubg,
                        double* lam_g, int32_t* status, int32_t* iters, int32_t flags) {
-  if (!b || !sp || !p || !x || !lbg || !ubg || !lam_g || !status || !iters) { g_err = "null argument"; return OMGX_E_INVALID; }
-  if (!(flags & OMGX_PTR_DEVICE) || !(flags & OMGX_BOUNDS_DEVICE)) { g_err = "rollout: device pointers only (OMGX_PTR_DEVICE | OMGX_BOUNDS_DEVICE)"; return OMGX_E_INVALID; }
+  if (!sp || !lbg || !ubg || !lam_g || !status || !iters) return bad("null argument");
+  const Plan pl = plan_of(*sp);
+  TRY(check_predict("rollout", pl, 1, kOwnedSpl, x, p, sp->p_off, sp->n_out));
+  if (!(flags & OMGX_PTR_DEVICE) || !(flags & OMGX_BOUNDS_DEVICE)) return bad("rollout: device pointers only (OMGX_PTR_DEVICE | OMGX_BOUNDS_DEVICE)");
+  if (sp->n_steps <= 0 || !sp->tau || !sp->t_rel || !sp->crossed || sp->n_obst < 0 || sp->n_obst > 8 || (sp->n_obst > 0 && !sp->obst) || sp->n_ent < 0 ||
+      (sp->n_ent > 0 && (!sp->shift_entries || !sp->shift_T || !sp->lam_perm)))
+    return bad("rollout: bad specification (n_steps, tau / t_rel / crossed, at most 8 obstacles, shift tables with their multiplier map)");
+  if (!b) return bad("null handle");
   const omgx::Dims& d = b->dims;
-  if (!b->inst.rollout || b->n_range > 0 || !b->d_next) {
-    g_err = "rollout: not available for this template class (spill modes, general instance, two-sided rows): step with omgx_batch_solve";
-    return OMGX_E_INVALID;
-  }
-  if (b->plant_on && (!b->inst.rollout_plant || !b->d_plant)) {
-    g_err = "rollout: a plant is set (omgx_batch_set_plant) but this template class has no plant instance of the rollout kernel: step with "
-            "omgx_batch_plant_predict / omgx_batch_solve / omgx_batch_plant_simulate";
-    return OMGX_E_INVALID;
-  }
-  if (b->plant_on && (sp->coeff_off != b->plant_host.pl.coeff_off || sp->n_spl != b->plant_host.pl.n_spl || sp->degree != b->plant_host.pl.degree ||
-                      sp->n_knots != b->plant_host.pl.n_knots || sp->p_t != b->plant_host.pl.p_t)) {
-    g_err = "rollout: the plan of the specification (coeff_off, n_spl, degree, n_knots, p_t) is not the one the plant was set with";
-    return OMGX_E_INVALID;
-  }
-  if (sp->n_steps <= 0 || !sp->tau || !sp->t_rel || !sp->crossed || !sp->knots || !sp->p_off || sp->n_knots > 40 || sp->degree > 5 ||
-      sp->degree < 1 || sp->n_spl <= 0 || sp->n_spl > 64 || sp->n_out < 1 || sp->n_out > 4 || sp->n_out > sp->degree + 1 || sp->n_obst < 0 ||
-      sp->n_obst > 8 || (sp->n_obst > 0 && !sp->obst) || sp->n_ent < 0 || (sp->n_ent > 0 && (!sp->shift_entries || !sp->shift_T || !sp->lam_perm))) {
-    g_err = "rollout: bad specification"; return OMGX_E_INVALID;
-  }
-  const int L = sp->n_knots - sp->degree - 1;
-  if (sp->coeff_off < 0 || sp->coeff_off + sp->n_spl * L > d.n_var || sp->p_t >= d.n_par) { g_err = "rollout: offsets outside x / p"; return OMGX_E_INVALID; }
-  HIPCHK(hipSetDevice(b->device));
+  if (!b->inst.rollout || b->n_range > 0 || !b->d_next)
+    return bad("rollout: not available for this template class (spill modes, general instance, two-sided rows): step with omgx_batch_solve");
+  if (b->plant_on && (!b->inst.rollout_plant || !b->d_plant))
+    return bad("rollout: a plant is set (omgx_batch_set_plant) but this template class has no plant instance of the rollout kernel: step with "
+               "omgx_batch_plant_predict / omgx_batch_solve / omgx_batch_plant_simulate");
+  if (b->plant_on && (!same_plan(*sp, b->plant_host.pl) || sp->p_t != b->plant_host.pl.p_t))
+    return bad("rollout: the plan of the specification (coeff_off, n_spl, degree, n_knots, p_t) is not the one the plant was set with");
   RolloutArgs a;
   memset(&a, 0, sizeof a);
-  fill_knots(a.kn, sp->knots, sp->n_knots);
-  a.coeff_off = sp->coeff_off; a.n_spl = sp->n_spl; a.degree = sp->degree; a.n_knots = sp->n_knots; a.n_out = sp->n_out; a.p_t = sp->p_t;
-  for (int o = 0; o < 4; ++o) {
-    a.p_off[o] = o < sp->n_out ? sp->p_off[o] : -1;
-    if (a.p_off[o] >= 0 && a.p_off[o] + sp->n_spl > d.n_par) { g_err = "rollout: offsets outside p"; return OMGX_E_INVALID; }
-  }
-  a.inv_T = sp->inv_T; a.dt = sp->dt; a.n_obst = sp->n_obst;
+  TRY(check_predict_in_xp(b, "rollout", pl, sp->n_out, sp->p_off, sp->p_t, a.p_off));
+  HIPCHK(hipSetDevice(b->device));
+  put_plan(a, pl);
+  a.n_out = sp->n_out; a.p_t = sp->p_t; a.dt = sp->dt; a.n_obst = sp->n_obst;
   for (int q = 0; q < sp->n_obst; ++q) {
     for (int k = 0; k < 4; ++k) a.obst[q][k] = sp->obst[4 * q + k];
     const int nd = a.obst[q][3];
-    if (nd <= 0 || nd > 64 || a.obst[q][0] < 0 || a.obst[q][1] < 0 || a.obst[q][2] < 0 || a.obst[q][0] + nd > d.n_par || a.obst[q][1] + nd > d.n_par ||
-        a.obst[q][2] + nd > d.n_par) { g_err = "rollout: obstacle entries outside p"; return OMGX_E_INVALID; }
+    if (nd <= 0 || nd > 64 || !in_p(b, a.obst[q][0], nd) || !in_p(b, a.obst[q][1], nd) || !in_p(b, a.obst[q][2], nd)) return bad("rollout: obstacle entries outside p");
   }
   // knot-crossing tables: the shift set (cached on the device by content) and the multiplier map
   a.n_ent = sp->n_ent;
@@ -1442,13 +1437,12 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   if (any_cross && sp->n_ent <= 0) { g_err = "rollout: a step crosses a knot but no shift tables were given"; return OMGX_E_INVALID; }
   if (sp->n_ent > 0) {
     int max_elems = 0;
-    const int rc = stage_shift_tables(b, sp->shift_entries, sp->n_ent, sp->shift_T, sp->n_tmat, d.n_var, &max_elems);
-    if (rc != OMGX_OK) return rc;
+    TRY(stage_shift_tables(b, sp->shift_entries, sp->n_ent, sp->shift_T, sp->n_tmat, d.n_var, &max_elems));
     if (max_elems > b->kkt_doubles || d.n_con > b->kkt_doubles) { g_err = "rollout: shift scratch exceeds the KKT store"; return OMGX_E_INVALID; }
     a.sh_ent = b->d_shift_ent; a.sh_T = b->d_shift_T;
     for (int i = 0; i < d.n_con; ++i) if (sp->lam_perm[i] >= d.n_con) { g_err = "rollout: multiplier map out of range"; return OMGX_E_INVALID; }
     if (b->ro_perm_host.size() != (size_t)d.n_con || memcmp(b->ro_perm_host.data(), sp->lam_perm, d.n_con * sizeof(int32_t)) != 0) {
-      if (!b->d_ro_perm) { const int rcp = dalloc(b, (size_t)d.n_con, &b->d_ro_perm); if (rcp != OMGX_OK) return rcp; }
+      if (!b->d_ro_perm) TRY(dalloc(b, (size_t)d.n_con, &b->d_ro_perm));
       b->ro_perm_host.assign(sp->lam_perm, sp->lam_perm + d.n_con);
       // (stream-ordered like the two copies below: a rollout still running on a non-blocking caller stream reads the old map)
       HIPCHK(hipMemcpyAsync(b->d_ro_perm, b->ro_perm_host.data(), sizeof(int32_t) * (size_t)d.n_con, hipMemcpyHostToDevice, b->stream));
@@ -1484,8 +1478,8 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   // kernel of a previous rollout reads these tables for its whole run, and on a non-blocking caller stream a null-stream
   // hipMemcpy would overwrite them under it (pageable sources: staged before the calls return, executed in stream order).
   HIPCHK(hipMemcpyAsync(b->ro_steps.p, steps.data(), sizeof(RolloutStep) * steps.size(), hipMemcpyHostToDevice, b->stream));
-  { const int rc_a = push_args(b, &b->d_rollout, a); if (rc_a != OMGX_OK) return rc_a; }
-  { const int rc_o = flush_order(b); if (rc_o != OMGX_OK) return rc_o; }
+  TRY(push_args(b, &b->d_rollout, a));
+  TRY(flush_order(b));
   const bool shared = flags & OMGX_BOUNDS_SHARED;
   hipEvent_t e0 = b->ext_ev0, e1 = b->ext_ev0 ? b->ext_ev1 : nullptr;
   b->ext_ev0 = b->ext_ev1 = nullptr;
@@ -1502,15 +1496,14 @@ int omgx_batch_predict_ex(omgx_batch* b, const double* x, double* p, int32_t coe
                           const double* knots, int32_t n_knots, double tau, double inv_T, int32_t n_out,
                           const int32_t* p_off, int32_t p_t, double t_value, int32_t mode, const double* state_in,
                           int32_t n_sub, double dtau) {
-  if (!b || !x || !p || !knots || !p_off || n_knots > 40 || degree > 5 || degree < 1 || n_spl <= 0 || n_out < 1 || n_out > 4 ||
-      n_out > degree + 1 || (mode != OMGX_PREDICT_IDEAL && mode != OMGX_PREDICT_RK4) ||
-      (mode == OMGX_PREDICT_RK4 && (!state_in || n_sub < 1 || !(dtau > 0.0) || n_out < 2))) {
-    g_err = "bad argument"; return OMGX_E_INVALID;
-  }
-  const omgx::Dims& d = b->dims;
+  const Plan pl{coeff_off, n_spl, degree, n_knots, inv_T, knots};
+  TRY(check_predict("predict", pl, 1, kAnySpl, x, p, p_off, n_out));
+  if (mode != OMGX_PREDICT_IDEAL && mode != OMGX_PREDICT_RK4) return bad("predict: mode = %d is neither OMGX_PREDICT_IDEAL nor OMGX_PREDICT_RK4", mode);
+  if (mode == OMGX_PREDICT_RK4 && (!state_in || n_sub < 1 || !(dtau > 0.0) || n_out < 2))
+    return bad("predict: OMGX_PREDICT_RK4 needs state_in, n_sub >= 1, dtau > 0 and n_out >= 2");
   PredictArgs a;
-  const int rc = fill_predict(b, a, coeff_off, n_spl, degree, knots, n_knots, tau, inv_T, n_out, p_off, p_t, t_value, mode, state_in, n_sub, dtau);
-  if (rc != OMGX_OK) return rc;
+  TRY(fill_predict(b, "predict", a, pl, tau, n_out, p_off, p_t, t_value, mode, state_in, n_sub, dtau));
+  const omgx::Dims& d = b->dims;
   HIPCHK(hipSetDevice(b->device));
   const int n = b->n_agents * n_spl;
   const int32_t* oi = b->pend_iters; int32_t* oo = b->pend_order;
@@ -1560,13 +1553,13 @@ int omgx_batch_set_center(omgx_batch* b, const omgx_admm_layout* lay, double* x_
     if (inv[r] >= 0) { g_err = "a row published twice cannot ride on the solve (use omgx_admm_center_ex)"; return OMGX_E_INVALID; }
     inv[r] = i;
   }
-  if (n_pub > 0 && !b->d_pub_inv) { const int rcp = dalloc(b, (size_t)b->n_agents, &b->d_pub_inv); if (rcp != OMGX_OK) return rcp; }
+  if (n_pub > 0 && !b->d_pub_inv) TRY(dalloc(b, (size_t)b->n_agents, &b->d_pub_inv));
   CenterArgs ca;
   ca.x_spl = lay->x_spl; ca.p_rel = lay->p_rel; ca.n_dim = lay->n_dim; ca.L = lay->L;
   ca.x_i = x_i; ca.pub_inv = n_pub > 0 ? b->d_pub_inv : nullptr; ca.x_send = x_send;
   // (pageable host memory: the copies are staged before the calls return)
   if (n_pub > 0) HIPCHK(hipMemcpyAsync(b->d_pub_inv, inv.data(), sizeof(int32_t) * inv.size(), hipMemcpyHostToDevice, b->stream));
-  { const int rcc = push_args(b, &b->d_center, ca); if (rcc != OMGX_OK) return rcc; }
+  TRY(push_args(b, &b->d_center, ca));
   HIPCHK(hipStreamSynchronize(b->stream));
   b->center_on = true;
   return OMGX_OK;
@@ -1599,7 +1592,7 @@ int omgx_admm_update_ex(omgx_batch* b, const omgx_admm_layout* lay, const double
   if (na > 256) { g_err = "stacked consensus vector longer than 256"; return OMGX_E_TOOLARGE; }
   HIPCHK(hipSetDevice(b->device));
   if (sums && !b->d_admm_done) {
-    int rc = dalloc(b, (size_t)1, &b->d_admm_done); if (rc != OMGX_OK) return rc;
+    TRY(dalloc(b, (size_t)1, &b->d_admm_done));
     HIPCHK(hipMemset(b->d_admm_done, 0, sizeof(int)));
   }
   const size_t lds_doubles = (size_t)std::max(6 * na + 16, sums ? 3 * 256 : 0);
@@ -1635,8 +1628,7 @@ int omgx_shift_rows(omgx_batch* b, double* data, int32_t stride, int32_t n_rows,
   if (!b || (!data && n_rows > 0) || !entries || !Tmats || n_ent <= 0 || n_rows < 0 || n_tmat <= 0 || stride <= 0) { g_err = "bad argument"; return OMGX_E_INVALID; }
   HIPCHK(hipSetDevice(b->device));
   int max_elems = 0;
-  int rc = stage_shift_tables(b, entries, n_ent, Tmats, n_tmat, stride, &max_elems);
-  if (rc != OMGX_OK) return rc;
+  TRY(stage_shift_tables(b, entries, n_ent, Tmats, n_tmat, stride, &max_elems));
   if (n_rows == 0) return OMGX_OK;            // (tables uploaded ahead of the loop that will use them)
   hipLaunchKernelGGL(shift_kernel, dim3(n_rows), dim3(64), max_elems * sizeof(double), b->stream, data, stride,
                      mask, b->d_shift_ent, n_ent, b->d_shift_T);

@@ -587,7 +587,7 @@ sample_kernel(const double* __restrict__ x, int x_stride, int coeff_off, int n_s
 // holds there, by the statements of the reference's `Vehicle::integrate` (export/vehicles/Vehicle.cpp:82-110)
 // for the integrator models (`ode` = input: Holonomic, Holonomic3D).
 struct PredictArgs {
-  KnotArg kn;
+  KnotArg knots;
   int coeff_off, n_spl, degree, n_knots, n_out, p_off[4], p_t, mode, n_sub;
   double tau, inv_T, t_value, dtau;
   const double* state_in;
@@ -672,11 +672,11 @@ predict_kernel(const double* __restrict__ x, int n_var, double* __restrict__ p, 
   const int L = a.n_knots - a.degree - 1;
   const double* c = x + (size_t)b * n_var + a.coeff_off + k * L;
   double* pb = p + (size_t)b * n_par;
-  const int j = span_of(a.kn.k, a.degree, a.n_knots, a.tau);
+  const int j = span_of(a.knots.k, a.degree, a.n_knots, a.tau);
   double sc = 1.0;
   for (int o = 0; o < a.n_out; ++o) {
     if (a.p_off[o] >= 0 && !(o == 0 && a.mode == OMGX_PREDICT_RK4))
-      pb[a.p_off[o] + k] = spline_der_at(c, a.kn.k, a.degree, j, a.tau, o) * sc;
+      pb[a.p_off[o] + k] = spline_der_at(c, a.knots.k, a.degree, j, a.tau, o) * sc;
     sc *= a.inv_T;
   }
   if (a.mode == OMGX_PREDICT_RK4 && a.p_off[0] >= 0) {
@@ -684,10 +684,10 @@ predict_kernel(const double* __restrict__ x, int n_var, double* __restrict__ p, 
     const double h = a.dtau / a.inv_T;
     double st = a.state_in[(size_t)b * a.n_spl + k];
     double u0 = a.tau - a.n_sub * a.dtau;
-    double ui = spline_der_at(c, a.kn.k, a.degree, span_of(a.kn.k, a.degree, a.n_knots, u0), u0, 1) * a.inv_T;
+    double ui = spline_der_at(c, a.knots.k, a.degree, span_of(a.knots.k, a.degree, a.n_knots, u0), u0, 1) * a.inv_T;
     for (int i = 0; i < a.n_sub; ++i) {
       const double u1 = a.tau - (a.n_sub - 1 - i) * a.dtau;
-      const double un = spline_der_at(c, a.kn.k, a.degree, span_of(a.kn.k, a.degree, a.n_knots, u1), u1, 1) * a.inv_T;
+      const double un = spline_der_at(c, a.knots.k, a.degree, span_of(a.knots.k, a.degree, a.n_knots, u1), u1, 1) * a.inv_T;
       st += (h / 6.0) * (ui + 2.0 * ui + 2.0 * ui + un);
       ui = un;
     }
@@ -704,10 +704,10 @@ predict_kernel(const double* __restrict__ x, int n_var, double* __restrict__ p, 
 // `vehicle.py:412-423`), the position of the integrated state into spl0, the plan's own derivatives at tau into
 // dspl0 / ddspl0 (`quadrotor.py:110-114`: only state[:2] of the prediction enters the parameters).
 __device__ __forceinline__ void quad_inputs(const double* cx, const double* cy, const PredictArgs& a, double u, double g, double* u1, double* u2) {
-  const int j = span_of(a.kn.k, a.degree, a.n_knots, u);
+  const int j = span_of(a.knots.k, a.degree, a.n_knots, u);
   const double s2 = a.inv_T * a.inv_T, s3 = s2 * a.inv_T;
-  const double ddx = spline_der_at(cx, a.kn.k, a.degree, j, u, 2) * s2, ddy = spline_der_at(cy, a.kn.k, a.degree, j, u, 2) * s2;
-  const double dddx = spline_der_at(cx, a.kn.k, a.degree, j, u, 3) * s3, dddy = spline_der_at(cy, a.kn.k, a.degree, j, u, 3) * s3;
+  const double ddx = spline_der_at(cx, a.knots.k, a.degree, j, u, 2) * s2, ddy = spline_der_at(cy, a.knots.k, a.degree, j, u, 2) * s2;
+  const double dddx = spline_der_at(cx, a.knots.k, a.degree, j, u, 3) * s3, dddy = spline_der_at(cy, a.knots.k, a.degree, j, u, 3) * s3;
   const double n2 = (ddy + g) * (ddy + g) + ddx * ddx;
   *u1 = sqrt(n2);
   *u2 = (dddx * (ddy + g) - ddx * dddy) / n2;
@@ -746,13 +746,13 @@ predict_quadrotor_kernel(const double* __restrict__ x, int n_var, double* __rest
     u1a = u1b; u2a = u2b;
   }
   if (state_out) for (int q = 0; q < 5; ++q) state_out[(size_t)b * 5 + q] = s[q];
-  const int j = span_of(a.kn.k, a.degree, a.n_knots, a.tau);
+  const int j = span_of(a.knots.k, a.degree, a.n_knots, a.tau);
   if (a.p_off[0] >= 0) { pb[a.p_off[0]] = s[0]; pb[a.p_off[0] + 1] = s[1]; }
   double sc = a.inv_T;
   for (int o = 1; o < a.n_out; ++o) {
     if (a.p_off[o] >= 0) {
-      pb[a.p_off[o]] = spline_der_at(cx, a.kn.k, a.degree, j, a.tau, o) * sc;
-      pb[a.p_off[o] + 1] = spline_der_at(cy, a.kn.k, a.degree, j, a.tau, o) * sc;
+      pb[a.p_off[o]] = spline_der_at(cx, a.knots.k, a.degree, j, a.tau, o) * sc;
+      pb[a.p_off[o] + 1] = spline_der_at(cy, a.knots.k, a.degree, j, a.tau, o) * sc;
     }
     sc *= a.inv_T;
   }
@@ -985,7 +985,7 @@ plant_predict_kernel(const double* __restrict__ x, int n_var, double* __restrict
 // ---------------------------------------------------------------------------
 struct RolloutStep { double tau, t_rel; int32_t crossed, pad; };
 struct RolloutArgs {
-  KnotArg kn;
+  KnotArg knots;
   int coeff_off, n_spl, degree, n_knots, n_out, p_off[4], p_t;
   double inv_T, dt;
   int n_obst, obst[8][4];
@@ -1053,10 +1053,10 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
         if ((int)threadIdx.x < n_spl) {
           const int ks = threadIdx.x;
           const double* cc = xb + rop->coeff_off + ks * L;
-          const int j = span_of(rop->kn.k, degree, n_knots, st.tau);
+          const int j = span_of(rop->knots.k, degree, n_knots, st.tau);
           double sc = 1.0;
           for (int q = 0; q < n_out; ++q) {
-            if (rop->p_off[q] >= 0) pb[rop->p_off[q] + ks] = spline_der_at(cc, rop->kn.k, degree, j, st.tau, q) * sc;
+            if (rop->p_off[q] >= 0) pb[rop->p_off[q] + ks] = spline_der_at(cc, rop->knots.k, degree, j, st.tau, q) * sc;
             sc *= rop->inv_T;
           }
           if (ks == 0 && rop->p_t >= 0) pb[rop->p_t] = st.t_rel;

@@ -263,6 +263,23 @@ def _ptr(a):
     return a.data_ptr() if hasattr(a, 'data_ptr') else (a.ctypes.data if hasattr(a, 'ctypes') else int(a))
 
 
+def _need(name, a, shape, kind, optional=False):
+    """ValueError unless the torch tensor `a` is contiguous and has that shape and element kind.  shape: per dimension an int or (label, int)
+    = that extent, a label alone = any extent; kind: 'float64 device', 'int32 device', 'int64' or '' (any); optional: None passes."""
+    if a is None and optional:
+        return
+    dt = np.dtype(kind.split(' ')[0]) if kind else None
+    want = [w[1] if isinstance(w, tuple) else w for w in shape]
+    if a is None or a.dim() != len(want) or any(not isinstance(w, str) and int(w) != n for w, n in zip(want, a.shape)) or not a.is_contiguous() \
+            or (dt is not None and (a.element_size() != dt.itemsize or a.is_floating_point() != (dt.kind == 'f'))):
+        raise ValueError('%s must be a contiguous [%s] %s' % (name, ', '.join(str(w[0] if isinstance(w, tuple) else w) for w in shape),
+                                                              (kind + ' tensor').strip()))
+
+
+def _host_knots(knots):      # the knot vector as the library reads it; the caller keeps it alive over the call or with the spec
+    return np.ascontiguousarray(knots, dtype=np.float64)
+
+
 # Every entry of include/omgx.h the package calls: name -> (restype, argtypes).  load_library applies the table once; nothing
 # else assigns a prototype (tests/test_binding_prototypes_cpu.py holds the table against the header).
 _I, _D, _P, _H = C.c_int32, C.c_double, C.c_void_p, C.c_void_p      # (_H: the omgx_batch handle)
@@ -381,6 +398,7 @@ class BatchSolver(object):
         self.lib = load_library()
         self.template = template
         self.n_agents = int(n_agents)
+        self._B = ('n_agents', self.n_agents)                       # (first dimension of every per-agent tensor, as `_need` takes it)
         self._ct, self._keep = make_ctemplate(template)
         self._h = C.c_void_p()
         _check(self.lib, self.lib.omgx_batch_create(C.byref(self._ct), self.n_agents,
@@ -484,8 +502,7 @@ class BatchSolver(object):
         [n_alt, B, n_var] device tensor or None, attempts [B] int32 device tensor or None.  The caller keeps both
         alive until the solves are done."""
         n_alt = 0 if x0_alt is None else int(x0_alt.shape[0])
-        if n_alt and (tuple(x0_alt.shape[1:]) != (self.n_agents, self.template.n_var) or not x0_alt.is_contiguous()):
-            raise ValueError("x0_alt must be a contiguous [n_alt, %d, %d] tensor" % (self.n_agents, self.template.n_var))
+        _need('x0_alt', x0_alt, ('n_alt', self.n_agents, self.template.n_var), '', optional=True)
         _check(self.lib, self.lib.omgx_batch_set_restarts(
             self._h, x0_alt.data_ptr() if n_alt else None, n_alt,
             attempts.data_ptr() if attempts is not None else None), 'omgx_batch_set_restarts')
@@ -495,8 +512,7 @@ class BatchSolver(object):
         """Launch statistics on the device (include/omgx.h omgx_batch_set_stats): stats [n_slots, 4] int64 device
         tensor (zeroed by the caller, kept alive by it) or None; row k % n_slots of the k-th following solve gets
         {solved agents, sum of iterations, largest iteration count, agents solved}."""
-        if stats is not None and (stats.dim() != 2 or stats.shape[1] != 4 or not stats.is_contiguous() or stats.element_size() != 8):
-            raise ValueError('stats must be a contiguous [n_slots, 4] int64 tensor')
+        _need('stats', stats, ('n_slots', 4), 'int64', optional=True)
         _check(self.lib, self.lib.omgx_batch_set_stats(self._h, stats.data_ptr() if stats is not None else None,
                                                         int(stats.shape[0]) if stats is not None else 0), 'omgx_batch_set_stats')
         self._stats_keep = stats
@@ -568,9 +584,7 @@ class BatchSolver(object):
     def set_stop(self, o_state0=0, o_input0=0, o_poseT=0, n_dim=0, stop_tol=1e-3, under_way=None):
         """The reference's stop criterion inside the solve launch (include/omgx.h omgx_batch_set_stop, ABI 9): under_way [B] int32
         device tensor (kept alive by the caller too), 1 = the agent's loop is running; None switches the rule off."""
-        if under_way is not None and (under_way.dim() != 1 or under_way.shape[0] != self.n_agents or not under_way.is_contiguous()
-                                      or under_way.element_size() != 4 or under_way.is_floating_point()):
-            raise ValueError('under_way must be a contiguous [n_agents] int32 device tensor')
+        _need('under_way', under_way, (self._B,), 'int32 device', optional=True)
         _check(self.lib, self.lib.omgx_batch_set_stop(self._h, int(o_state0), int(o_input0), int(o_poseT), int(n_dim), float(stop_tol),
                                                        under_way.data_ptr() if under_way is not None else None), 'omgx_batch_set_stop')
         self._under_way_keep = under_way
@@ -583,7 +597,7 @@ class BatchSolver(object):
 
     def predict(self, x, p, coeff_off, n_spl, degree, knots, tau, inv_T, p_state0, p_input0, p_t, t_value):
         """Ideal prediction on device-resident x / p (torch tensors or raw device pointers)."""
-        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        knots = _host_knots(knots)
         _check(self.lib, self.lib.omgx_batch_predict(
             self._h, _ptr(x), _ptr(p), int(coeff_off), int(n_spl), int(degree), knots.ctypes.data, len(knots),
             float(tau), float(inv_T), int(p_state0), int(p_input0), int(p_t), float(t_value)),
@@ -594,7 +608,7 @@ class BatchSolver(object):
         """p[p_off[o] + k] <- o-th time derivative of spline k at tau (o < len(p_off), -1 skips); mode
         PREDICT_RK4: p[p_off[0] + k] <- state_in integrated over the n_sub sample intervals that end at tau
         (include/omgx.h omgx_batch_predict_ex).  Device-resident tensors / pointers."""
-        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        knots = _host_knots(knots)
         off = np.ascontiguousarray(p_off, dtype=np.int32)
         _check(self.lib, self.lib.omgx_batch_predict_ex(
             self._h, _ptr(x), _ptr(p), int(coeff_off), int(n_spl), int(degree), knots.ctypes.data, len(knots),
@@ -608,7 +622,7 @@ class BatchSolver(object):
         tensors p, x, lam_g, status, iters updated in place; tau / t_rel / crossed: per-step host arrays; the rest as
         `predict_ex` / `shift`; obstacles: [(p_x, p_v, p_a, n_dim)] of the ones that move; lam_perm: multiplier map of a crossing."""
         keep = dict(tau=np.ascontiguousarray(tau, dtype=np.float64), t_rel=np.ascontiguousarray(t_rel, dtype=np.float64),
-                    crossed=np.ascontiguousarray(crossed, dtype=np.uint8), knots=np.ascontiguousarray(knots, dtype=np.float64),
+                    crossed=np.ascontiguousarray(crossed, dtype=np.uint8), knots=_host_knots(knots),
                     p_off=np.ascontiguousarray(p_off, dtype=np.int32),
                     obst=np.ascontiguousarray(np.array(list(obstacles), dtype=np.int32).reshape(-1, 4)))
         sp = CRolloutSpec()
@@ -634,7 +648,7 @@ class BatchSolver(object):
     def predict_quadrotor(self, x, p, coeff_off, degree, knots, tau, inv_T, p_off, p_t, t_value, state_in, state_out, n_sub, dtau, g=9.81):
         """Non-ideal prediction of the Quadrotor model: state_in [B, 5] integrated over the n_sub sample intervals that end at tau
         with the inputs the plan holds there (include/omgx.h omgx_batch_predict_quadrotor).  Device tensors / pointers."""
-        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        knots = _host_knots(knots)
         off = np.ascontiguousarray(p_off, dtype=np.int32)
         _check(self.lib, self.lib.omgx_batch_predict_quadrotor(
             self._h, _ptr(x), _ptr(p), int(coeff_off), int(degree), knots.ctypes.data, len(knots), float(tau), float(inv_T), len(off),
@@ -642,7 +656,7 @@ class BatchSolver(object):
             'omgx_batch_predict_quadrotor')
 
     def _store_spec(self, out, v_tot, t0, coeff_off, n_spl, degree, knots, n_der, n_samp, dt, inv_T):
-        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        knots = _host_knots(knots)
         sp = CStoreSpec(out.data_ptr(), v_tot.data_ptr() if v_tot is not None else None, t0.data_ptr(),
                         knots.ctypes.data, int(coeff_off), int(n_spl), int(degree), len(knots), int(n_der),
                         int(n_samp), float(dt), float(inv_T))
@@ -667,15 +681,10 @@ class BatchSolver(object):
 
     def _signals_spec(self, log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T):
         """omgx_signals_spec from device tensors: log [B, n_der, n_spl, cap] fp64, count / overflow [B] int32 (overflow may be None)."""
-        if log.dim() != 4 or log.shape[0] != self.n_agents or log.shape[2] != int(n_spl) or not log.is_contiguous() or log.element_size() != 8 \
-                or not log.is_floating_point():
-            raise ValueError('log must be a contiguous [n_agents, n_der, n_spl, cap] float64 device tensor')
-        for nm, a in (('count', count), ('overflow', overflow)):
-            if a is None and nm == 'overflow':
-                continue
-            if a is None or a.dim() != 1 or a.shape[0] != self.n_agents or not a.is_contiguous() or a.element_size() != 4 or a.is_floating_point():
-                raise ValueError('%s must be a contiguous [n_agents] int32 device tensor' % nm)
-        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        _need('log', log, (self._B, 'n_der', ('n_spl', n_spl), 'cap'), 'float64 device')
+        _need('count', count, (self._B,), 'int32 device')
+        _need('overflow', overflow, (self._B,), 'int32 device', optional=True)
+        knots = _host_knots(knots)
         sp = CSignalsSpec(log.data_ptr(), count.data_ptr(), overflow.data_ptr() if overflow is not None else None, knots.ctypes.data,
                           int(coeff_off), int(n_spl), int(degree), len(knots), int(log.shape[1]), int(n_samp), int(log.shape[3]), int(p_t),
                           float(sample_time), float(inv_T))
@@ -697,12 +706,9 @@ class BatchSolver(object):
     def signals_append(self, x, p, log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T, under_way=None):
         """The same append for the plans in x at the times p[:, p_t] (device tensors), one launch (omgx_batch_signals_append);
         under_way: optional [n_agents] int32 device tensor, agents with 0 are skipped."""
-        for nm, a, w in (('x', x, self.template.n_var), ('p', p, self.template.n_par)):
-            if a.dim() != 2 or a.shape[0] != self.n_agents or a.shape[1] != w or not a.is_contiguous() or a.element_size() != 8:
-                raise ValueError('%s must be a contiguous [n_agents, %d] float64 device tensor' % (nm, w))
-        if under_way is not None and (under_way.dim() != 1 or under_way.shape[0] != self.n_agents or not under_way.is_contiguous()
-                                      or under_way.element_size() != 4 or under_way.is_floating_point()):
-            raise ValueError('under_way must be a contiguous [n_agents] int32 device tensor')
+        _need('x', x, (self._B, self.template.n_var), 'float64 device')
+        _need('p', p, (self._B, self.template.n_par), 'float64 device')
+        _need('under_way', under_way, (self._B,), 'int32 device', optional=True)
         sp = self._signals_spec(log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T)
         _check(self.lib, self.lib.omgx_batch_signals_append(self._h, x.data_ptr(), p.data_ptr(),
                                                              under_way.data_ptr() if under_way is not None else None, C.byref(sp)),
@@ -711,9 +717,8 @@ class BatchSolver(object):
     def signals_reduce(self, log, count, target, summary, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T):
         """summary [B, 8] <- {columns, motion time, path length, max |input|, max |dinput|, |state_last - target|, |input_last|, 0}
         from the log (omgx_batch_signals_reduce); target [B, n_spl].  Device tensors."""
-        for nm, a, w in (('target', target, int(n_spl)), ('summary', summary, 8)):
-            if a.dim() != 2 or a.shape[0] != self.n_agents or a.shape[1] != w or not a.is_contiguous() or a.element_size() != 8:
-                raise ValueError('%s must be a contiguous [n_agents, %d] float64 device tensor' % (nm, w))
+        _need('target', target, (self._B, int(n_spl)), 'float64 device')
+        _need('summary', summary, (self._B, 8), 'float64 device')
         sp = self._signals_spec(log, count, None, coeff_off, n_spl, degree, knots, n_samp, p_t, sample_time, inv_T)
         _check(self.lib, self.lib.omgx_batch_signals_reduce(self._h, C.byref(sp), target.data_ptr(), summary.data_ptr()),
                'omgx_batch_signals_reduce')
@@ -723,17 +728,11 @@ class BatchSolver(object):
         """omgx_plant_spec from device tensors: state / state_prev / input_last [B, n_spl] fp64, n_upd / overflow / under_way [B] int32
         (overflow, under_way may be None), dist [B, n_spl, max_updates, n_samp + 1] fp64 or None."""
         for nm, a in (('state', state), ('state_prev', state_prev), ('input_last', input_last)):
-            if a.dim() != 2 or tuple(a.shape) != (self.n_agents, int(n_spl)) or not a.is_contiguous() or a.element_size() != 8 or not a.is_floating_point():
-                raise ValueError('%s must be a contiguous [n_agents, n_spl] float64 device tensor' % nm)
+            _need(nm, a, (self._B, ('n_spl', n_spl)), 'float64 device')
         for nm, a in (('n_upd', n_upd), ('overflow', overflow), ('under_way', under_way)):
-            if a is None and nm != 'n_upd':
-                continue
-            if a is None or a.dim() != 1 or a.shape[0] != self.n_agents or not a.is_contiguous() or a.element_size() != 4 or a.is_floating_point():
-                raise ValueError('%s must be a contiguous [n_agents] int32 device tensor' % nm)
-        if dist is not None and (tuple(dist.shape) != (self.n_agents, int(n_spl), int(max_updates), int(n_samp) + 1) or not dist.is_contiguous()
-                                 or dist.element_size() != 8 or not dist.is_floating_point()):
-            raise ValueError('dist must be a contiguous [n_agents, n_spl, max_updates, n_samp + 1] float64 device tensor')
-        knots = np.ascontiguousarray(knots, dtype=np.float64)
+            _need(nm, a, (self._B,), 'int32 device', optional=nm != 'n_upd')
+        _need('dist', dist, (self._B, ('n_spl', n_spl), ('max_updates', max_updates), ('n_samp + 1', int(n_samp) + 1)), 'float64 device', optional=True)
+        knots = _host_knots(knots)
         sp = CPlantSpec(state.data_ptr(), state_prev.data_ptr(), input_last.data_ptr(), _ptr(dist), n_upd.data_ptr(), _ptr(overflow),
                         _ptr(under_way), knots.ctypes.data, int(coeff_off), int(n_spl), int(degree), len(knots), int(n_samp),
                         int(max_updates), int(p_t), int(p_state0), int(p_input0), int(p_poseT), float(sample_time), float(inv_T),
@@ -769,7 +768,7 @@ class BatchSolver(object):
 
     def sample(self, x, coeff_off, n_spl, degree, knots, n_der, t0, dt, n_samp,
                out=None, as_f32=False, device=False):
-        knots = np.ascontiguousarray(knots, dtype=np.float64)
+        knots = _host_knots(knots)
         if out is None:
             out = np.empty((self.n_agents, n_der, n_spl, n_samp),
                            dtype=np.float32 if as_f32 else np.float64)

@@ -397,6 +397,8 @@ class DeviceP2P(BatchP2P):
         f64 = dict(dtype=torch.float64, device=self.dev)
         self.solver = BatchSolver(self.tpl, self.B, device=self.dev.index or 0, options=self.opts)
         self.solver.set_stream(torch.cuda.current_stream().cuda_stream)
+        # the plan as every glue entry of the library takes it (include/omgx.h, above omgx_store_spec): built once
+        self._plan = dict(coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree, knots=self.basis.knots, inv_T=1.0 / self.T)
         self.p = torch.as_tensor(np.ascontiguousarray(P['p']), **f64)
         self.x = torch.as_tensor(np.ascontiguousarray(P['x0']), **f64)
         self.x_new = torch.empty_like(self.x)
@@ -414,8 +416,7 @@ class DeviceP2P(BatchP2P):
         if self.straggler_first:
             self.solver.order_by_iters(self.iters, self._order)
         # one kernel: the initial conditions from the plan at tau and the new t, all written into p
-        self.solver.predict_ex(self.x, self.p, self.o_spl, self.n_spl, self.basis.degree, self.basis.knots, tau,
-                               1.0 / self.T, self.p_offs, self.o_t, t_rel)
+        self.solver.predict_ex(self.x, self.p, tau=tau, p_off=self.p_offs, p_t=self.o_t, t_value=t_rel, **self._plan)
 
     def _shift(self):
         if self._pl is not None and self.under_way is not None:
@@ -489,9 +490,9 @@ class DeviceP2P(BatchP2P):
         if self.straggler_first:
             self.solver.order_by_iters(self.iters, self._order)
         self.solver.rollout(self.p, self.x, self.lb, self.ub, self.lam, self.status, self.iters, tau, t_rel, crossed,
-                            self.o_spl, self.n_spl, self.basis.degree, self.basis.knots, 1.0 / self.T, self.p_offs, self.o_t,
-                            obstacles=self.obst, dt=self.update_time, shift_entries=self.shift_entries, shift_T=self.shift_mats,
-                            lam_perm=self.perm, cross_options=self.cross_options or None, iters_log=iters_log, status_log=status_log)
+                            p_off=self.p_offs, p_t=self.o_t, obstacles=self.obst, dt=self.update_time, shift_entries=self.shift_entries, shift_T=self.shift_mats,
+                            lam_perm=self.perm, cross_options=self.cross_options or None, iters_log=iters_log, status_log=status_log,
+                            **self._plan)
 
     def _norm(self, a):
         return a.norm(dim=1)
@@ -511,8 +512,7 @@ class DeviceP2P(BatchP2P):
 
     def _signals_args(self):
         g = self._sig
-        return dict(coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree, knots=self.basis.knots, n_samp=g['n_samp'],
-                    p_t=self.o_t, sample_time=g['sample_time'], inv_T=1.0 / self.T)
+        return dict(self._plan, n_samp=g['n_samp'], p_t=self.o_t, sample_time=g['sample_time'])
 
     def _signals_fused(self, on):
         """The append inside the solve / rollout kernel, on or off."""
@@ -536,10 +536,9 @@ class DeviceP2P(BatchP2P):
 
     def _plant_args(self):
         g = self._pl
-        return dict(state=g['state'], state_prev=g['state_prev'], input_last=g['input_last'], n_upd=g['n_upd'], overflow=g['overflow'],
-                    dist=g['dist'], under_way=self.under_way, coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree,
-                    knots=self.basis.knots, n_samp=g['n_samp'], max_updates=g['max_updates'], p_t=self.o_t, p_state0=self.o_state0,
-                    p_input0=self.o_input0, p_poseT=g['o_pose'], sample_time=g['sample_time'], inv_T=1.0 / self.T, stop_tol=self.stop_tol)
+        return dict(self._plan, state=g['state'], state_prev=g['state_prev'], input_last=g['input_last'], n_upd=g['n_upd'], overflow=g['overflow'],
+                    dist=g['dist'], under_way=self.under_way, n_samp=g['n_samp'], max_updates=g['max_updates'], p_t=self.o_t,
+                    p_state0=self.o_state0, p_input0=self.o_input0, p_poseT=g['o_pose'], sample_time=g['sample_time'], stop_tol=self.stop_tol)
 
     def _plant_log_args(self):
         g = self._sig
