@@ -12,6 +12,7 @@
 #include "omgx_core.h"
 #include "omgx_plan.h"
 #include "omgx_kernels.h"
+#include "omgx_table_cache.h"
 
 namespace {
 
@@ -126,10 +127,12 @@ struct omgx_batch {
   CenterArgs* d_center = nullptr;   // omgx_batch_set_center: device copy of the arguments (nullptr: off); the slot map behind it
   int32_t* d_pub_inv = nullptr;
   bool center_on = false;
-  // Every device buffer that lives as long as the handle comes from dalloc / upload and is freed by the loop over `allocs` in
+  // Every device buffer that lives as long as the handle comes from dalloc and is freed by the loop over `allocs` in
   // omgx_batch_destroy, the lazily allocated ones (d_store, d_stop ...) included; what is resized or evicted is a DevBuf.
+  // The plan's tables (`dev`) are not the handle's: it holds a reference to their image in the table cache (omgx_table_cache.h),
+  // shared with every handle of the same template on this device, and only reads through it.
   std::vector<void*> allocs;
-  char* arena = nullptr; size_t arena_cap = 0, arena_used = 0;      // bump allocator of the plan's tables (arena_alloc)
+  const omgx::TableCache::Entry* tables = nullptr;      // taken by build_batch, released by omgx_batch_destroy
   hipStream_t own_stream = nullptr, stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ext_ev0 = nullptr, ext_ev1 = nullptr;   // caller's events for the next solve launch (one shot)
@@ -159,29 +162,45 @@ struct omgx_batch {
 
 namespace {
 
-// The ~60 tables of a plan live in one arena (chunks of 4 MiB, 256-byte aligned pieces) instead of sixty separately
-// placed hipMalloc'ed buffers: every thread of every solve walks them.
-int arena_alloc(omgx_batch* b, size_t bytes, void** out) {
-  const size_t need = (bytes + 255) & ~(size_t)255;
-  if (!b->arena || b->arena_used + need > b->arena_cap) {
-    const size_t cap = need > ((size_t)4 << 20) ? need : ((size_t)4 << 20);
-    void* ptr = nullptr;
-    HIPCHK(hipMalloc(&ptr, cap));
-    b->allocs.push_back(ptr);
-    b->arena = (char*)ptr; b->arena_cap = cap; b->arena_used = 0;
-  }
-  *out = b->arena + b->arena_used;
-  b->arena_used += need;
+// The ~60 tables of a plan live in one image (256-byte aligned pieces, one exact-size allocation) instead of sixty separately
+// placed hipMalloc'ed buffers: every thread of every solve walks them.  build_batch lays the image out on the host (upload: a piece
+// and the table pointer that will point at it), then takes its device copy from the table cache -- one per template and device,
+// whoever asks first uploads it (bind_tables).  Nothing writes into it afterwards: the tables are const to every kernel.
+struct TableImage {
+  std::vector<char> bytes;
+  std::vector<std::pair<const void**, size_t>> slots;      // (table pointer of the handle, offset of its piece)
+};
+
+template <typename T>
+int upload(TableImage& img, const T* src, size_t n, const T** dst) {
+  const size_t bytes = (n > 0 ? n : 1) * sizeof(T), off = img.bytes.size();
+  img.bytes.resize(off + ((bytes + 255) & ~(size_t)255), 0);
+  if (n > 0) memcpy(img.bytes.data() + off, src, n * sizeof(T));
+  img.slots.emplace_back((const void**)dst, off);
   return OMGX_OK;
 }
 
-template <typename T>
-int upload(omgx_batch* b, const T* src, size_t n, const T** dst) {
-  void* ptr = nullptr;
-  const size_t bytes = (n > 0 ? n : 1) * sizeof(T);
-  TRY(arena_alloc(b, bytes, &ptr));
-  if (n > 0) HIPCHK(hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice));
-  *dst = (const T*)ptr;
+// the process-wide cache of table images (never destroyed: handles may outlive static destruction order)
+omgx::TableCache& table_cache() {
+  static const omgx::TableCacheOps ops = {
+      [](void*, int, size_t bytes, void** out) -> int { return (int)hipMalloc(out, bytes); },
+      [](void*, int, void* dst, const void* src, size_t bytes) -> int { return (int)hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); },
+      [](void*, int, void* ptr) { (void)hipFree(ptr); },      // (hipFree waits for queued launches that still read it)
+      nullptr};
+  static omgx::TableCache* cache = new omgx::TableCache(ops);
+  return *cache;
+}
+
+int bind_tables(omgx_batch* b, TableImage& img) {
+  int err = 0, step = 0;
+  b->tables = table_cache().take(b->device, img.bytes.data(), img.bytes.size(), &err, &step);
+  if (!b->tables) {
+    // (the texts are kept verbatim from the HIPCHK lines of the per-table upload this replaces: callers match on them)
+    g_err = std::string(step == omgx::TableCache::STEP_COPY ? "hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice): " : "hipMalloc(&ptr, cap): ") +
+            hipGetErrorString((hipError_t)err);
+    return OMGX_E_HIP;
+  }
+  for (auto& s : img.slots) *s.first = (const char*)b->tables->dev + s.second;
   return OMGX_OK;
 }
 
@@ -246,7 +265,7 @@ template <class A, class B> bool same_plan(const A& a, const B& b) {
 }
 
 #define UP(field, count)                                          \
-  TRY(upload(b, H.field, (size_t)(count), &b->dev.field))
+  TRY(upload(img, H.field, (size_t)(count), &b->dev.field))
 
 // smallest spill mode whose LDS part fits one CU (WS_MODES: none does)
 int pick_mode(const omgx::Dims& d, int kkt_doubles, size_t* lds_doubles, size_t* hbm_doubles) {
@@ -388,6 +407,7 @@ int build_batch(omgx_batch* b, const omgx_template* t) {
   if (const char* e = getenv("OMGX_ORDER_DW")) b->order_dw = atoi(e);
   const omgx::Tables& H = plan.tables;
   const omgx::Dims& d = plan.dims;
+  TableImage img;
   {
     b->ev_jrow.assign(plan.je_row.begin(), plan.je_row.begin() + d.nnz_j);
     b->ev_jvar.resize(d.nnz_j);
@@ -402,11 +422,9 @@ int build_batch(omgx_batch* b, const omgx_template* t) {
   UP(pm_ptr, t->n_mono + 1); UP(pm_atom, t->n_matom); UP(slot_pp, d.n_slots);
   // (packed monomial records: 16-byte MonoRec or, with 5..8 atoms per monomial, 24-byte MonoRec8 behind the same pointers)
   if (d.mono_packed == 2) {
-    const omgx::MonoRec8* dev8 = nullptr;
-    TRY(upload(b, plan.pm_rec8.data(), plan.pm_rec8.size(), &dev8));
-    b->dev.pm_rec = (const omgx::MonoRec*)dev8;
-    TRY(upload(b, plan.sl_ell8.data(), plan.sl_ell8.size(), &dev8));
-    b->dev.sl_ell = (const omgx::MonoRec*)dev8;
+    // (the pointers are bound once the image is on the device: straight into the handle's table, the records' type apart)
+    TRY(upload(img, plan.pm_rec8.data(), plan.pm_rec8.size(), (const omgx::MonoRec8**)&b->dev.pm_rec));
+    TRY(upload(img, plan.sl_ell8.data(), plan.sl_ell8.size(), (const omgx::MonoRec8**)&b->dev.sl_ell));
   } else { UP(pm_rec, plan.pm_rec.size()); UP(sl_ell, plan.sl_ell.size()); }
   UP(row_ptr, d.n_con + 2); UP(t_coef, d.n_terms); UP(t_slot, d.n_terms); UP(t_var, OMGX_TERM_VARS * d.n_terms);
   UP(order, d.N); UP(leaf_off, d.n_leaf + 1); UP(leaf_bw, plan.leaf_bw.size()); UP(blk, d.N);
@@ -428,7 +446,7 @@ int build_batch(omgx_batch* b, const omgx_template* t) {
   UP(ja_ell, plan.ja_ell.size()); UP(ja_own, plan.ja_own.size()); UP(ja_glen, plan.ja_glen.size());
   UP(sl_list, plan.sl_list.size()); UP(sl_glen, plan.sl_glen.size());
   UP(lift_rec, plan.lift_rec.size()); UP(lift_lev, plan.lift_lev.size());
-  return OMGX_OK;
+  return bind_tables(b, img);
 }
 
 }  // namespace
@@ -765,7 +783,8 @@ int omgx_batch_set_stop(omgx_batch* b, int32_t o_state0, int32_t o_input0, int32
 void omgx_batch_destroy(omgx_batch* b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  for (void* p : b->allocs) (void)hipFree(p);      // (everything dalloc / upload handed out; the DevBufs go with `delete b`)
+  for (void* p : b->allocs) (void)hipFree(p);      // (everything dalloc handed out; the DevBufs go with `delete b`)
+  table_cache().release(b->tables);                // (the last handle of the template on this device frees the image)
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
   if (b->own_stream) (void)hipStreamDestroy(b->own_stream);

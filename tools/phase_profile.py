@@ -18,9 +18,12 @@ PHASES = ['jac', 'resid', 'assemble', 'factor', 'solve', 'step', 'linesearch', '
           'f_park', 'f_sweep', 'f_scale', 'a_tcol', 'a_hess', 's_p_load', 's_p_div', 's_p_bspl', 's_p_slots']
 
 
-def mpc_mode(problem, P, B, steps=20, warmup=3):
+def mpc_mode(problem, P, B, steps=20, warmup=3, rounds=False):
     """The headline protocol (bench.py): cold solve, `warmup` receding-horizon steps, then the phase counters
-    of `steps` steps summed -- cycles per solve and per iteration of the warm-started steps."""
+    of `steps` steps summed -- cycles per solve and per iteration of the warm-started steps.
+    rounds: the phase cycles split by the round of the launch an agent was solved in -- the first round are the
+    agents in the first `n_slabs` launch slots (one per resident workgroup: they start together, on tables nobody has touched
+    in this launch), the later rounds everyone behind them (handed out one by one as workgroups come free)."""
     import torch
     from omgtools.batch import BatchP2P
     mpc = BatchP2P(problem, P, ops='hip', device=torch.device('cuda', 0), options=dict(tol=1e-3, max_iter=300))
@@ -33,6 +36,8 @@ def mpc_mode(problem, P, B, steps=20, warmup=3):
     tot = np.zeros(len(PHASES))
     its, ms = 0, []
     prof = np.zeros((B, len(PHASES)), dtype=np.int64)
+    slabs = solver.workspace()['n_slabs']
+    split = {'first_round': [np.zeros(len(PHASES)), 0], 'later_rounds': [np.zeros(len(PHASES)), 0]}
     for _ in range(steps):
         mpc.step()
         torch.cuda.synchronize()
@@ -40,11 +45,22 @@ def mpc_mode(problem, P, B, steps=20, warmup=3):
         solver.lib.omgx_batch_phase_cycles(solver._h, prof.ctypes.data)
         tot += prof.sum(axis=0)
         its += int(mpc.iters.sum().item())
+        if rounds:
+            # launch slot of every agent: the order this step's solve was launched with (identity without straggler ordering)
+            slot = np.empty(B, dtype=np.int64)
+            slot[mpc._order.cpu().numpy().astype(np.int64)] = np.arange(B)
+            for key, sel in (('first_round', slot < slabs), ('later_rounds', slot >= slabs)):
+                split[key][0] += prof[sel].sum(axis=0)
+                split[key][1] += int(sel.sum())
     n_solves = B * steps
     out = {'mode': 'mpc', 'agents': B, 'steps': steps, 'kernel_ms_mean': float(np.mean(ms)), 'kernel_ms_p50': float(np.median(ms)),
            'iters_per_solve': its / n_solves,
            'cycles_per_solve': {p: float(tot[k] / n_solves) for k, p in enumerate(PHASES)},
            'cycles_per_iter': {p: float(tot[k] / max(1, its)) for k, p in enumerate(PHASES)}}
+    if rounds:
+        out['resident_workgroups'] = int(slabs)
+        out['rounds'] = {key: {'solves': n, 'cycles_per_solve': {p: float(t[k] / max(1, n)) for k, p in enumerate(PHASES)}}
+                         for key, (t, n) in split.items()}
     print(json.dumps(out, indent=1))
 
 
@@ -58,7 +74,7 @@ def main():
     be.create_nlp = saved
     tpl = problem.father.template
     if len(sys.argv) > 2 and sys.argv[2] == 'mpc':
-        return mpc_mode(problem, P, B)
+        return mpc_mode(problem, P, B, rounds=len(sys.argv) > 3 and sys.argv[3] == 'rounds')
     solver = be.BatchSolver(tpl, B, options=dict(P.get('solver_options', {}), tol=1e-3, max_iter=300))
     warm = len(sys.argv) > 2 and sys.argv[2] == 'warm'
     for _ in range(2):

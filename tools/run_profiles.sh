@@ -12,6 +12,13 @@ B1="python $R/bench.py --full --no-cpu --no-extras --no-parity"
 B="python $R/bench.py --full --streams 1 --no-cpu --no-extras --no-parity"
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/out/prof/stats -- $B1 > $R/out/prof/bench_stats.json 2> $R/out/prof/stats.err )
 ( cd /tmp && rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/out/prof/fetch -- $B --steps 5 --warmup 1 > /dev/null 2> $R/out/prof/fetch.err )
+# the L2 pass (hits, misses, read requests to the fabric) is a run of its own like every other counter set; once one launch per step,
+# once in the default three-launch form (under --pmc the launches of the sub-batches run one after the other); the plain bench line,
+# so that every solve-kernel launch of the process is a cold solve or a step of the headline batch
+L2="python $R/bench.py --gpus 1 --steps 5 --warmup 1"
+( cd /tmp && rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_REQ_sum --output-format csv -d $R/out/prof/l2 -- $L2 --streams 1 > /dev/null 2> $R/out/prof/l2.err )
+( cd /tmp && rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_REQ_sum --output-format csv -d $R/out/prof/l2_default -- $L2 > /dev/null 2> $R/out/prof/l2_default.err )
+python $R/tools/pmc_per_launch.py $R/out/prof/l2 > $R/out/${TAG}_pmc_l2.txt 2>&1; python $R/tools/pmc_per_launch.py $R/out/prof/l2_default >> $R/out/${TAG}_pmc_l2.txt 2>&1
 ( cd /tmp && rocprofv3 --pmc WRITE_SIZE --output-format csv -d $R/out/prof/write -- $B --steps 5 --warmup 1 > /dev/null 2> $R/out/prof/write.err )
 ( cd /tmp && rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 --output-format csv -d $R/out/prof/mfma -- $B --steps 5 --warmup 1 > /dev/null 2> $R/out/prof/mfma.err )
 ( cd /tmp && rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --output-format csv -d $R/out/prof/lds -- $B --steps 5 --warmup 1 > /dev/null 2> $R/out/prof/lds.err )
