@@ -450,11 +450,11 @@ int  omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, d
  * THE PLAN.  coeff_off, n_spl, degree, knots, n_knots and, where time derivatives are taken, inv_T say which coefficients of x
  * are the vehicle's splines and on which basis.  Every entry that takes them -- omgx_batch_sample, _store / _set_store,
  * _set_signals / _signals_append / _signals_reduce, _set_plant / _plant_simulate / _plant_predict, _predict / _predict_ex /
- * _predict_quadrotor, _rollout -- holds them to one rule:
+ * _predict_quadrotor, _predict_measured, _rollout -- holds them to one rule:
  *   knots is not null;
  *   min_degree <= degree <= 5, min_degree = 0 for omgx_batch_sample, 3 for omgx_batch_predict_quadrotor, 1 elsewhere;
  *   2 * degree + 2 <= n_knots <= 40 (a clamped basis with at least one span; the kernels take the knots by value);
- *   1 <= n_spl, and n_spl <= 64 where a thread owns a spline (the plant entries, omgx_batch_rollout);
+ *   1 <= n_spl, and n_spl <= 64 where a thread owns a spline (the plant entries, omgx_batch_predict_measured, omgx_batch_rollout);
  *   coeff_off >= 0;  inv_T > 0 wherever the entry carries one;
  *   coeff_off + n_spl * (n_knots - degree - 1) <= n_var.
  * A call that breaks it returns OMGX_E_INVALID before anything is launched, and omgx_last_error() names the entry and the field.
@@ -557,6 +557,45 @@ int  omgx_batch_plant_simulate(omgx_batch* b, const double* x, const double* p, 
                                const omgx_signals_spec* log_sp);
 int  omgx_batch_plant_predict(omgx_batch* b, const double* x, double* p, double tau, double t_value, const omgx_plant_spec* sp);
 int  omgx_batch_set_plant(omgx_batch* b, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp);
+
+/* (OMGX_HAS_FEEDBACK) States measured outside the loop: the reference's deployment contract `Deployer.update(current_time, states,
+ * inputs, ..., enforce_states, enforce_inputs)` (`execution/deployer.py:43-79`) -> `Vehicle.predict(state0 = ...)`
+ * (`vehicles/vehicle.py:302-337`), for the whole batch at the head of an update -- the place of omgx_batch_predict_ex /
+ * omgx_batch_plant_predict in the step, before obstacle motion and the knot-crossing shift; it reads the old plan and the old
+ * p[p_t].  Integrator classes (`ode` = input: Holonomic, Holonomic3D), one clock for the batch (no `delay`), no first-order actuator
+ * lag.  Per agent b, spline k < n_spl (p_off, n_out, p_t as omgx_batch_predict_ex: p_off[o] < 0 for o >= 1 skips that order;
+ * p_off[0] and p_t are needed):
+ *   fresh[b] == 0 (no measurement at this update) -- the ideal prediction, the statements of omgx_batch_predict_ex:
+ *     p[p_off[o] + k] <- d^o/dt^o spline_k at tau (o < n_out),  p[p_t] <- t_value.
+ *   fresh, enforce == 0 -- `Vehicle.predict` with state0 given (`vehicle.py:326-337`): the measured state is the one the vehicle
+ *     had when the plan in x was solved, at t_rel = the OLD p[p_t]; it is integrated over the update under the plan's nominal inputs
+ *     u_i = d/dt spline_k at (t_rel + i sample_time) * inv_T,  i = 0 .. n_samp:
+ *     p[p_off[0] + k] <- state[b, k] + sample_time * sum_{i < n_samp} (u_i + u_{i+1}) / 2
+ *     p[p_off[o] + k] <- d^o/dt^o spline_k at tau (1 <= o < n_out),  p[p_t] <- t_value.
+ *     The sum is taken by the statements of omgx_batch_plant_predict (index order, no fused multiply-adds): with state equal to the
+ *     plant's state_prev the two entries write the same bits.  (The u_i of an agent are evaluated side by side, one per thread,
+ *     and added up by the thread that owns the spline.)
+ *   fresh, enforce != 0 -- `enforce_states` (+ `enforce_inputs`), `vehicle.py:303-321` with `holonomic.py:107-113`:
+ *     p[p_off[0] + k] <- state[b, k];  p[p_off[1] + k] <- input[b, k], or 0.0 with input == NULL;  orders o >= 2 <- 0.0;
+ *     p[p_t] <- t_value.  input is read in this form only.
+ * One launch on the handle's stream, one workgroup per agent (device pointers x, p); it carries a pending
+ * omgx_batch_order_by_iters as omgx_batch_plant_predict does.  state, input and fresh may be device pointers or pinned host
+ * pointers (the kernel reads each value once, over the link).  n_samp = int(round(update_time / sample_time, 6)).
+ * Checks, in this order: x, p, the specification and state not null; the plan (the rule above omgx_store_spec, n_spl <= 64);
+ * n_samp >= 1, sample_time > 0, 1 <= n_out <= min(4, degree + 1), p_off[0] >= 0, and the staged knots, plan and input samples --
+ * n_knots + n_spl * (n_knots - degree - 1 + n_samp + 1) doubles -- within 64 KiB of LDS; the handle; the plan inside x, p_off / p_t
+ * inside p. */
+#define OMGX_HAS_FEEDBACK 1
+typedef struct omgx_feedback_spec {
+  const double*  state;   /* [B, n_spl] measured states; device or pinned host */
+  const double*  input;   /* [B, n_spl] or NULL; read in the enforce form only */
+  const int32_t* fresh;   /* [B] or NULL (= all): 0 -> the agent has no measurement at this update */
+  const double*  knots;   /* host; the plan: the rule above omgx_store_spec */
+  int32_t coeff_off, n_spl, degree, n_knots, n_samp, n_out, p_off[4], p_t, enforce;
+  double  sample_time, inv_T;
+} omgx_feedback_spec;
+int  omgx_batch_predict_measured(omgx_batch* b, const double* x, double* p, double tau, double t_value,
+                                 const omgx_feedback_spec* sp);
 
 /* Same shift on any device-resident row-major array (stride doubles per row, n_rows rows):
  * used for the ADMM consensus state on a knot crossing (`problems/admm.py:477-491`).

@@ -1540,6 +1540,34 @@ int omgx_batch_predict(omgx_batch* b, const double* x, double* p, int32_t coeff_
                                OMGX_PREDICT_IDEAL, nullptr, 0, 0.0);
 }
 
+int omgx_batch_predict_measured(omgx_batch* b, const double* x, double* p, double tau, double t_value, const omgx_feedback_spec* sp) {
+  if (!sp || !x || !p) return bad("predict_measured: null x / p / specification");
+  if (!sp->state) return bad("predict_measured: null state");
+  const Plan plan = plan_of(*sp);
+  TRY(check_plan("predict_measured", plan, 1, kOwnedSpl));
+  if (sp->n_samp < 1) return bad("predict_measured: n_samp = %d, at least one sample interval per update is needed", sp->n_samp);
+  if (!(sp->sample_time > 0.0)) return bad("predict_measured: sample_time = %g must be positive", sp->sample_time);
+  if (sp->n_out < 1 || sp->n_out > 4 || sp->n_out > sp->degree + 1) return bad("predict_measured: n_out = %d outside 1 .. min(4, degree + 1)", sp->n_out);
+  if (sp->p_off[0] < 0) return bad("predict_measured: p_off[0] = %d, the state has no place in p", sp->p_off[0]);
+  const size_t lds = feedback_lds_doubles(sp->n_spl, sp->degree, sp->n_knots, sp->n_samp) * sizeof(double);
+  if (lds > 64 * 1024) return bad("predict_measured: n_samp = %d, the staged plan and n_spl * (n_samp + 1) input samples exceed 64 KiB of LDS", sp->n_samp);
+  if (tau != tau || t_value != t_value) return bad("predict_measured: tau / t_value is not a number");
+  if (!b) return bad("null handle");
+  FeedbackArgs a;
+  TRY(check_predict_in_xp(b, "predict_measured", plan, sp->n_out, sp->p_off, sp->p_t, a.p_off));
+  if (sp->p_t < 0) return bad("predict_measured: p_t = %d outside p (the old t is read, the new one written)", sp->p_t);
+  put_plan(a, plan);
+  a.state = sp->state; a.input = sp->enforce ? sp->input : nullptr; a.fresh = sp->fresh;
+  a.n_samp = sp->n_samp; a.n_out = sp->n_out; a.p_t = sp->p_t; a.enforce = sp->enforce ? 1 : 0; a.sample_time = sp->sample_time;
+  HIPCHK(hipSetDevice(b->device));
+  const int32_t* oi = b->pend_iters; int32_t* oo = b->pend_order;
+  b->pend_iters = nullptr; b->pend_order = nullptr;
+  hipLaunchKernelGGL(feedback_predict_kernel, dim3(b->n_agents + (oi ? 1 : 0)), dim3(64), lds, b->stream, x, b->dims.n_var, p, b->dims.n_par, b->n_agents,
+                     a, tau, t_value, oi, oo, (const double*)(b->order_dw ? b->d_dw : nullptr));
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
 int omgx_admm_center(omgx_batch* b, const omgx_admm_layout* lay, const double* x, const double* p, double* x_i) {
   return omgx_admm_center_ex(b, lay, x, p, x_i, nullptr, 0, nullptr);
 }

@@ -814,7 +814,9 @@ __host__ __device__ inline size_t plant_stage_doubles(int n_spl, int degree, int
   return (size_t)n_knots + (size_t)n_spl * (n_knots - degree - 1);
 }
 // knots -> stage[0 .. n_knots), coefficients [n_spl][L] -> behind them; every thread of the workgroup, a barrier at the end
-__device__ __forceinline__ void plant_stage(const PlantArgs& pl, const double* coeffs, double* stage) {
+// (Args: PlantArgs, or the FeedbackArgs of omgx_batch_predict_measured -- the plan fields of either)
+template <class Args>
+__device__ __forceinline__ void plant_stage(const Args& pl, const double* coeffs, double* stage) {
   const int n_c = pl.n_spl * (pl.n_knots - pl.degree - 1);
   for (int i = threadIdx.x; i < pl.n_knots; i += blockDim.x) stage[i] = pl.knots.k[i];
   for (int i = threadIdx.x; i < n_c; i += blockDim.x) stage[pl.n_knots + i] = coeffs[i];
@@ -822,7 +824,8 @@ __device__ __forceinline__ void plant_stage(const PlantArgs& pl, const double* c
 }
 
 // nominal input of spline c (time derivative of the plan) at sample i of the update solved at t_rel; kk: the knots
-__device__ __forceinline__ double plant_input_at(const PlantArgs& pl, const double* kk, const double* c, double t_rel, int i) {
+template <class Args>
+__device__ __forceinline__ double plant_input_at(const Args& pl, const double* kk, const double* c, double t_rel, int i) {
 #pragma clang fp contract(off)
   const double u = (t_rel + i * pl.sample_time) * pl.inv_T;
   return spline_der_at(c, kk, pl.degree, span_of(kk, pl.degree, pl.n_knots, u), u, 1) * pl.inv_T;
@@ -972,6 +975,92 @@ plant_predict_kernel(const double* __restrict__ x, int n_var, double* __restrict
   if (b >= B) return;
   const PlantArgs& pl = pb->pl;
   (void)plant_predict_agent(pl, b, x + (size_t)b * n_var + pl.coeff_off, p + (size_t)b * n_par, tau, t_value, lds);
+}
+
+// ---------------------------------------------------------------------------
+// States measured outside the loop (omgx_batch_predict_measured; include/omgx.h states the semantics): the prediction of
+// `Vehicle.predict(state0=...)` / `enforce_states` / `enforce_inputs` (`vehicles/vehicle.py:302-337`) for the integrator classes.
+// state / input / fresh may lie in pinned host memory: every value is read once, by the thread that owns it.
+// ---------------------------------------------------------------------------
+struct FeedbackArgs {
+  const double* state; const double* input;      // [B, n_spl]; input: nullptr or the enforce form's
+  const int32_t* fresh;                          // [B] or nullptr (= all)
+  int coeff_off, n_spl, degree, n_knots, n_samp, n_out, p_off[4], p_t, enforce;
+  double sample_time, inv_T;
+  KnotArg knots;
+};
+
+// Agent b, called by its whole workgroup: reads the OLD plan (coeffs, global memory) and the OLD p[p_t], writes the initial
+// conditions and the new t into p.  A fresh measurement: p_off[0] from the statements of plant_predict_agent with the measured state
+// in the place of state_prev (the same bits for the same state), or the given values as they are (enforce); none: the statements of
+// predict_kernel.  stage (LDS): feedback_lds_doubles() doubles -- the staged knots and plan, the nominal inputs behind them.  Barriers inside.
+__host__ __device__ inline size_t feedback_lds_doubles(int n_spl, int degree, int n_knots, int n_samp) {
+  return plant_stage_doubles(n_spl, degree, n_knots) + (size_t)n_spl * ((size_t)n_samp + 1);
+}
+__device__ __noinline__ void feedback_predict_agent(const FeedbackArgs& fb, int b, const double* coeffs, double* pb, double tau, double t_value,
+                                                    double* stage) {
+  const bool fresh = !fb.fresh || fb.fresh[b] != 0;      // (the same branch in every thread of the workgroup)
+  const int k = threadIdx.x;
+  if (fresh && fb.enforce) {
+    if (k < fb.n_spl) {
+      pb[fb.p_off[0] + k] = fb.state[(size_t)b * fb.n_spl + k];
+      for (int o = 1; o < fb.n_out; ++o)
+        if (fb.p_off[o] >= 0) pb[fb.p_off[o] + k] = (o == 1 && fb.input) ? fb.input[(size_t)b * fb.n_spl + k] : 0.0;
+      if (k == 0) pb[fb.p_t] = t_value;
+    }
+    return;
+  }
+  const double t_rel = pb[fb.p_t];      // (the time the plan was solved at: read by every thread before thread 0 writes the new one)
+  plant_stage(fb, coeffs, stage);
+  const int L = fb.n_knots - fb.degree - 1, n_u = fb.n_samp + 1;
+  const double* kk = stage;
+  double* ub = stage + plant_stage_doubles(fb.n_spl, fb.degree, fb.n_knots);      // [n_spl][n_samp + 1]: the nominal inputs
+  if (fresh) {
+    // one (spline, sample) per thread: plant_input_at is a function of its arguments alone, the same bits whichever thread evaluates
+    // it -- the de Boor recursions of an update run side by side instead of one after the other in the owner thread
+    for (int q = k; q < fb.n_spl * n_u; q += blockDim.x) {
+      const int ks = q / n_u;
+      ub[q] = plant_input_at(fb, kk, stage + fb.n_knots + ks * L, t_rel, q - ks * n_u);
+    }
+    __syncthreads();
+  }
+  if (k >= fb.n_spl) return;
+  const double* c = stage + fb.n_knots + k * L;
+  const int j = span_of(kk, fb.degree, fb.n_knots, tau);
+  if (fresh) {
+#pragma clang fp contract(off)
+    const double s0 = fb.state[(size_t)b * fb.n_spl + k];
+    const double* u = ub + k * n_u;
+    double u_a = u[0], acc = 0.0;
+    for (int i = 1; i <= fb.n_samp; ++i) {      // (the owner thread adds up in index order: the statements of plant_predict_agent)
+      const double u_b = u[i];
+      const double h = (u_a + u_b) / 2.0;
+      acc = acc + h;
+      u_a = u_b;
+    }
+    const double m = fb.sample_time * acc;
+    pb[fb.p_off[0] + k] = s0 + m;
+  } else {
+    pb[fb.p_off[0] + k] = spline_der_at(c, kk, fb.degree, j, tau, 0);
+  }
+  double sc = fb.inv_T;
+  for (int o = 1; o < fb.n_out; ++o) {
+    if (fb.p_off[o] >= 0) pb[fb.p_off[o] + k] = spline_der_at(c, kk, fb.degree, j, tau, o) * sc;
+    sc *= fb.inv_T;
+  }
+  if (k == 0) pb[fb.p_t] = t_value;
+}
+
+// one workgroup per agent; the launch carries the launch order of the next solve as plant_predict_kernel does (block B is not an agent)
+__global__ void __launch_bounds__(256)
+feedback_predict_kernel(const double* __restrict__ x, int n_var, double* __restrict__ p, int n_par, int B, FeedbackArgs fb, double tau,
+                        double t_value, const int32_t* __restrict__ ord_iters, int32_t* __restrict__ ord_out,
+                        const double* __restrict__ ord_dw) {
+  extern __shared__ __align__(16) double lds[];
+  if (ord_iters && blockIdx.x == gridDim.x - 1) { order_block(ord_iters, ord_dw, ord_out, B); return; }
+  const int b = blockIdx.x;
+  if (b >= B) return;
+  feedback_predict_agent(fb, b, x + (size_t)b * n_var + fb.coeff_off, p + (size_t)b * n_par, tau, t_value, lds);
 }
 
 // ---------------------------------------------------------------------------

@@ -209,6 +209,14 @@ class CPlantSpec(C.Structure):
                 ('stop_tol', C.c_double)]
 
 
+class CFeedbackSpec(C.Structure):
+    """include/omgx.h omgx_feedback_spec"""
+    _fields_ = [('state', C.c_void_p), ('input', C.c_void_p), ('fresh', C.c_void_p), ('knots', C.c_void_p),
+                ('coeff_off', C.c_int32), ('n_spl', C.c_int32), ('degree', C.c_int32), ('n_knots', C.c_int32),
+                ('n_samp', C.c_int32), ('n_out', C.c_int32), ('p_off', C.c_int32 * 4), ('p_t', C.c_int32), ('enforce', C.c_int32),
+                ('sample_time', C.c_double), ('inv_T', C.c_double)]
+
+
 PREDICT_IDEAL, PREDICT_RK4 = 0, 1
 ONLY_FAILED = 8
 
@@ -331,6 +339,7 @@ PROTOTYPES = {
     'omgx_batch_plant_simulate': (C.c_int, [_H, _P, _P, _PLA, _SIG]),
     'omgx_batch_plant_predict': (C.c_int, [_H, _P, _P, _D, _D, _PLA]),
     'omgx_batch_set_plant': (C.c_int, [_H, _PLA, _SIG]),
+    'omgx_batch_predict_measured': (C.c_int, [_H, _P, _P, _D, _D, C.POINTER(CFeedbackSpec)]),
     'omgx_shift_rows': (C.c_int, [_H, _P, _I, _I, _P, _P, _I, _P, _I]),
     'omgx_admm_center': (C.c_int, [_H, _LAY] + [_P] * 3),
     'omgx_admm_update': (C.c_int, [_H, _LAY] + [_P] * 4 + [_D] + [_P] * 4),
@@ -753,6 +762,27 @@ class BatchSolver(object):
         sp = self._plant_spec(**plant)
         _check(self.lib, self.lib.omgx_batch_plant_predict(self._h, x.data_ptr(), p.data_ptr(), float(tau), float(t_value), C.byref(sp)),
                'omgx_batch_plant_predict')
+
+    def predict_measured(self, x, p, tau, t_value, state, coeff_off, n_spl, degree, knots, inv_T, n_samp, sample_time, p_off, p_t,
+                         input=None, fresh=None, enforce=False):
+        """Initial conditions of the next solve from states measured outside the loop (include/omgx.h omgx_batch_predict_measured):
+        x, p device tensors; state [B, n_spl] fp64, input [B, n_spl] fp64 or None (read with `enforce` only), fresh [B] int32 or None
+        (= all) -- device tensors or pinned host tensors, which the kernel reads over the link."""
+        _need('x', x, (self._B, self.template.n_var), 'float64 device')
+        _need('p', p, (self._B, self.template.n_par), 'float64 device')
+        _need('state', state, (self._B, ('n_spl', n_spl)), 'float64 device')
+        _need('input', input, (self._B, ('n_spl', n_spl)), 'float64 device', optional=True)
+        _need('fresh', fresh, (self._B,), 'int32 device', optional=True)
+        for nm, a, pinned_ok in (('x', x, False), ('p', p, False), ('state', state, True), ('input', input, True), ('fresh', fresh, True)):
+            if a is not None and not (a.is_cuda or (pinned_ok and a.is_pinned())):      # (a pageable host address would fault the kernel)
+                raise ValueError('%s must be a device tensor%s' % (nm, ' or a pinned host tensor' if pinned_ok else ''))
+        knots = _host_knots(knots)
+        off = [int(o) for o in p_off]
+        sp = CFeedbackSpec(state.data_ptr(), _ptr(input), _ptr(fresh), knots.ctypes.data, int(coeff_off), int(n_spl), int(degree), len(knots),
+                           int(n_samp), len(off), (C.c_int32 * 4)(*(off + [-1] * 4)[:4]), int(p_t), int(bool(enforce)),
+                           float(sample_time), float(inv_T))
+        _check(self.lib, self.lib.omgx_batch_predict_measured(self._h, x.data_ptr(), p.data_ptr(), float(tau), float(t_value), C.byref(sp)),
+               'omgx_batch_predict_measured')
 
     def set_plant(self, plant=None, log=None):
         """Every following `rollout` runs with the plant in the loop (include/omgx.h omgx_batch_set_plant; plant=None: off).  The

@@ -10,7 +10,7 @@ with a primal-dual warm start.
 Layout: `BatchP2P` states that protocol once -- tables and options from the template, `solve_cold`, `step`, `rollout`, the stop rule,
 the log -- and branches on no executor.  Where the [B, *] arrays live and who computes on them sits behind its hooks (`_allocate,
 _predict, _shift, _solve, _cold, _rollout, _norm, _stop_rule, _signals_alloc, _signals_fused, _signals_append_now,
-_signals_summary, _plant_alloc, _plant_predict, _plant_simulate, _plant_rollout`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
+_signals_summary, _plant_alloc, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
 being the allocator / stream only; no data leaves HBM between steps) and `HostP2P` (`ops=<a host solver object>`: the same
 statements in numpy, how the parity tests and the CPU baseline of bench.py replay the loop; this package never imports the
 oracle).  `BatchP2P(problem, P, ops=...)` hands out the executor `ops` names.  The clock of a step is `splines.step_clock`, the
@@ -19,6 +19,8 @@ obstacle motion `splines.advance_obstacles`: shared with the formation loops.
 `BatchP2P.plant` puts a simulated vehicle into the loop (the reference's default `ideal_prediction=False, ideal_update=False`, with an
 optional input disturbance): step (1) then starts the solve from the state the vehicle had one update ago integrated under the planned
 inputs, and after step (3) the vehicle travels the update under the applied inputs (include/omgx.h OMGX_HAS_PLANT has the statements).
+`BatchP2P.feedback` lets `step` take states measured outside the loop instead (`step(states=...)`, the reference's
+`Deployer.update(current_time, states, ...)`; include/omgx.h OMGX_HAS_FEEDBACK): a loop has one source of states.
 """
 import os
 
@@ -138,6 +140,7 @@ class BatchP2P(object):
         self.under_way, self.stop_tol = None, 1e-3        # (stop_at_arrival)
         self._sig = None                                  # (record_signals)
         self._pl = None                                   # (plant)
+        self._fb = None                                   # (feedback)
         self._plan_ready = False                          # (solve_cold has run: x holds a plan)
         # (warm_mu_factor 0.1: a step starts at the barrier parameter the previous solve of the agent ended with, tol / 10,
         # unless the shifted point is far off that central path -- a tenth of its average complementarity then: at tol 1e-3
@@ -181,14 +184,37 @@ class BatchP2P(object):
         return 0
 
     # -- one receding-horizon step ---------------------------------------------------------
-    def step(self, events=None, before_solve=None):
+    def step(self, events=None, before_solve=None, states=None, inputs=None, fresh=None, enforce=False):
         """before_solve(self): called between the glue of the step (prediction, obstacles, shift: p and x are what the
         solve will read) and the solve -- where a caller with host buffers uploads its parameters (bench.py's pipelined
-        host-boundary leg)."""
+        host-boundary leg).
+
+        states [B, n_spl] (after `feedback`): the states measured at the start of the update that ends now -- the reference's
+        `Deployer.update(current_time, states, ...)` -> `Vehicle.predict(state0=...)`.  Part (1) of the step is then the measured
+        prediction: the solve starts from `states` integrated over the update under the current plan's inputs.  fresh [B] (0 / 1,
+        None: all): an agent with 0 has no measurement at this update and is predicted from its plan.  enforce: the solve starts
+        from `states` as they are, with `inputs` [B, n_spl] (None: zero) as its initial input (`enforce_states` / `enforce_inputs`).
+        Device loop: device or pinned host tensors (include/omgx.h omgx_batch_predict_measured); host loop: arrays."""
+        if states is None:
+            if inputs is not None or fresh is not None or enforce:
+                raise ValueError('step: inputs / fresh / enforce go with states')
+        else:
+            if self._fb is None:
+                raise RuntimeError('step(states=...): call feedback() first (it fixes the sample grid of the prediction)')
+            if self._pl is not None:
+                raise ValueError('step(states=...): the plant is in the loop; a loop has one source of states')
+            if inputs is not None and not enforce:
+                raise ValueError('step: inputs are read with enforce=True only')
+            for nm, a, shape in (('states', states, (self.B, self.n_spl)), ('inputs', inputs, (self.B, self.n_spl)), ('fresh', fresh, (self.B,))):
+                if a is not None and tuple(a.shape) != shape:
+                    raise ValueError('step: %s must be %s, got %s' % (nm, list(shape), list(a.shape)))
         t_now, tau, t_rel, crossed = step_clock(self.time, self.update_time, self.knot_time, self.T)
         # (1) ideal prediction on the current plan, (2) horizon bookkeeping: the initial conditions from the plan at tau and the new t
-        # (with the plant in the loop: from the state the vehicle had one update ago, and the stop test on the travelled state)
-        if self._pl is None:
+        # (with the plant in the loop: from the state the vehicle had one update ago, and the stop test on the travelled state;
+        # with measured states: from those)
+        if states is not None:
+            self._feedback_predict(tau, t_rel, states, inputs, fresh, bool(enforce))
+        elif self._pl is None:
             self._predict(tau, t_rel)
         else:
             self._plant_predict(tau, t_rel)
@@ -210,7 +236,8 @@ class BatchP2P(object):
         between the steps of different agents (they are independent problems: each vehicle of the reference runs its own
         `Deployer.update` loop).  After `plant` the vehicle of every agent is simulated inside the launch too -- prediction from the
         travelled state, input disturbance, stop test on the travelled state: a disturbance study of a whole fleet in one launch.  A
-        deployment that feeds states measured outside back steps with `step`.  Returns the number of knot crossings."""
+        deployment that feeds states measured outside back steps with `step` (`feedback`, `step(states=...)`): a rollout takes none.
+        Returns the number of knot crossings."""
         clock, t = [], self.time
         for _ in range(int(n_steps)):
             t, tau, t_rel, crossed = step_clock(t, self.update_time, self.knot_time, self.T)
@@ -242,7 +269,8 @@ class BatchP2P(object):
         """Per agent: the reference's `stop_criterium` (`problems/point2point.py:98-102` -> `vehicles/holonomic.py:145-151`,
         `holonomic3d.py`: |state - poseT| <= stop_tol and |input| <= stop_tol, Euclidean norms, `stop_tol` = 1e-3 by default,
         `vehicles/vehicle.py:72`) on the state the last prediction wrote into p -- the state the vehicle is in at the time of
-        the current update -- or, after `plant`, on the travelled state and the last applied input.  Boolean tensor (device loop) / array (host loop); the reference's `Simulator.run` ends a vehicle's
+        the current update (with `step(states=...)`: the state predicted from the measurement, or the enforced one) -- or, after `plant`,
+        on the travelled state and the last applied input.  Boolean tensor (device loop) / array (host loop); the reference's `Simulator.run` ends a vehicle's
         loop at the first update for which this holds (`execution/simulator.py:39-62`).  Point-mass classes (state0 / input0 / poseT)."""
         st, inp, pose = (self.p[:, o:o + self.n_dim] for o in (self.o_state0, self.o_input0, self._o_pose('arrived')))
         pl = getattr(self, '_pl', None)
@@ -256,7 +284,9 @@ class BatchP2P(object):
         vehicles arrive at different updates) -- it keeps its plan, its multipliers and its status, `iters` reads 0.  Device loop:
         the rule is the solve kernel's (`omgx_batch_set_stop`, no launch of its own); `under_way` [B] (int32 tensor / bool array)
         holds who is still running.  The agents under way are solved exactly as without the rule.  `rollout` applies it too: an agent's
-        loop inside the launch ends at the step its state meets the criterion (its plan stays as it is at that step)."""
+        loop inside the launch ends at the step its state meets the criterion (its plan stays as it is at that step).  With
+        `step(states=...)` the rule still tests p[state0], p[input0]: now the state predicted from the measurement (or the enforced
+        state and input), not the measurement itself."""
         o_pose = self._o_pose('stop_at_arrival') if on else None
         if on:
             self.stop_tol = float(stop_tol)
@@ -281,6 +311,8 @@ class BatchP2P(object):
         n_samp = int(round(self.update_time / float(sample_time), 6))
         if n_samp < 1 or int(max_updates) < 1:
             raise ValueError('record_signals: sample_time must not exceed update_time and max_updates must be positive')
+        if self._fb is not None and self._fb['sample_time'] != float(sample_time):
+            raise ValueError('record_signals: measured states are integrated with sample_time %g (feedback)' % self._fb['sample_time'])
         if self._pl is not None:
             if self._pl['sample_time'] != float(sample_time):
                 raise ValueError('record_signals: the plant is simulated with sample_time %g' % self._pl['sample_time'])
@@ -335,6 +367,8 @@ class BatchP2P(object):
             raise ValueError('plant: sample_time must not exceed update_time and max_updates must be positive')
         if self._sig is not None and self._sig['sample_time'] != float(sample_time):
             raise ValueError('plant: the log is kept with sample_time %g' % self._sig['sample_time'])
+        if self._fb is not None and self._fb['sample_time'] != float(sample_time):
+            raise ValueError('plant: measured states are integrated with sample_time %g (feedback)' % self._fb['sample_time'])
         shape = (self.B, self.n_spl, int(max_updates), n_samp + 1)
         if disturbance is not None and tuple(disturbance.shape) != shape:
             raise ValueError('plant: disturbance must be [B, n_spl, max_updates, n_samp + 1] = %s, got %s' % (shape, tuple(disturbance.shape)))
@@ -353,6 +387,34 @@ class BatchP2P(object):
         if self._pl is None:
             raise RuntimeError('plant_state(): call plant() first')
         return dict((nm, self._pl[nm]) for nm in ('state', 'state_prev', 'input_last', 'n_upd', 'overflow'))
+
+    # -- states measured outside the loop ------------------------------------------------------------
+    def feedback(self, sample_time=0.01, on=True):
+        """Let `step` take measured states (`step(states=...)`): the reference's deployment contract, `Deployer.update(current_time,
+        states, inputs, ..., enforce_states, enforce_inputs)` -> `Vehicle.predict(state0=...)` (`execution/deployer.py:43-79`,
+        `vehicles/vehicle.py:302-337`).  Fixes the sample grid the measured state is integrated on, n_samp = update_time /
+        sample_time intervals per update (the trapezoid sum of the plan's inputs: exact for the reference's linearly interpolated
+        input).  Integrator classes (`ode` = input: Holonomic, Holonomic3D) without the first-order actuator lag; every agent on the
+        batch's one clock (no `delay`).  `rollout` takes no states.  on=False: `step` takes none again."""
+        if not on:
+            self._fb = None
+            return
+        lay, label = self.tpl.par_layout, self.veh.label
+        cls_name = type(self.veh).__name__ if hasattr(self.veh, 'ode') else label
+        if any((label, nm) not in lay for nm in ('state0', 'input0', 'poseT')) or self.n_spl != self.n_dim:
+            raise NotImplementedError('feedback(): %s is not an integrator class (ode = input: Holonomic, Holonomic3D, parameters state0 / '
+                                      'input0 / poseT); its own model is not integrated in the batched loop' % cls_name)
+        if getattr(self.veh, 'options', {}).get('1storder_delay'):
+            raise NotImplementedError("feedback(): %s has '1storder_delay' set; the first-order actuator lag is not integrated in the batched loop" % cls_name)
+        if getattr(self, 'pool', None) is not None:
+            raise NotImplementedError('feedback: not with a host pool (its workers run the step glue themselves)')
+        n_samp = int(round(self.update_time / float(sample_time), 6))
+        if n_samp < 1:
+            raise ValueError('feedback: sample_time must not exceed update_time')
+        for what, g in (('log', self._sig), ('plant', self._pl)):
+            if g is not None and g['sample_time'] != float(sample_time):
+                raise ValueError('feedback: the %s is kept with sample_time %g' % (what, g['sample_time']))
+        self._fb = dict(sample_time=float(sample_time), n_samp=n_samp)
 
     def signals(self):
         """The log of `record_signals`: dict with `count` [B] (columns written per agent), `time` [cap] (the time of the first logged
@@ -550,6 +612,22 @@ class DeviceP2P(BatchP2P):
             self.solver.order_by_iters(self.iters, self._order)
         self.solver.plant_predict(self.x, self.p, tau, t_rel, self._plant_args())
 
+    def _feedback_predict(self, tau, t_rel, states, inputs, fresh, enforce):
+        """One launch: the initial conditions from the measured states (device or pinned host tensors; an array is uploaded first),
+        the new t, and -- as `_predict` -- the ordering of the next solve as one more workgroup."""
+        t = self.torch
+
+        def dev(a, dtype):
+            if a is None or t.is_tensor(a):
+                return a
+            return t.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(self.dev)
+        states, inputs, fresh = dev(states, t.float64), dev(inputs, t.float64), dev(fresh, t.int32)
+        if self.straggler_first:
+            self.solver.order_by_iters(self.iters, self._order)
+        g = self._fb
+        self.solver.predict_measured(self.x, self.p, tau, t_rel, states, input=inputs, fresh=fresh, enforce=enforce, n_samp=g['n_samp'],
+                                     sample_time=g['sample_time'], p_off=self.p_offs, p_t=self.o_t, **self._plan)
+
     def _plant_simulate(self):
         self.solver.plant_simulate(self.x, self.p, self._plant_args(), self._plant_log_args())
 
@@ -583,9 +661,11 @@ class HostP2P(BatchP2P):
         self.status, self.iters = np.zeros(self.B, dtype=np.int32), np.zeros(self.B, dtype=np.int32)
         self._log_in_solve = True                # (`_signals_fused`)
 
-    def step(self, events=None, before_solve=None):
+    def step(self, events=None, before_solve=None, states=None, inputs=None, fresh=None, enforce=False):
         if self.pool is None:
-            return BatchP2P.step(self, events, before_solve)
+            return BatchP2P.step(self, events, before_solve, states, inputs, fresh, enforce)
+        if states is not None or inputs is not None or fresh is not None or enforce:
+            raise NotImplementedError('step(states=...): not with a host pool (its workers run the step glue themselves)')
         t_now, tau, t_rel, crossed = step_clock(self.time, self.update_time, self.knot_time, self.T)
         self.time = t_now
         self._solve(True, step_desc=self._pool_step(tau, t_rel, crossed), extra=self.cross_options if crossed else None)
@@ -717,10 +797,10 @@ class HostP2P(BatchP2P):
         out['dist'] = None if disturbance is None else np.ascontiguousarray(disturbance, dtype=float).copy()
         return out
 
-    def _plant_plan(self, b):
+    def _plant_plan(self, b, g=None):
         """(c, t_rel, u): the plan of agent b [n_spl, L], the time it was solved at, and its inputs (time derivative) at the samples
-        0 .. n_samp of the update [n_spl, n_samp + 1]."""
-        g = self._pl
+        0 .. n_samp of the update [n_spl, n_samp + 1].  g: whose sample grid (the plant's; `_feedback_predict` passes its own)."""
+        g = self._pl if g is None else g
         inv_T = 1.0 / self.T
         c = self.x[b, self.o_spl:self.o_spl + self.n_spl * self.L].reshape(self.n_spl, self.L)
         t_rel = float(self.p[b, self.o_t])
@@ -765,6 +845,25 @@ class HostP2P(BatchP2P):
 
     def _plant_rollout(self):
         pass
+
+    def _feedback_predict(self, tau, t_rel, states, inputs, fresh, enforce):
+        """`omgx_batch_predict_measured` in numpy: an agent without a fresh measurement as `_predict`, one with as `_plant_predict`
+        with the measured state in the place of `state_prev` (the same statements: the same bits), or the given values (enforce)."""
+        states = np.asarray(states, dtype=float)
+        go = np.ones(self.B, dtype=bool) if fresh is None else np.asarray(fresh) != 0
+        st, new = self._fb['sample_time'], {}
+        if not enforce:                                   # (ahead of `_predict`: `_plant_plan` reads the time the plan was solved at)
+            Ed = self._eval_rows(tau)[1]
+            for b in np.flatnonzero(go):
+                c, _, u = self._plant_plan(b, self._fb)
+                new[b] = (states[b] + st * np.cumsum((u[:, :-1] + u[:, 1:]) / 2.0, axis=1)[:, -1], c @ Ed)
+        self._predict(tau, t_rel)
+        if enforce:
+            self.p[go, self.o_state0:self.o_state0 + self.n_spl] = states[go]
+            self.p[go, self.o_input0:self.o_input0 + self.n_spl] = 0.0 if inputs is None else np.asarray(inputs, dtype=float)[go]
+        for b, (s0, i0) in new.items():
+            self.p[b, self.o_state0:self.o_state0 + self.n_spl] = s0
+            self.p[b, self.o_input0:self.o_input0 + self.n_spl] = i0
 
     def _signals_summary(self, target):
         return signals_summary_numpy(self._sig['log'], self._sig['count'], target, self._sig['sample_time'])
@@ -885,14 +984,26 @@ class StreamedP2P(object):
     def restart_failed(self, *a, **kw):
         return max(self._each(lambda m: m.restart_failed(*a, **kw)))
 
-    def step(self, events=None, before_solve=None):
-        """events: one (start, stop) pair per sub-batch (stamped on that sub-batch's solve kernel)."""
+    def step(self, events=None, before_solve=None, states=None, inputs=None, fresh=None, enforce=False):
+        """events: one (start, stop) pair per sub-batch (stamped on that sub-batch's solve kernel).  states / inputs / fresh
+        (`BatchP2P.step`): of the whole batch, every sub-batch gets its rows; the sub-batches' streams wait for what the caller's
+        stream has enqueued so far (the tensors may still be written there)."""
         evs = events if events is not None else [None] * len(self.parts)
         hooks = before_solve if isinstance(before_solve, (list, tuple)) else [before_solve] * len(self.parts)
+        fed = {}
+        if states is not None or inputs is not None or fresh is not None or enforce:
+            for nm, a, shape in (('states', states, (self.B, self.parts[0].n_spl)), ('inputs', inputs, (self.B, self.parts[0].n_spl)), ('fresh', fresh, (self.B,))):
+                if a is not None and tuple(a.shape) != shape:
+                    raise ValueError('step: %s must be %s, got %s' % (nm, list(shape), list(a.shape)))
+            self.fork()
+            fed = dict(states=states, inputs=inputs, fresh=fresh)
         out = []
-        for part, st, ev, hk in zip(self.parts, self.streams, evs, hooks):
+        for (lo, hi), part, st, ev, hk in zip(self.bounds, self.parts, self.streams, evs, hooks):
+            kw = dict((nm, None if a is None else a[lo:hi]) for nm, a in fed.items())
+            if fed:
+                kw['enforce'] = enforce
             with self.torch.cuda.stream(st):
-                out.append(part.step(events=ev, before_solve=hk))
+                out.append(part.step(events=ev, before_solve=hk, **kw))
         return any(out)
 
     def stop_at_arrival(self, stop_tol=1e-3, on=True):
@@ -908,6 +1019,11 @@ class StreamedP2P(object):
         for (lo, hi), m, st in zip(self.bounds, self.parts, self.streams):
             with self.torch.cuda.stream(st):
                 m.plant(sample_time, max_updates, None if disturbance is None else disturbance[lo:hi], on)
+
+    def feedback(self, sample_time=0.01, on=True):
+        """`BatchP2P.feedback` for every sub-batch; `step(states=...)` then hands each its rows."""
+        for m in self.parts:
+            m.feedback(sample_time, on)
 
     def plant_state(self):
         """`BatchP2P.plant_state` of the whole batch, joined and concatenated like `signals`."""
