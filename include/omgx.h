@@ -597,6 +597,49 @@ typedef struct omgx_feedback_spec {
 int  omgx_batch_predict_measured(omgx_batch* b, const double* x, double* p, double tau, double t_value,
                                  const omgx_feedback_spec* sp);
 
+/* (OMGX_HAS_OBSTACLE_SCRIPT) Obstacle scripts: the reference's obstacle trajectories `simulation={'trajectories': {...}}` -- at given
+ * times a value is added to an obstacle's position, velocity or acceleration, between these jumps it moves with constant
+ * acceleration (`environment/obstacle.py:172-264`) -- for the whole batch.  Per agent b a list of n_ev events (time, what, value[3]):
+ * what = 3 * obstacle + kind, kind 0 / 1 / 2 = position / velocity / acceleration; obstacle indexes the table obst [n_obst][4] =
+ * {p_x, p_v, p_a, n_dim} (the one omgx_batch_rollout takes: at most 8 obstacles, n_dim <= 3); events ascending in time per agent, pads
+ * have time = +inf.  Times are absolute loop time, starting at 0 (the reference's `signals['time']`).  An event at time 0 is not
+ * part of a script: the reference folds it into the initial state (`obstacle.py:50-55`).
+ *
+ * One update carries the parameters x, v, a of every listed obstacle from t_prev to t_now = t_prev + dt:
+ *   an event belongs to the update if  t_prev + 1e-9 < time <= t_now + 1e-9.
+ *   No event of the agent belongs to it: the statements of the plain obstacle motion with dt and c2 = 0.5 * dt * dt, every product
+ *     and sum rounded on its own (no fused multiply-add):  m1 = dt v, m2 = c2 a, x += (m1 + m2), v += dt a.  A loop with a script that
+ *     never fires gives the bits of the plain loop.
+ *   Otherwise the events of the update in table order, from t_cur = t_prev: for each, h = min(time, t_now) - t_cur; if h > 1e-9
+ *     the same statements run with h and 0.5 * h * h and t_cur becomes min(time, t_now); then the event's value is added to its
+ *     kind.  After the last event the rest h = t_now - t_cur runs if it is above 1e-9.  One exception: an event with
+ *     t_now - time <= 1e-9 met while t_cur is still t_prev gets the whole-interval statements with dt itself (t_cur <- t_now): an
+ *     event on the update grid shares every bit with the plain motion up to its jump.
+ *   The motion is exact for the model (constant acceleration between jumps); no sample grid is involved.
+ * time [B, n_ev] fp64, what [B, n_ev] int32 and value [B, n_ev, 3] fp64 are DEVICE arrays.  what must lie in 0 .. 3 * n_obst - 1:
+ * with what_host (a host copy of what) the library checks it; without, the kernel skips the jump of an event outside that range
+ * (its time still splits the update).
+ * omgx_batch_obstacles_advance: one launch on the handle's stream, a few agents per workgroup, p [B, n_par] device.
+ * omgx_batch_set_obstacle_script: every following omgx_batch_rollout runs the script instance of its kernel -- its obstacle motion
+ * is this update between t_abs[k] and t_abs[k + 1] (t_abs [n_t] host: the absolute time of every step boundary, n_t >= n_steps + 1
+ * or the rollout is refused; its obstacle table must be the script's); script == NULL switches it off.  The time / what / value
+ * arrays must stay valid while the script is set; obst, what_host and t_abs are read during the call.  Inside a rollout an agent's
+ * obstacles move only while its loop runs (a stopped agent's stay where they were).
+ * Checks, in this order: the specification and its time / what / value / obst (and p, or t_abs) not null; 1 <= n_ev <= 32,
+ * 1 <= n_obst <= 8, 1 <= n_dim <= 3 for every obstacle (set: n_t >= 2, advance: dt a positive number); the handle; what_host within
+ * range; every obstacle entry inside p. */
+#define OMGX_HAS_OBSTACLE_SCRIPT 1
+typedef struct omgx_obstacle_script {
+  const double*  time;       /* [B, n_ev] device */
+  const int32_t* what;       /* [B, n_ev] device */
+  const double*  value;      /* [B, n_ev, 3] device */
+  const int32_t* what_host;  /* [B, n_ev] host copy of what, or NULL */
+  const int32_t* obst;       /* [n_obst][4] host */
+  int32_t n_ev, n_obst;
+} omgx_obstacle_script;
+int  omgx_batch_obstacles_advance(omgx_batch* b, double* p, const omgx_obstacle_script* sp, double t_prev, double dt);
+int  omgx_batch_set_obstacle_script(omgx_batch* b, const omgx_obstacle_script* sp, const double* t_abs, int32_t n_t);
+
 /* Same shift on any device-resident row-major array (stride doubles per row, n_rows rows):
  * used for the ADMM consensus state on a knot crossing (`problems/admm.py:477-491`).
  * The handle keeps the table sets it has seen on the device (16, found again by content): a loop that shifts with the

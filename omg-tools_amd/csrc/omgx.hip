@@ -53,6 +53,7 @@ struct Instances {
   ipm_kernel_t full = nullptr, refine = nullptr, lean = nullptr;
   ipm_eval_kernel_t eval = nullptr;
   ipm_rollout_t rollout = nullptr, rollout_plant = nullptr;      // (rollout_plant: the instance with the plant in the loop, omgx_batch_set_plant)
+  ipm_rollout_t rollout_script = nullptr, rollout_plant_script = nullptr;      // (the two with an obstacle script, omgx_batch_set_obstacle_script)
   decltype(&ipm_prepare_kernel<true>) prepare = nullptr;
 };
 static Instances instances_for(int mode, int wave_ok, int general) {
@@ -64,6 +65,8 @@ static Instances instances_for(int mode, int wave_ok, int general) {
   in.eval = ipm_eval_kernel_for(mode, wave_ok, general);
   in.rollout = rollout_kernel_for(mode, wave_ok, general);
   in.rollout_plant = rollout_kernel_for(mode, wave_ok, general, 1);
+  in.rollout_script = rollout_kernel_for(mode, wave_ok, general, 0, 1);
+  in.rollout_plant_script = rollout_kernel_for(mode, wave_ok, general, 1, 1);
   in.prepare = general ? ipm_prepare_kernel<true> : ipm_prepare_kernel<false>;
   return in;
 }
@@ -120,7 +123,12 @@ struct omgx_batch {
   PlantBlock* d_plant = nullptr;    // ... their copy in device memory ...
   PlantBlock* d_plant_call = nullptr;      // ... and the copy of what a stand-alone omgx_batch_plant_simulate / _predict call was given
   bool plant_on = false;
-  StopArgs* d_stop = nullptr;       // omgx_batch_set_stop: device copy of the arguments
+  ObstacleScriptArgs script_host = {};      // omgx_batch_set_obstacle_script: the script as the rollout's script instances read it ...
+  ObstacleScriptArgs* d_script = nullptr;   // ... its copy in device memory ...
+  ObstacleScriptArgs* d_script_call = nullptr;      // ... and the copy of what a stand-alone omgx_batch_obstacles_advance call was given
+  DevBuf script_t; int script_t_cap = 0;    // (t_abs of the script set: grows with the longest step list registered)
+  bool script_on = false;
+  StopArgs* d_stop = nullptr;      // omgx_batch_set_stop: device copy of the arguments
   StopArgs stop_host = {};          // (and the host copy: omgx_batch_rollout hands it to its kernel inside RolloutArgs)
   bool stop_on = false;
   int last_instance = 0;            // solve-kernel instance of the last omgx_batch_solve launch: 0 full, 1 lean (omgx_batch_last_instance)
@@ -694,11 +702,11 @@ int create_batch(omgx_batch* b, const omgx_template* tpl) {
   static int lds_reserved[4 * omgx::WS_MODES] = {0};
   int& reserved = lds_reserved[4 * b->ws_mode + (d.wave_ok ? 1 : 0) + (d.general ? 2 : 0)];
   if ((int)b->lds_bytes > reserved) reserved = (int)b->lds_bytes;
-  const void* const launched[5] = {(const void*)b->inst.full, (const void*)b->inst.refine, (const void*)b->inst.lean, (const void*)b->inst.rollout,
-                                   (const void*)b->inst.rollout_plant};
+  const void* const launched[7] = {(const void*)b->inst.full, (const void*)b->inst.refine, (const void*)b->inst.lean, (const void*)b->inst.rollout,
+                                   (const void*)b->inst.rollout_plant, (const void*)b->inst.rollout_script, (const void*)b->inst.rollout_plant_script};
   for (const void* k : launched)
     if (k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, reserved) != hipSuccess) {
-      g_err = (k == (const void*)b->inst.rollout || k == (const void*)b->inst.rollout_plant) ? "cannot reserve dynamic LDS for ipm_rollout_kernel" : "cannot reserve dynamic LDS for ipm_solve_kernel";
+      g_err = (k != (const void*)b->inst.full && k != (const void*)b->inst.refine && k != (const void*)b->inst.lean) ? "cannot reserve dynamic LDS for ipm_rollout_kernel" : "cannot reserve dynamic LDS for ipm_solve_kernel";
       return OMGX_E_HIP;
     }
   {
@@ -1438,6 +1446,18 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
                "omgx_batch_plant_predict / omgx_batch_solve / omgx_batch_plant_simulate");
   if (b->plant_on && (!same_plan(*sp, b->plant_host.pl) || sp->p_t != b->plant_host.pl.p_t))
     return bad("rollout: the plan of the specification (coeff_off, n_spl, degree, n_knots, p_t) is not the one the plant was set with");
+  if (b->script_on) {
+    const ObstacleScriptArgs& sc = b->script_host;
+    if (!(b->plant_on ? b->inst.rollout_plant_script : b->inst.rollout_script) || !b->d_script)
+      return bad("rollout: an obstacle script is set (omgx_batch_set_obstacle_script) but this template class has no script instance of the "
+                 "rollout kernel: step with omgx_batch_obstacles_advance / omgx_batch_solve");
+    if (sc.n_t < sp->n_steps + 1)
+      return bad("rollout: t_abs of the obstacle script holds %d times, n_steps + 1 = %d are needed", sc.n_t, sp->n_steps + 1);
+    bool same = sp->n_obst == sc.n_obst;
+    for (int q = 0; same && q < sc.n_obst; ++q)
+      for (int k = 0; k < 4; ++k) same = same && sp->obst[4 * q + k] == sc.obst[q][k];
+    if (!same) return bad("rollout: the obstacle table of the specification is not the one the obstacle script was set with");
+  }
   RolloutArgs a;
   memset(&a, 0, sizeof a);
   TRY(check_predict_in_xp(b, "rollout", pl, sp->n_out, sp->p_off, sp->p_t, a.p_off));
@@ -1493,6 +1513,9 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   }
   a.iters_log = sp->iters_log; a.status_log = sp->status_log;
   a.plant = b->plant_on ? b->d_plant : nullptr;
+  a.script = b->script_on ? b->d_script : nullptr;
+  const ipm_rollout_t kern = b->script_on ? (b->plant_on ? b->inst.rollout_plant_script : b->inst.rollout_script)
+                                          : (b->plant_on ? b->inst.rollout_plant : b->inst.rollout);
   // Two small copies per call (one call is n_steps steps of the whole batch), ORDERED ON THE HANDLE'S STREAM: the persistent
   // kernel of a previous rollout reads these tables for its whole run, and on a non-blocking caller stream a null-stream
   // hipMemcpy would overwrite them under it (pageable sources: staged before the calls return, executed in stream order).
@@ -1503,7 +1526,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   hipEvent_t e0 = b->ext_ev0, e1 = b->ext_ev0 ? b->ext_ev1 : nullptr;
   b->ext_ev0 = b->ext_ev1 = nullptr;
   b->timed = false;
-  hipExtLaunchKernelGGL(b->plant_on ? b->inst.rollout_plant : b->inst.rollout, dim3(b->n_slabs < b->n_agents ? b->n_slabs : b->n_agents), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream, e0, e1, 0u,
+  hipExtLaunchKernelGGL(kern, dim3(b->n_slabs < b->n_agents ? b->n_slabs : b->n_agents), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream, e0, e1, 0u,
                         d, b->dev, b->opts, b->kkt_doubles, p, x, lbg, ubg, shared ? 1 : 0, lam_g, status, iters, b->n_agents,
                         b->d_slabs, b->slab_doubles, b->d_dw, b->d_next, (const RolloutArgs*)b->d_rollout, b->stagger, b->d_order,
                         (const StoreArgs*)((b->store.out || b->signals.log) ? &b->d_store->st : nullptr));
@@ -1565,6 +1588,73 @@ int omgx_batch_predict_measured(omgx_batch* b, const double* x, double* p, doubl
   hipLaunchKernelGGL(feedback_predict_kernel, dim3(b->n_agents + (oi ? 1 : 0)), dim3(64), lds, b->stream, x, b->dims.n_var, p, b->dims.n_par, b->n_agents,
                      a, tau, t_value, oi, oo, (const double*)(b->order_dw ? b->d_dw : nullptr));
   HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
+namespace {
+// An obstacle script -> the block the kernels read.  The checks that need no handle come first; `who` names the entry.
+int fill_script(const omgx_batch* b, const char* who, const omgx_obstacle_script* sp, ObstacleScriptArgs* a) {
+  if (!sp->time || !sp->what || !sp->value || !sp->obst) return bad("%s: null time / what / value / obst", who);
+  if (sp->n_ev < 1 || sp->n_ev > 32) return bad("%s: n_ev = %d outside 1 .. 32", who, sp->n_ev);
+  if (sp->n_obst < 1 || sp->n_obst > 8) return bad("%s: n_obst = %d outside 1 .. 8", who, sp->n_obst);
+  for (int q = 0; q < sp->n_obst; ++q)
+    if (sp->obst[4 * q + 3] < 1 || sp->obst[4 * q + 3] > 3) return bad("%s: n_dim = %d of obstacle %d outside 1 .. 3", who, sp->obst[4 * q + 3], q);
+  if (!b) return bad("null handle");
+  if (sp->what_host)
+    for (size_t i = 0; i < (size_t)b->n_agents * sp->n_ev; ++i)
+      if (sp->what_host[i] < 0 || sp->what_host[i] >= 3 * sp->n_obst)
+        return bad("%s: what = %d of agent %d, event %d outside 0 .. %d", who, sp->what_host[i], (int)(i / sp->n_ev), (int)(i % sp->n_ev), 3 * sp->n_obst - 1);
+  *a = ObstacleScriptArgs{};
+  for (int q = 0; q < sp->n_obst; ++q) {
+    for (int k = 0; k < 4; ++k) a->obst[q][k] = sp->obst[4 * q + k];
+    for (int k = 0; k < 3; ++k)
+      if (!in_p(b, a->obst[q][k], a->obst[q][3])) return bad("%s: obst[%d][%d] = %d outside p", who, q, k, a->obst[q][k]);
+  }
+  a->time = sp->time; a->what = sp->what; a->value = sp->value; a->n_ev = sp->n_ev; a->n_obst = sp->n_obst;
+  return OMGX_OK;
+}
+}  // namespace
+
+int omgx_batch_obstacles_advance(omgx_batch* b, double* p, const omgx_obstacle_script* sp, double t_prev, double dt) {
+  if (!sp || !p) return bad("obstacles_advance: null p / specification");
+  if (!sp->time || !sp->what || !sp->value || !sp->obst) return bad("obstacles_advance: null time / what / value / obst");
+  if (t_prev != t_prev || !(dt > 0.0) || dt - dt != 0.0) return bad("obstacles_advance: t_prev = %g is not a number or dt = %g not a positive number", t_prev, dt);
+  ObstacleScriptArgs a;
+  TRY(fill_script(b, "obstacles_advance", sp, &a));
+  HIPCHK(hipSetDevice(b->device));
+  TRY(push_args(b, &b->d_script_call, a));
+  hipLaunchKernelGGL(obstacles_advance_kernel, dim3((b->n_agents + 7) / 8), dim3(256), 0, b->stream, p, b->dims.n_par, b->n_agents,
+                     (const ObstacleScriptArgs*)b->d_script_call, t_prev, t_prev + dt, dt);
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
+int omgx_batch_set_obstacle_script(omgx_batch* b, const omgx_obstacle_script* sp, const double* t_abs, int32_t n_t) {
+  if (!sp) {
+    if (!b) return bad("null handle");
+    b->script_on = false;
+    return OMGX_OK;
+  }
+  if (!sp->time || !sp->what || !sp->value || !sp->obst) return bad("set_obstacle_script: null time / what / value / obst");
+  if (!t_abs) return bad("set_obstacle_script: null t_abs");
+  if (n_t < 2) return bad("set_obstacle_script: n_t = %d, the step boundaries of at least one step are needed", n_t);
+  for (int k = 0; k < n_t; ++k)
+    if (t_abs[k] - t_abs[k] != 0.0 || (k > 0 && !(t_abs[k] > t_abs[k - 1]))) return bad("set_obstacle_script: t_abs[%d] = %g is not a number above t_abs[%d]", k, t_abs[k], k - 1);
+  ObstacleScriptArgs a;
+  TRY(fill_script(b, "set_obstacle_script", sp, &a));
+  b->script_on = false;      // (a failed registration leaves the script OFF)
+  HIPCHK(hipSetDevice(b->device));
+  if (n_t > b->script_t_cap) {
+    b->script_t_cap = 0;
+    HIPCHK(b->script_t.alloc(sizeof(double) * (size_t)n_t));      // (frees the shorter table first)
+    b->script_t_cap = n_t;
+  }
+  // (stream-ordered, like the step table of omgx_batch_rollout: a rollout still running reads the previous times)
+  HIPCHK(hipMemcpyAsync(b->script_t.p, t_abs, sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice, b->stream));
+  a.t_abs = (const double*)b->script_t.p; a.n_t = n_t;
+  b->script_host = a;
+  TRY(push_args(b, &b->d_script, b->script_host));
+  b->script_on = true;
   return OMGX_OK;
 }
 

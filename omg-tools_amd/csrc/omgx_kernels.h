@@ -1064,6 +1064,85 @@ feedback_predict_kernel(const double* __restrict__ x, int n_var, double* __restr
 }
 
 // ---------------------------------------------------------------------------
+// Obstacle scripts (omgx_batch_set_obstacle_script; include/omgx.h OMGX_HAS_OBSTACLE_SCRIPT states the semantics): the reference's
+// `simulation={'trajectories': ...}` -- at given times a value is added to an obstacle's position, velocity or acceleration, between
+// the jumps it moves with constant acceleration (`environment/obstacle.py:172-264`).  One routine carries the parameters x, v, a of
+// every listed obstacle of an agent over one update; lane 4 q + i (i < n_dim <= 3, q < n_obst <= 8: the first 32 lanes of whoever
+// calls) owns component i of obstacle q and walks the agent's event list on its own.  Every product and sum is rounded on its
+// own: an update without an event writes the bits of `splines.advance_obstacles`, the stand-alone kernel and the rollout kernel
+// write the same bits.  No barrier inside; lanes >= 32 return at once.
+// ---------------------------------------------------------------------------
+struct ObstacleScriptArgs {
+  const double* time; const int32_t* what; const double* value;      // [B, n_ev] ascending per agent (pads +inf), [B, n_ev], [B, n_ev, 3]
+  int n_ev, n_obst, obst[8][4];                                      // {p_x, p_v, p_a, n_dim}
+  const double* t_abs; int n_t;                                      // the rollout's: absolute time of every step boundary [n_t]
+};
+
+constexpr double kScriptEps = 1e-9;      // (the tolerance of `splines.since_knot`)
+
+__device__ __noinline__ void obstacles_advance_agent(const ObstacleScriptArgs& sc, int b, double* pb, double t_prev, double t_now, double dt,
+                                                     int lane) {
+#pragma clang fp contract(off)
+  const int q = lane >> 2, i = lane & 3;
+  if (lane < 0 || q >= sc.n_obst || q >= 8) return;
+  const int ox = sc.obst[q][0], ov = sc.obst[q][1], oa = sc.obst[q][2], nd = sc.obst[q][3];
+  if (i >= nd) return;
+  double x = pb[ox + i], v = pb[ov + i], a = pb[oa + i];
+  const double* te = sc.time + (size_t)b * sc.n_ev;
+  const int32_t* we = sc.what + (size_t)b * sc.n_ev;
+  const double* ve = sc.value + (size_t)b * sc.n_ev * 3;
+  const double lo = t_prev + kScriptEps, hi = t_now + kScriptEps;
+  double t_cur = t_prev;
+  bool any = false, a_moved = false;
+  for (int e = 0; e < sc.n_ev; ++e) {
+    const double t_e = te[e];
+    if (!(t_e > lo)) continue;      // (behind this update; a NaN is no event)
+    if (t_e > hi) break;            // (ascending: the rest lies ahead)
+    any = true;
+    double h = 0.0, c2 = 0.0;
+    if (t_cur == t_prev && t_now - t_e <= kScriptEps) {      // the event sits on t_now and nothing split the update: the whole-interval statements
+      h = dt; c2 = 0.5 * dt * dt; t_cur = t_now;
+    } else {
+      const double t_to = t_e < t_now ? t_e : t_now;
+      const double hh = t_to - t_cur;
+      if (hh > kScriptEps) { h = hh; c2 = 0.5 * hh * hh; t_cur = t_to; }
+    }
+    if (h > 0.0) {
+      const double m1 = h * v, m2 = c2 * a, m3 = h * a;
+      const double s1 = m1 + m2;
+      x = x + s1;
+      v = v + m3;
+    }
+    const int w = we[e];
+    if (w >= 3 * q && w < 3 * q + 3) {
+      const double val = ve[3 * (size_t)e + i];
+      if (w == 3 * q) x = x + val;
+      else if (w == 3 * q + 1) v = v + val;
+      else { a = a + val; a_moved = true; }
+    }
+  }
+  double h = dt, c2 = 0.5 * dt * dt;
+  if (any) { h = t_now - t_cur; c2 = 0.5 * h * h; }
+  if (!any || h > kScriptEps) {
+    const double m1 = h * v, m2 = c2 * a, m3 = h * a;
+    const double s1 = m1 + m2;
+    x = x + s1;
+    v = v + m3;
+  }
+  pb[ox + i] = x;
+  pb[ov + i] = v;
+  if (a_moved) pb[oa + i] = a;
+}
+
+// stand-alone launch (omgx_batch_obstacles_advance): eight agents share a workgroup, 32 lanes each
+__global__ void __launch_bounds__(256)
+obstacles_advance_kernel(double* __restrict__ p, int n_par, int B, const ObstacleScriptArgs* __restrict__ sc, double t_prev, double t_now, double dt) {
+  const int b = blockIdx.x * 8 + (threadIdx.x >> 5);
+  if (b >= B) return;
+  obstacles_advance_agent(*sc, b, p + (size_t)b * n_par, t_prev, t_now, dt, threadIdx.x & 31);
+}
+
+// ---------------------------------------------------------------------------
 // Rollout: K receding-horizon steps of every agent in ONE launch (omgx_batch_rollout).  Agents of a point-to-point batch
 // are independent, so nothing in the protocol asks for a barrier between the steps of different agents: a persistent
 // workgroup takes an agent and runs its whole loop -- ideal prediction from the current plan, obstacles advanced, the
@@ -1086,11 +1165,14 @@ struct RolloutArgs {
   int32_t* iters_log; int32_t* status_log;     // [K][n_agents] or nullptr
   StopArgs stop; int stop_on;           // omgx_batch_set_stop: an agent's loop ends at the step its state meets the criterion
   const PlantBlock* plant;              // omgx_batch_set_plant: read by the PLANT instance only
+  const ObstacleScriptArgs* script;     // omgx_batch_set_obstacle_script: read by the SCRIPT instances only
 };
 
 // PLANT (omgx_batch_set_plant): step (1) is the plant's predict + stop test on the travelled state, and after the solve the plant's
 // simulate takes the place of the log append; every other statement is the same one.
-template <int MODE, bool WAVE_ONLY, bool GEN, bool PLANT = false>
+// SCRIPT (omgx_batch_set_obstacle_script): step (2) is obstacles_advance_agent between the absolute times of the step; every other
+// statement is the same one.
+template <int MODE, bool WAVE_ONLY, bool GEN, bool PLANT = false, bool SCRIPT = false>
 __global__ void __launch_bounds__(512)
 ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, double* __restrict__ p, double* __restrict__ x,
                    const double* __restrict__ lb, const double* __restrict__ ub, int bounds_shared, double* __restrict__ lam,
@@ -1153,7 +1235,11 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
       }
       // (2) obstacles move on: x <- x + (dt v + dt^2 / 2 a), v <- v + dt a (each product and sum rounded on its own, as the
       //     tensor statements of BatchP2P.step are)
-      for (int q = 0; q < rop->n_obst; ++q) {
+      if constexpr (SCRIPT) {
+        // with a script: the same motion, split at the events of this update (absolute times t_abs[k] .. t_abs[k + 1])
+        const ObstacleScriptArgs* sc = rop->script;
+        obstacles_advance_agent(*sc, b, pb, sc->t_abs[k], sc->t_abs[k + 1], rop->dt, threadIdx.x);
+      } else for (int q = 0; q < rop->n_obst; ++q) {
         const int ox = rop->obst[q][0], ov = rop->obst[q][1], oa = rop->obst[q][2], nd = rop->obst[q][3];
         if ((int)threadIdx.x < nd) {
 #pragma clang fp contract(off)      // (no fused multiply-add here: the tensor statements round every product)
@@ -1374,8 +1460,16 @@ __global__ void admm_comm_kernel(omgx_admm_layout lay, const int32_t* __restrict
 typedef void (*ipm_rollout_t)(omgx::Dims, omgx::Tables, omgx::Opts, int, double*, double*, const double*, const double*, int, double*,
                               int32_t*, int32_t*, int, double*, size_t, double*, int*, const RolloutArgs*, int, const int32_t*, const StoreArgs*);
 // (the classes of the wave path without quartic terms / cos / sin atoms: the receding-horizon classes that fit LDS)
-static ipm_rollout_t rollout_kernel_for(int mode, int wave_ok, int general, int plant = 0) {
+static ipm_rollout_t rollout_kernel_for(int mode, int wave_ok, int general, int plant = 0, int script = 0) {
   if (!wave_ok || general) return nullptr;
+  if (script) {      // (the instances with an obstacle script: the same three modes, with and without the plant)
+    switch (mode) {
+      case omgx::WS_LDS: return plant ? ipm_rollout_kernel<omgx::WS_LDS, true, false, true, true> : ipm_rollout_kernel<omgx::WS_LDS, true, false, false, true>;
+      case omgx::WS_JAC_ONLY: return plant ? ipm_rollout_kernel<omgx::WS_JAC_ONLY, true, false, true, true> : ipm_rollout_kernel<omgx::WS_JAC_ONLY, true, false, false, true>;
+      case omgx::WS_JAC_HV: return plant ? ipm_rollout_kernel<omgx::WS_JAC_HV, true, false, true, true> : ipm_rollout_kernel<omgx::WS_JAC_HV, true, false, false, true>;
+      default: return nullptr;
+    }
+  }
   if (plant) {      // (the plant instances: the same three modes)
     switch (mode) {
       case omgx::WS_LDS: return ipm_rollout_kernel<omgx::WS_LDS, true, false, true>;

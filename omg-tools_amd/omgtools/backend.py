@@ -217,6 +217,12 @@ class CFeedbackSpec(C.Structure):
                 ('sample_time', C.c_double), ('inv_T', C.c_double)]
 
 
+class CObstacleScript(C.Structure):
+    """include/omgx.h omgx_obstacle_script"""
+    _fields_ = [('time', C.c_void_p), ('what', C.c_void_p), ('value', C.c_void_p), ('what_host', C.c_void_p), ('obst', C.c_void_p),
+                ('n_ev', C.c_int32), ('n_obst', C.c_int32)]
+
+
 PREDICT_IDEAL, PREDICT_RK4 = 0, 1
 ONLY_FAILED = 8
 
@@ -340,6 +346,8 @@ PROTOTYPES = {
     'omgx_batch_plant_predict': (C.c_int, [_H, _P, _P, _D, _D, _PLA]),
     'omgx_batch_set_plant': (C.c_int, [_H, _PLA, _SIG]),
     'omgx_batch_predict_measured': (C.c_int, [_H, _P, _P, _D, _D, C.POINTER(CFeedbackSpec)]),
+    'omgx_batch_obstacles_advance': (C.c_int, [_H, _P, C.POINTER(CObstacleScript), _D, _D]),
+    'omgx_batch_set_obstacle_script': (C.c_int, [_H, C.POINTER(CObstacleScript), _P, _I]),
     'omgx_shift_rows': (C.c_int, [_H, _P, _I, _I, _P, _P, _I, _P, _I]),
     'omgx_admm_center': (C.c_int, [_H, _LAY] + [_P] * 3),
     'omgx_admm_update': (C.c_int, [_H, _LAY] + [_P] * 4 + [_D] + [_P] * 4),
@@ -783,6 +791,48 @@ class BatchSolver(object):
                            float(sample_time), float(inv_T))
         _check(self.lib, self.lib.omgx_batch_predict_measured(self._h, x.data_ptr(), p.data_ptr(), float(tau), float(t_value), C.byref(sp)),
                'omgx_batch_predict_measured')
+
+    def _script_spec(self, time, what, value, obstacles, what_host=None):
+        """omgx_obstacle_script from device tensors: time [B, n_ev] fp64, what [B, n_ev] int32, value [B, n_ev, 3] fp64; obstacles:
+        [(p_x, p_v, p_a, n_dim)] the events index; what_host: numpy copy of `what` for the library's range check, or None."""
+        n_ev = int(time.shape[1]) if time is not None and time.dim() == 2 else 0
+        _need('time', time, (self._B, 'n_ev'), 'float64 device')
+        _need('what', what, (self._B, ('n_ev', n_ev)), 'int32 device')
+        _need('value', value, (self._B, ('n_ev', n_ev), 3), 'float64 device')
+        for nm, a in (('time', time), ('what', what), ('value', value)):
+            if not a.is_cuda:      # (a host address would fault the kernel)
+                raise ValueError('%s must be a device tensor' % nm)
+        obst = np.ascontiguousarray(np.array(list(obstacles), dtype=np.int32).reshape(-1, 4))
+        wh = None if what_host is None else np.ascontiguousarray(what_host, dtype=np.int32)
+        if wh is not None and wh.shape != (self.n_agents, n_ev):
+            raise ValueError('what_host must be [n_agents, n_ev]')
+        sp = CObstacleScript(time.data_ptr(), what.data_ptr(), value.data_ptr(), _ptr(wh), obst.ctypes.data if len(obst) else None,
+                             n_ev, len(obst))
+        sp._keep = (time, what, value, wh, obst)
+        return sp
+
+    def obstacles_advance(self, p, script, t_prev, dt):
+        """The obstacles of every agent carried over one update with their script (include/omgx.h omgx_batch_obstacles_advance): one
+        launch; p [B, n_par] device tensor, script: the keyword arguments of `_script_spec`."""
+        _need('p', p, (self._B, self.template.n_par), 'float64 device')
+        if not p.is_cuda:
+            raise ValueError('p must be a device tensor')
+        sp = self._script_spec(**script)
+        _check(self.lib, self.lib.omgx_batch_obstacles_advance(self._h, p.data_ptr(), C.byref(sp), float(t_prev), float(dt)),
+               'omgx_batch_obstacles_advance')
+
+    def set_obstacle_script(self, script=None, t_abs=None):
+        """Every following `rollout` moves the obstacles with this script (include/omgx.h omgx_batch_set_obstacle_script; None: off).
+        t_abs: the absolute time of every step boundary of the rollout, len(tau) + 1 values.  The tensors are kept alive here."""
+        if script is None:
+            self._script = None
+            _check(self.lib, self.lib.omgx_batch_set_obstacle_script(self._h, None, None, 0), 'omgx_batch_set_obstacle_script')
+            return
+        sp = self._script_spec(**script)
+        t_abs = np.ascontiguousarray(t_abs, dtype=np.float64)
+        _check(self.lib, self.lib.omgx_batch_set_obstacle_script(self._h, C.byref(sp), t_abs.ctypes.data, len(t_abs)),
+               'omgx_batch_set_obstacle_script')
+        self._script = sp
 
     def set_plant(self, plant=None, log=None):
         """Every following `rollout` runs with the plant in the loop (include/omgx.h omgx_batch_set_plant; plant=None: off).  The

@@ -10,7 +10,7 @@ with a primal-dual warm start.
 Layout: `BatchP2P` states that protocol once -- tables and options from the template, `solve_cold`, `step`, `rollout`, the stop rule,
 the log -- and branches on no executor.  Where the [B, *] arrays live and who computes on them sits behind its hooks (`_allocate,
 _predict, _shift, _solve, _cold, _rollout, _norm, _stop_rule, _signals_alloc, _signals_fused, _signals_append_now,
-_signals_summary, _plant_alloc, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
+_signals_summary, _plant_alloc, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
 being the allocator / stream only; no data leaves HBM between steps) and `HostP2P` (`ops=<a host solver object>`: the same
 statements in numpy, how the parity tests and the CPU baseline of bench.py replay the loop; this package never imports the
 oracle).  `BatchP2P(problem, P, ops=...)` hands out the executor `ops` names.  The clock of a step is `splines.step_clock`, the
@@ -21,12 +21,14 @@ optional input disturbance): step (1) then starts the solve from the state the v
 inputs, and after step (3) the vehicle travels the update under the applied inputs (include/omgx.h OMGX_HAS_PLANT has the statements).
 `BatchP2P.feedback` lets `step` take states measured outside the loop instead (`step(states=...)`, the reference's
 `Deployer.update(current_time, states, ...)`; include/omgx.h OMGX_HAS_FEEDBACK): a loop has one source of states.
+`BatchP2P.obstacle_script` moves the obstacles by the reference's `simulation={'trajectories': ...}` -- jumps of position, velocity
+or acceleration at given times (include/omgx.h OMGX_HAS_OBSTACLE_SCRIPT; `splines.advance_obstacles_scripted` in numpy).
 """
 import os
 
 import numpy as np
 
-from .splines import advance_obstacles, shiftoverknot_T, step_clock
+from .splines import SCRIPT_EPS, advance_obstacles, advance_obstacles_scripted, shiftoverknot_T, step_clock
 
 
 # solver options of a knot-crossing step (BatchP2P `cross_options`)
@@ -48,6 +50,26 @@ def input_disturbance(B, n_in, n_updates, n_samp, n_horizon, fc, stdev, mean=Non
     noise = rng.normal(mean[None, :, None, None], stdev[None, :, None, None], (int(B), int(n_in), int(n_updates), int(n_horizon)))
     num, den = butter(3, fc, 'low')
     return np.ascontiguousarray(filtfilt(num, den, noise, axis=-1)[..., :int(n_samp) + 1])
+
+
+_SCRIPT_KINDS = ('position', 'velocity', 'acceleration')
+SCRIPT_MAX_EVENTS, SCRIPT_MAX_OBSTACLES = 32, 8      # (include/omgx.h omgx_obstacle_script)
+
+
+def random_obstacle_script(B, n_obst, n_dim, n_events, t_max, scale, seed=0, grid=0.1):
+    """A seeded realisation of per-agent obstacle scripts for `BatchP2P.obstacle_script(events=...)`, for tests and studies (the
+    counterpart of `input_disturbance`): dict `time` [B, n_events] (uniform in (0, t_max], ascending per agent; every second event
+    of an agent is moved onto the next multiple of `grid` -- the update grid of a loop with that update time -- so that on-grid and
+    off-grid events both occur), `obstacle` [B, n_events] (0 .. n_obst - 1), `kind` [B, n_events] (0 / 1 / 2 = position / velocity /
+    acceleration) and `value` [B, n_events, n_dim] (normal, standard deviation `scale`).  The same arrays for the same arguments."""
+    rng = np.random.default_rng(seed)
+    B, E = int(B), int(n_events)
+    time = rng.uniform(0.0, float(t_max), (B, E))
+    on_grid = np.ceil(time / grid) * grid
+    time[:, 1::2] = np.minimum(on_grid, np.floor(float(t_max) / grid + 1e-9) * grid)[:, 1::2]
+    time = np.sort(np.maximum(time, 1e-3), axis=1)
+    return dict(time=time, obstacle=rng.integers(0, int(n_obst), (B, E)).astype(np.int32), kind=rng.integers(0, 3, (B, E)).astype(np.int32),
+                value=np.ascontiguousarray(rng.normal(0.0, float(scale), (B, E, int(n_dim)))))
 
 
 def dual_shift_perm(father, extrapolate=True):
@@ -141,6 +163,7 @@ class BatchP2P(object):
         self._sig = None                                  # (record_signals)
         self._pl = None                                   # (plant)
         self._fb = None                                   # (feedback)
+        self._sc = None                                   # (obstacle_script)
         self._plan_ready = False                          # (solve_cold has run: x holds a plan)
         # (warm_mu_factor 0.1: a step starts at the barrier parameter the previous solve of the agent ended with, tol / 10,
         # unless the shifted point is far off that central path -- a tenth of its average complementarity then: at tol 1e-3
@@ -218,7 +241,7 @@ class BatchP2P(object):
             self._predict(tau, t_rel)
         else:
             self._plant_predict(tau, t_rel)
-        advance_obstacles(self.p, self.obst, self.update_time)      # (a no-op for static obstacles)
+        self._advance_obstacles(self.time, t_now)            # (a no-op for static obstacles)
         if crossed:
             self._shift()
         self.time = t_now
@@ -238,16 +261,101 @@ class BatchP2P(object):
         travelled state, input disturbance, stop test on the travelled state: a disturbance study of a whole fleet in one launch.  A
         deployment that feeds states measured outside back steps with `step` (`feedback`, `step(states=...)`): a rollout takes none.
         Returns the number of knot crossings."""
-        clock, t = [], self.time
+        clock, t, t_abs = [], self.time, [self.time]
         for _ in range(int(n_steps)):
             t, tau, t_rel, crossed = step_clock(t, self.update_time, self.knot_time, self.T)
             clock.append((tau, t_rel, crossed))
-        self._rollout(*([c[k] for c in clock] for k in range(3)), iters_log=iters_log, status_log=status_log)
+            t_abs.append(t)
+        self._rollout(*([c[k] for c in clock] for k in range(3)), iters_log=iters_log, status_log=status_log, t_abs=t_abs)
         self.time = t
         return int(sum(c[2] for c in clock))
 
-    def _rollout(self, tau, t_rel, crossed, iters_log, status_log):
+    def _rollout(self, tau, t_rel, crossed, iters_log, status_log, t_abs=None):
         raise NotImplementedError('rollout is a device launch')
+
+    # -- obstacle scripts ----------------------------------------------------------------------------
+    def _advance_obstacles(self, t_prev, t_now):
+        """Part of `step`: the obstacles move from t_prev to t_now -- constant acceleration, and with a script (`obstacle_script`) its
+        jumps."""
+        if self._sc is None:
+            advance_obstacles(self.p, self.obst, self.update_time)
+        else:
+            self._script_advance(t_prev, t_now)
+
+    def obstacle_script(self, events=None, on=True):
+        """Move the obstacles as the reference's `simulation={'trajectories': {...}}` does (`environment/obstacle.py:172-264`): at given
+        times a value is added to an obstacle's position, velocity or acceleration, between these jumps it moves with constant
+        acceleration.  From now on every `step` and every step inside a `rollout` launch carries the obstacles over its update with
+        these events (include/omgx.h OMGX_HAS_OBSTACLE_SCRIPT has the statement: exact for the model, split at the event times, no
+        sample grid); an update without an event is the plain motion, bit for bit.
+        events=None: the script of the problem's own obstacles (`obstacle.simulation['trajectories']`), the same for every agent; a
+        problem loaded from a bundle carries none.  Otherwise a dict of per-agent scripts: `time` [B, E] (absolute loop time, as
+        `self.time`; +inf: no event), `obstacle` [B, E] (index into `problem.environment.obstacles`), `kind` [B, E] (0 / 1 / 2 =
+        position / velocity / acceleration), `value` [B, E, n_dim].  Events are sorted per agent (events at one time keep their
+        order) and padded.  Refused: an event at or before the current time (the reference folds an event at time 0 into the initial
+        state: put it into `P`), more than 32 events of an agent, more than 8 moving obstacles.  Every obstacle an event names joins
+        the moving obstacles, even when its v and a are zero in `P`.  Not modelled: `bounce`, a custom `simulation['model']`, obstacle
+        `input` trajectories.
+        Stopped agents: `step` advances every agent's obstacles, stopped or not; inside a `rollout` launch an agent's obstacles move
+        only while its loop runs.  on=False: the plain motion again (obstacles an event has set moving keep moving)."""
+        if not on:
+            self._sc = None
+            return
+        if getattr(self, 'pool', None) is not None:
+            raise NotImplementedError('obstacle_script: not with a host pool (its workers run the step glue themselves)')
+        obstacles = self.problem.environment.obstacles
+        if events is None:
+            rows = []
+            for q, obs in enumerate(obstacles):
+                sim = getattr(obs, 'simulation', None)
+                if sim is None:
+                    raise ValueError('obstacle_script: this problem comes from a bundle, its obstacles carry no simulation: pass events=')
+                if 'model' in sim or 'input' in sim.get('trajectories', {}):
+                    raise NotImplementedError("obstacle_script: a custom simulation['model'] / an 'input' trajectory is not moved in the batched loop")
+                for kind, traj in sim.get('trajectories', {}).items():
+                    if len(traj['time']) != len(traj['values']):
+                        raise ValueError('Dimension mismatch between time array and values for ' + kind + ' trajectory.')
+                    rows += [(float(tau), q, _SCRIPT_KINDS.index(kind), np.asarray(val, dtype=float)) for tau, val in zip(traj['time'], traj['values'])
+                             if tau != 0]
+            if not rows:
+                raise ValueError('obstacle_script: no obstacle of the problem has a trajectory: pass events=')
+            events = dict(time=np.tile([r[0] for r in rows], (self.B, 1)), obstacle=np.tile([r[1] for r in rows], (self.B, 1)),
+                          kind=np.tile([r[2] for r in rows], (self.B, 1)), value=np.zeros((self.B, len(rows), 3)))
+            for e, r in enumerate(rows):
+                events['value'][:, e, :len(r[3])] = r[3]
+        time = np.array(events['time'], dtype=float)
+        which, kind, val = np.array(events['obstacle'], dtype=np.int64), np.array(events['kind'], dtype=np.int64), np.asarray(events['value'], dtype=float)
+        if time.ndim != 2 or time.shape[0] != self.B or which.shape != time.shape or kind.shape != time.shape or val.shape[:2] != time.shape or \
+                val.ndim != 3 or val.shape[2] > 3:
+            raise ValueError('obstacle_script: events must be time / obstacle / kind [B, E] and value [B, E, n_dim] with B = %d' % self.B)
+        live = time < np.inf
+        if np.isnan(time).any() or (live & (time <= self.time + SCRIPT_EPS)).any():
+            raise ValueError('obstacle_script: an event at or before the current time %g (an event at the start belongs into P)' % self.time)
+        if live.sum(axis=1).max(initial=0) > SCRIPT_MAX_EVENTS:
+            raise ValueError('obstacle_script: %d events of one agent, at most %d' % (live.sum(axis=1).max(), SCRIPT_MAX_EVENTS))
+        if not live.any():
+            raise ValueError('obstacle_script: no event')
+        if (which[live] < 0).any() or (which[live] >= len(obstacles)).any() or (kind[live] < 0).any() or (kind[live] > 2).any():
+            raise ValueError('obstacle_script: obstacle outside 0 .. %d or kind outside 0 .. 2' % (len(obstacles) - 1))
+        obst, slot = list(self.obst), {}
+        for q in sorted(set(which[live].tolist())):
+            ox, ov, oa = (self.tpl.entry_range(obstacles[q].label, nm, 'par') for nm in ('x', 'v', 'a'))
+            entry = (ox[0], ov[0], oa[0], ox[1] - ox[0])
+            if entry not in obst:
+                obst.append(entry)
+            slot[q] = obst.index(entry)
+        if len(obst) > SCRIPT_MAX_OBSTACLES:
+            raise ValueError('obstacle_script: %d moving obstacles, at most %d' % (len(obst), SCRIPT_MAX_OBSTACLES))
+        E = max(1, int(live.sum(axis=1).max()))
+        order = np.argsort(time, axis=1, kind='stable')[:, :E]
+        take = lambda a: np.take_along_axis(a, order, axis=1)
+        time, live = take(time), take(live)
+        what = np.where(live, np.vectorize(lambda q: slot.get(q, 0))(take(which)) * 3 + take(kind), 0).astype(np.int32)
+        value = np.zeros((self.B, E, 3))
+        value[:, :, :val.shape[2]] = np.take_along_axis(val, order[:, :, None], axis=1)
+        value[~live] = 0.0
+        self.obst = obst
+        self._sc = self._script_alloc(np.ascontiguousarray(time), np.ascontiguousarray(what), value)
 
     def _eval_rows(self, tau):
         """[E_0, E_1, ...]: c @ E_o = o-th time derivative of the plan at tau."""
@@ -546,8 +654,24 @@ class DeviceP2P(BatchP2P):
             passes += 1
         return passes
 
-    def _rollout(self, tau, t_rel, crossed, iters_log, status_log):
+    def _script_alloc(self, time, what, value):
+        t = self.torch
+        return dict(time=t.as_tensor(time, dtype=t.float64).to(self.dev), what=t.as_tensor(what, dtype=t.int32).to(self.dev),
+                    value=t.as_tensor(value, dtype=t.float64).to(self.dev), what_host=what)
+
+    def _script_args(self):
+        return dict(self._sc, obstacles=self.obst)
+
+    def _script_advance(self, t_prev, t_now):
+        """One launch in place of the tensor statements (the library forms t_now = t_prev + update_time as `step_clock` does)."""
+        self.solver.obstacles_advance(self.p, self._script_args(), t_prev, self.update_time)
+
+    def _rollout(self, tau, t_rel, crossed, iters_log, status_log, t_abs=None):
         self._plant_rollout()
+        # (the script with the absolute times of this step list, registered with the handle; taken off without one)
+        if self._sc is not None or getattr(self, '_sc_registered', False):
+            self.solver.set_obstacle_script(None if self._sc is None else self._script_args(), t_abs)
+            self._sc_registered = self._sc is not None
         self.solver.set_options(warm_start=1, max_iter=self.max_iter_step, **self._base_extra)
         if self.straggler_first:
             self.solver.order_by_iters(self.iters, self._order)
@@ -846,6 +970,12 @@ class HostP2P(BatchP2P):
     def _plant_rollout(self):
         pass
 
+    def _script_alloc(self, time, what, value):
+        return dict(time=time, what=what, value=value)
+
+    def _script_advance(self, t_prev, t_now):
+        advance_obstacles_scripted(self.p, self.obst, self._sc, t_prev, t_now, dt=self.update_time)
+
     def _feedback_predict(self, tau, t_rel, states, inputs, fresh, enforce):
         """`omgx_batch_predict_measured` in numpy: an agent without a fresh measurement as `_predict`, one with as `_plant_predict`
         with the measured state in the place of `state_prev` (the same statements: the same bits), or the given values (enforce)."""
@@ -1024,6 +1154,12 @@ class StreamedP2P(object):
         """`BatchP2P.feedback` for every sub-batch; `step(states=...)` then hands each its rows."""
         for m in self.parts:
             m.feedback(sample_time, on)
+
+    def obstacle_script(self, events=None, on=True):
+        """`BatchP2P.obstacle_script` for every sub-batch, each with its rows of the events."""
+        for (lo, hi), m, st in zip(self.bounds, self.parts, self.streams):
+            with self.torch.cuda.stream(st):
+                m.obstacle_script(None if events is None else dict((k, np.asarray(v)[lo:hi]) for k, v in events.items()), on)
 
     def plant_state(self):
         """`BatchP2P.plant_state` of the whole batch, joined and concatenated like `signals`."""

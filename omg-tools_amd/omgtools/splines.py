@@ -410,6 +410,59 @@ def advance_obstacles(p, obst, dt):
         pv += dt * pa
 
 
+SCRIPT_EPS = 1e-9      # (an event within it of an update's end belongs to that update: the tolerance of `since_knot`)
+
+
+def advance_obstacles_scripted(p, obst, script, t_prev, t_now, dt=None):
+    """`advance_obstacles` from t_prev to t_now with an obstacle script (include/omgx.h OMGX_HAS_OBSTACLE_SCRIPT has the statement;
+    the reference's `simulation={'trajectories': ...}`, `environment/obstacle.py:172-264`): script = dict `time` [B, E] (absolute,
+    ascending per agent, pads +inf), `what` [B, E] (3 * index into `obst` + kind, kind 0 / 1 / 2 = position / velocity /
+    acceleration), `value` [B, E, 3].  p [B, *] numpy, in place, row by row.  An event belongs to the update if
+    t_prev + 1e-9 < time <= t_now + 1e-9; a row without one gets the statements of `advance_obstacles` with `dt` (None: t_now -
+    t_prev; a loop passes its update time, so that an update without an event keeps the bits of the plain loop); otherwise the
+    motion is split at the events, in table order, and each adds its value to its kind.  An event on t_now (within 1e-9) that
+    nothing precedes in the update sees the whole-interval statements with `dt` itself.  The device routine
+    `obstacles_advance_agent` makes the same roundings in the same order."""
+    dt = t_now - t_prev if dt is None else dt
+    time, what, value = np.asarray(script['time']), np.asarray(script['what']), np.asarray(script['value'])
+    lo, hi = t_prev + SCRIPT_EPS, t_now + SCRIPT_EPS
+
+    def move(row, h, c2):
+        for ox, ov, oa, nd in obst:
+            px, pv, pa = row[ox:ox + nd], row[ov:ov + nd], row[oa:oa + nd]
+            px += h * pv + c2 * pa
+            pv += h * pa
+
+    for b in range(p.shape[0]):
+        row, t_cur, any_event = p[b], t_prev, False
+        for e in range(time.shape[1]):
+            t_e = float(time[b, e])
+            if not t_e > lo:
+                continue
+            if t_e > hi:
+                break
+            any_event = True
+            if t_cur == t_prev and t_now - t_e <= SCRIPT_EPS:
+                move(row, dt, 0.5 * dt * dt)
+                t_cur = t_now
+            else:
+                t_to = t_e if t_e < t_now else t_now
+                h = t_to - t_cur
+                if h > SCRIPT_EPS:
+                    move(row, h, 0.5 * h * h)
+                    t_cur = t_to
+            q, kind = divmod(int(what[b, e]), 3)
+            if 0 <= q < len(obst):
+                off, nd = obst[q][kind], obst[q][3]
+                row[off:off + nd] += value[b, e, :nd]
+        if not any_event:
+            move(row, dt, 0.5 * dt * dt)
+        else:
+            h = t_now - t_cur
+            if h > SCRIPT_EPS:
+                move(row, h, 0.5 * h * h)
+
+
 def shiftoverknot_T(basis):
     """Warm-start matrix when the horizon start passes the first interior knot:
     the new coefficients describe s(tau + delta) on the same (uniform) knot
