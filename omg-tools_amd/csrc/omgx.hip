@@ -440,6 +440,7 @@ int build_batch(omgx_batch* b, const omgx_template* t) {
   UP(cpl_ptr, d.n_leaf + 1); UP(cpl_idx, plan.cpl_idx.size()); UP(cpl_map, plan.cpl_map.size());
   UP(d_off, d.n_leaf + 1); UP(b_off, plan.b_off.size());
   UP(lf_w, plan.lf_w.size()); UP(lf_ldb, plan.lf_ldb.size()); UP(lf_band, plan.lf_band.size()); UP(lf_kind, plan.lf_kind.size()); UP(dl_pos, plan.dl_pos.size());
+  UP(bmat_img, plan.bmat_img.size());
   UP(pair4, plan.pair4.size()); UP(eqe3, plan.eqe3.size());
   UP(je_row, plan.je_row.size()); UP(diag_addr, d.N); UP(tq_addr, plan.tq_addr.size());
   UP(reg_w, d.N); UP(je_rp, plan.je_rp.size());
@@ -939,11 +940,13 @@ int omgx_batch_solve(omgx_batch* b, const double* p, const double* x0, const dou
   const Instances& in = b->inst;
   b->last_instance = lean_launch && in.lean ? 1 : 0;      // (classes without a lean instance -- general, off the wave path, spill modes -- run the full one)
   const ipm_kernel_t kern = b->last_instance ? in.lean : (b->opts.refine && in.refine ? in.refine : in.full);
+  // (the slot queue only where it decides something: with a workgroup per agent every fetch would return a slot past the end)
+  int* const k_next = b->n_slabs >= B ? nullptr : b->d_next;
   hipExtLaunchKernelGGL(kern, dim3(b->n_slabs), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream,
                         e0, e1, 0u, d, b->dev,
                         b->opts, b->kkt_doubles, kp, kx0, klb, kub, shared ? 1 : 0, kx, klam, kst, kit, B, b->d_prof,
                         b->d_slabs, b->slab_doubles, b->d_dw, b->d_order, k_stp, k_only_failed,
-                        b->d_next, b->d_x0_alt, k_n_alt, b->d_attempts,
+                        k_next, b->d_x0_alt, k_n_alt, b->d_attempts,
                         (unsigned long long*)(b->d_stats ? b->d_stats + 4 * (size_t)(b->stats_launch++ % b->stats_slots) : nullptr),
                         b->stagger, k_ctr, k_prep, b->prep_doubles, k_stop);
   HIPCHK(hipGetLastError());
@@ -1528,7 +1531,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   b->timed = false;
   hipExtLaunchKernelGGL(kern, dim3(b->n_slabs < b->n_agents ? b->n_slabs : b->n_agents), dim3(b->threads), (uint32_t)b->lds_bytes, b->stream, e0, e1, 0u,
                         d, b->dev, b->opts, b->kkt_doubles, p, x, lbg, ubg, shared ? 1 : 0, lam_g, status, iters, b->n_agents,
-                        b->d_slabs, b->slab_doubles, b->d_dw, b->d_next, (const RolloutArgs*)b->d_rollout, b->stagger, b->d_order,
+                        b->d_slabs, b->slab_doubles, b->d_dw, b->n_slabs >= b->n_agents ? nullptr : b->d_next, (const RolloutArgs*)b->d_rollout, b->stagger, b->d_order,
                         (const StoreArgs*)((b->store.out || b->signals.log) ? &b->d_store->st : nullptr));
   HIPCHK(hipGetLastError());
   return OMGX_OK;

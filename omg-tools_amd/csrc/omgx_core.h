@@ -25,9 +25,11 @@
 #ifdef OMGX_HOST_PORT
 #define OMGX_FN inline
 #define OMGX_HD inline
+#define OMGX_HDF inline
 #else
 #define OMGX_FN __device__ __forceinline__
 #define OMGX_HD __host__ __device__ inline
+#define OMGX_HDF __host__ __device__ __forceinline__      // OMGX_FN that the plan (host code of the library) may call too
 #endif
 
 #ifdef OMGX_HOST_PORT
@@ -112,6 +114,7 @@ struct Tables {   // read-only, shared by all agents (global memory)
   // leaf: the number of coupling slots S), the row stride and width of its band, its kind (0 banded panel, 1 sparse
   // diagonal leaf); dl_pos[4 * leaf_off[l] + s * n_l + j]: root position coupled through slot s of variable j (-1: none)
   const int32_t* lf_w; const int32_t* lf_ldb; const int32_t* lf_band; const int32_t* lf_kind; const int32_t* dl_pos;
+  const int32_t* bmat_img;  // compact store only: the matrix descriptors of a solve, [n_leaf + 1] BMat as the plan filled them (kkt_describe_fill)
   // precomputed KKT addresses (HostPlan): Jacobian pairs, t-column, diagonal, Hessian terms
   const int32_t* eqe3;      // [n_eqe][3] = {Jacobian entry, KKT address, row} of the equality-row entries
   const int32_t* pair4;     // [n_pairs][4] = {Jacobian entry a, entry b, KKT address, row}: one 16-byte record per pair
@@ -485,7 +488,9 @@ typedef CtxT<false> Ctx;
 enum { PH_JAC = 0, PH_RESID, PH_ASSEMBLE, PH_FACTOR, PH_SOLVE, PH_STEP, PH_LINESEARCH, PH_UPDATE, PH_F_LEAF, PH_F_SCHUR, PH_F_ROOT, PH_LA, PH_LS, PH_LB, PH_SETUP, PH_TOTAL,
        PH_S_DESC, PH_S_PARAMS, PH_S_JAC0, PH_S_CLASS, PH_S_INIT, PH_A_ZERO, PH_A_PAIRS, PH_A_REST, PH_A_DIAG,
        PH_K_FWD, PH_K_ROOTRHS, PH_K_ROOT, PH_K_LEAFRHS, PH_K_BWD, PH_L_TERMS, PH_L_ROWS,
-       PH_F_PARK, PH_F_SWEEP, PH_F_SCALE, PH_A_TCOL, PH_A_HESS, PH_P_LOAD, PH_P_DIV, PH_P_BSPL, PH_P_SLOTS, PH_COUNT };
+       PH_F_PARK, PH_F_SWEEP, PH_F_SCALE, PH_A_TCOL, PH_A_HESS, PH_P_LOAD, PH_P_DIV, PH_P_BSPL, PH_P_SLOTS,
+       PH_WG_HEAD, PH_WG_TAIL,      // outside PH_TOTAL: kernel entry (or the workgroup's previous solve) to the start of a solve; its last solve to its exit
+       PH_COUNT };
 #if defined(OMGX_PROFILE) && !defined(OMGX_HOST_PORT)
 #define OMGX_TIC() long long tic_ = (c.sync(), clock64())
 #define OMGX_TOC(k) do { c.sync(); long long now_ = clock64(); if (c.tid() == 0 && c.prof) c.prof[k] += now_ - tic_; tic_ = now_; } while (0)
@@ -857,7 +862,7 @@ struct Kkt {
   const int32_t *d_off, *b_off, *leaf_off, *leaf_bw, *cpl_ptr, *cpl_idx, *blk, *cpl_map, *lf_w, *lf_ldb, *lf_band, *lf_kind, *dl_pos;
   int n_leaf, n_root, root_off;
   double* a;
-  OMGX_FN void bind(const Dims& dd, const Tables& TT, double* store) {
+  OMGX_HDF void bind(const Dims& dd, const Tables& TT, double* store) {
     d_off = TT.d_off; b_off = TT.b_off; leaf_off = TT.leaf_off; leaf_bw = TT.leaf_bw; cpl_ptr = TT.cpl_ptr;
     cpl_idx = TT.cpl_idx; blk = TT.blk; cpl_map = TT.cpl_map;
     lf_w = TT.lf_w; lf_ldb = TT.lf_ldb; lf_band = TT.lf_band; lf_kind = TT.lf_kind; dl_pos = TT.dl_pos;
@@ -869,10 +874,10 @@ struct Kkt {
   // row-major, nr rows + one more for its right-hand side.  The right-hand sides are carried through
   // the factorisation like coupling rows, so the forward substitutions L^{-1} r come out of it.
   OMGX_FN double* P(int l) const { return a + d_off[l]; }
-  OMGX_FN int ld(int l) const { return b_off[l]; }
+  OMGX_HDF int ld(int l) const { return b_off[l]; }
   OMGX_FN double* R() const { return a + d_off[n_leaf]; }
-  OMGX_FN int nl(int l) const { return leaf_off[l + 1] - leaf_off[l]; }
-  OMGX_FN int nc(int l) const { return cpl_ptr[l + 1] - cpl_ptr[l]; }
+  OMGX_HDF int nl(int l) const { return leaf_off[l + 1] - leaf_off[l]; }
+  OMGX_HDF int nc(int l) const { return cpl_ptr[l + 1] - cpl_ptr[l]; }
 };
 
 // ---------------------------------------------------------------------------
@@ -1320,37 +1325,57 @@ OMGX_FN void ldl_blocked(const C& c, const BMat* Ms, int nm, double* A, double* 
   *bad = c.rmax(badl ? 1.0 : 0.0) > 0.0 ? 1 : 0;
 }
 
-// Matrix descriptors of the block-arrow store: written once per solve at the head of w.col (shared
-// by the workgroup; the plan tables they come from are global memory, i.e. a chain of dependent
-// loads per look-up), followed by the staging area and the panel buffers.
+// Matrix descriptors of the block-arrow store, at the head of w.col (shared by the workgroup), followed by the staging area
+// and the panel buffers.  kkt_describe_fill is the one definition of their fields: a kernel runs it per workgroup
+// (kkt_describe: the plan tables it reads are global memory, i.e. a chain of dependent loads per look-up), the plan runs it
+// once per template for the instances on the wave path, whose descriptors depend on the template alone (HostPlan::bmat_img,
+// Tables::bmat_img) and are then copied (kkt_descriptors).
+template <bool WAVE_ONLY, bool HBM, bool ROOT_LDS>
+OMGX_HDF void kkt_describe_fill(const Dims& d, const Kkt& K, BMat* Ms) {
+  const int pan0 = (OMGX_BMAT_DOUBLES + OMGX_STAGE_LD) * (OMGX_MAX_LEAF + 1);      // (offset of the panel buffers in w.col)
+  int pan = pan0;
+  for (int l = 0; l < d.n_leaf; ++l) {
+    BMat& M = Ms[l];
+    if constexpr (WAVE_ONLY) {
+      // compact store: a = band of the leaf block (sparse diagonal leaf: its arrays), pan = its carried rows
+      // (sparse: number of coupling slots), pad_ = row stride of the band, bw = stored band (-1: sparse leaf)
+      M.a = K.d_off[l]; M.ld = K.ld(l); M.nfact = K.nl(l); M.rows = K.nl(l) + K.nc(l) + 1; M.npos = M.nfact;
+      M.dinv = K.leaf_off[l]; M.pan = K.lf_w[l]; M.cpl = K.cpl_ptr[l]; M.bw = K.lf_kind[l] ? -1 : K.lf_band[l]; M.pad_ = K.lf_ldb[l];
+      continue;
+    }
+    M.a = K.d_off[l]; M.ld = K.ld(l); M.nfact = K.nl(l); M.rows = K.nl(l) + K.nc(l) + 1; M.npos = M.nfact;   // + the rhs row
+    M.dinv = K.leaf_off[l]; M.pan = pan; pan += HBM ? OMGX_PAN_SMALL(M.nfact) : OMGX_PAN_LD * M.rows; M.cpl = K.cpl_ptr[l]; M.bw = K.leaf_bw[l];
+  }
+  BMat& Mr = Ms[d.n_leaf];
+  Mr.a = ROOT_LDS ? 0 : K.d_off[d.n_leaf]; Mr.ld = 0; Mr.nfact = d.nr; Mr.rows = d.nr + 1; Mr.npos = d.n_root; Mr.dinv = -1; Mr.pan = pan0; Mr.cpl = 0; Mr.bw = d.nr;
+  Mr.pad_ = K.d_off[d.n_leaf];      // where the assembly writes the root block (Mr.a: where the factorisation reads it)
+}
+
 template <class C>
 OMGX_FN void kkt_describe(const C& c, const Dims& d, const Kkt& K, Work& w, bool sync_after = true) {
   // (one thread, a chain of table loads: the first thread of the SECOND wave, so that a caller whose next stage is serial work
   // of thread 0 -- the parameter program -- can let the two chains run side by side: sync_after = false, the barriers of
   // that stage make the descriptors visible)
   const int who = c.nthr() > 64 ? 64 : 0;
-  BMat* Ms = (BMat*)w.col;
-  double* stage = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1);
-  const int pan0 = (int)(stage + OMGX_STAGE_LD * (OMGX_MAX_LEAF + 1) - w.col);
-  if (c.tid() == who) {
-    int pan = pan0;
-    for (int l = 0; l < d.n_leaf; ++l) {
-      BMat& M = Ms[l];
-      if constexpr (C::wave_only) {
-        // compact store: a = band of the leaf block (sparse diagonal leaf: its arrays), pan = its carried rows
-        // (sparse: number of coupling slots), pad_ = row stride of the band, bw = stored band (-1: sparse leaf)
-        M.a = K.d_off[l]; M.ld = K.ld(l); M.nfact = K.nl(l); M.rows = K.nl(l) + K.nc(l) + 1; M.npos = M.nfact;
-        M.dinv = K.leaf_off[l]; M.pan = K.lf_w[l]; M.cpl = K.cpl_ptr[l]; M.bw = K.lf_kind[l] ? -1 : K.lf_band[l]; M.pad_ = K.lf_ldb[l];
-        continue;
-      }
-      M.a = K.d_off[l]; M.ld = K.ld(l); M.nfact = K.nl(l); M.rows = K.nl(l) + K.nc(l) + 1; M.npos = M.nfact;   // + the rhs row
-      M.dinv = K.leaf_off[l]; M.pan = pan; pan += C::hbm ? OMGX_PAN_SMALL(M.nfact) : OMGX_PAN_LD * M.rows; M.cpl = K.cpl_ptr[l]; M.bw = K.leaf_bw[l];
-    }
-    BMat& Mr = Ms[d.n_leaf];
-    Mr.a = C::root_lds ? 0 : K.d_off[d.n_leaf]; Mr.ld = 0; Mr.nfact = d.nr; Mr.rows = d.nr + 1; Mr.npos = d.n_root; Mr.dinv = -1; Mr.pan = pan0; Mr.cpl = 0; Mr.bw = d.nr;
-    Mr.pad_ = K.d_off[d.n_leaf];      // where the assembly writes the root block (Mr.a: where the factorisation reads it)
-  }
+  if (c.tid() == who) kkt_describe_fill<C::wave_only, C::hbm, C::root_lds>(d, K, (BMat*)w.col);
   if (sync_after) c.sync();
+}
+
+// The descriptors of a solve: on the wave path the image the plan made, (n_leaf + 1) descriptors of 10 ints copied by the second
+// wave with coalesced loads (one round trip instead of a chain of them; the second wave for kkt_describe's reason);
+// kkt_describe for every other instance.
+template <class C>
+OMGX_FN void kkt_descriptors(const C& c, const Dims& d, const Tables& T, Work& w, bool sync_after = true) {
+  if constexpr (C::wave_only) {
+    const int t0 = c.nthr() > 64 ? 64 : 0, nt = c.nthr() > 64 ? 64 : c.nthr();
+    const int i0 = c.tid() - t0, n = (d.n_leaf + 1) * (int)(sizeof(BMat) / sizeof(int32_t));
+    int32_t* Ms = (int32_t*)w.col;
+    if (i0 >= 0 && i0 < nt) for (int i = i0; i < n; i += nt) Ms[i] = T.bmat_img[i];
+    if (sync_after) c.sync();
+  } else {
+    Kkt K; K.bind(d, T, w.kkt);
+    kkt_describe(c, d, K, w, sync_after);
+  }
 }
 
 #ifndef OMGX_HOST_PORT
@@ -2255,10 +2280,7 @@ OMGX_FN Start ipm_setup(const C& c, const Dims& d, const Tables& T, const Opts& 
   OMGX_TIC();
   if constexpr (!C::prep) {
     // (describe = false: the caller wrote the matrix descriptors -- the same for every agent -- once for its workgroup)
-    if (describe) {
-      Kkt K; K.bind(d, T, w.kkt);
-      kkt_describe(c, d, K, w, false);      // (beside the parameter program of eval_params, whose barriers publish it)
-    }
+    if (describe) kkt_descriptors(c, d, T, w, false);      // (beside the parameter program of eval_params, whose barriers publish it)
   }
 
   // the per-agent inputs come from HBM (~1 us each if loaded where they are first needed): all of
@@ -3287,8 +3309,7 @@ template <class C>
 OMGX_FN void ipm_eval(const C& c, const Dims& d, const Tables& T, Work& w, const double* p, const double* x,
                       const double* lam, int kkt_doubles, double* f_out) {
   const int n = d.n_var, m = d.n_con;
-  Kkt K; K.bind(d, T, w.kkt);
-  kkt_describe(c, d, K, w);
+  kkt_descriptors(c, d, T, w);
   OMGX_PFOR(i, n) w.x[i] = x[i];
   if (c.tid() == 0) w.x[n] = 0.0;
   eval_params(c, d, T, w, p);

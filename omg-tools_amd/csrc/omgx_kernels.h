@@ -259,6 +259,25 @@ signals_reduce_kernel(const double* __restrict__ log, const int32_t* __restrict_
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
+// The slot queue of the persistent kernels: next_slot[0] counts the slots handed out, next_slot[1] the workgroups that have left;
+// both are zero at every launch because the workgroup that leaves last resets them.  Called by thread 0 behind its last solve.
+// No fence on either side of it:
+//  * nothing a workgroup has stored (x, lam, status, iters, dw_state, its slab, the statistics) is read by another workgroup of
+//    the same launch; later launches read it behind the kernel boundary, which writes the caches back.  A __threadfence() here is
+//    a write-back of the whole L2 of the compute die plus an L1 invalidate, once per workgroup: with one agent per workgroup, once
+//    per solve, right after the solve has dirtied its Jacobian slab.
+//  * the counters are only ever touched by device-scope atomics, the reset included (exchanges, not plain stores: they are
+//    performed where the next launch's adds are performed, whatever a cache still holds).  Thread 0 has consumed the value of
+//    its last atomicAdd(next_slot) -- it wrote it to LDS and passed a barrier -- before it adds to next_slot[1], so an add that
+//    has returned has been performed.  The workgroup that reads gridDim.x - 1 therefore resets a queue no add is in flight on:
+//    every other thread 0 made its last add to next_slot[0] before its add to next_slot[1], and that one before ours returned.
+__device__ __forceinline__ void queue_leave(int* next_slot) {
+  if (atomicAdd(next_slot + 1, 1) == (int)gridDim.x - 1) {
+    __hip_atomic_exchange(next_slot, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_exchange(next_slot + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // LEAN: the instance for launches that leave every optional feature off -- no stop rule, no fused store / signals, no ADMM centre, no
 // prepared setup, no restart pass or restart guesses, no absolute tolerances (omgx::CtxT kLean), no refinement: the plain
 // receding-horizon solve of the benchmark classes.  Those blocks are compiled out (the arguments stay: one signature, one launch
@@ -276,6 +295,10 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
                  int* __restrict__ next_slot, const double* __restrict__ x0_alt, int n_alt, int32_t* __restrict__ attempts,
                  unsigned long long* __restrict__ stats, int stagger, const CenterArgs* __restrict__ ctr,
                  double* __restrict__ prep, size_t prep_doubles, const StopArgs* __restrict__ stop) {
+#ifdef OMGX_PROFILE
+  long long t_mark = clock64();      // kernel entry, then the end of every solve of this workgroup (PH_WG_HEAD, PH_WG_TAIL)
+  int b_last = -1;
+#endif
   extern __shared__ __align__(16) double lds[];
   omgx::Work w;
     omgx::work_carve_split<MODE>(w, lds, MODE == omgx::WS_LDS ? nullptr : slabs + (size_t)blockIdx.x * slab_doubles,
@@ -293,7 +316,7 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
   [[maybe_unused]] double* const jval_own = w.jval;      // (the lean instance never rebinds w.jval)
   // (the descriptors are rewritten per solve only where the fused trajectory store may use the space behind a small KKT store as scratch)
   const bool describe_once = LEAN || prep != nullptr || stp == nullptr;
-  if (describe_once) { omgx::Kkt K0; K0.bind(d, T, w.kkt); omgx::kkt_describe(c, d, K0, w, true); }
+  if (describe_once) omgx::kkt_descriptors(c, d, T, w, true);
   // mode 0: one workgroup per agent.  Spill modes: the grid is capped at the number of HBM
   // slabs and every workgroup walks over its agents.
   // `order` (optional) maps launch slots to agents: the host can put expected stragglers first so
@@ -302,22 +325,23 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
   // workgroup that finishes last resets it, next_slot[1] counts the finished ones):
   // solves differ by a factor of several in their iteration counts, and a fixed share of agents per workgroup would
   // leave most of the chip waiting for the unluckiest one.  Which workgroup solves an agent does not change its result.
-  __shared__ int slot_lds;
+  // A launch whose grid covers the batch (one agent per workgroup) gets next_slot = nullptr from the host: every fetch would
+  // return a slot past the end.  Otherwise thread 0 asks for the next slot BEFORE the solve and the workgroup reads the answer
+  // behind the barrier that ends the iteration: the atomic's round trip runs under the solve, no barrier of its own.  Two words,
+  // used in turn: thread 0 may be writing the answer of iteration i + 1 while a slower wave still reads that of iteration i.
+  __shared__ int slot_lds[2];
+  int slot_par = 0;
   // Two workgroups per CU start together and would run their (equally long) solves in lockstep -- both in a one-wave
   // phase, then both in an all-waves phase.  The workgroup in the second wave slot starts `stagger` x 8 k cycles late.
   if (stagger > 0 && (__builtin_amdgcn_s_getreg(6148) & 1))      // HW_ID[3:0] = wave slot within the SIMD
     for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
   for (int slot = blockIdx.x; slot < n_agents;) {
     const int b = order ? order[slot] : slot;
-    if (!next_slot) slot += gridDim.x;
-    else {
-      if (threadIdx.x == 0) slot_lds = gridDim.x + atomicAdd(next_slot, 1);
-      __syncthreads();
-      slot = slot_lds;
-      __syncthreads();
-    }
+    if (next_slot && threadIdx.x == 0) slot_lds[slot_par] = gridDim.x + atomicAdd(next_slot, 1);
+    // (the slot of the next iteration, behind a barrier that every path out of this one passes)
+    const auto next_agent = [&]() { slot = next_slot ? slot_lds[slot_par] : slot + (int)gridDim.x; slot_par ^= 1; };
     // restart pass (OMGX_ONLY_FAILED): agents that are solved already keep x, lam_g, status, iters
-    if constexpr (!LEAN) { if (only_failed && status[b] == 0) continue; }
+    if constexpr (!LEAN) { if (only_failed && status[b] == 0) { __syncthreads(); next_agent(); continue; } }
     // stop rule (omgx_batch_set_stop): a vehicle whose loop has ended -- the criterion held at this or an earlier update -- is not
     // solved again: it keeps its plan (x <- x0), its multipliers and its status; iters = 0.  Every thread evaluates the same
     // numbers from the same loads (a thread that reads the flag after thread 0 cleared it takes the same branch).
@@ -329,6 +353,8 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
       if (!go) {
         for (int i = threadIdx.x; i < d.n_var; i += blockDim.x) x[(size_t)b * d.n_var + i] = x0[(size_t)b * d.n_var + i];
         if (threadIdx.x == 0) { sa.under_way[b] = 0; iters[b] = 0; }
+        __syncthreads();
+        next_agent();
         continue;
       }
     }
@@ -336,6 +362,9 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
     if (threadIdx.x < omgx::PH_COUNT) prof_lds[threadIdx.x] = 0;
     __syncthreads();
     const long long t_begin = clock64();
+    // (what PH_TOTAL does not cover: from kernel entry, or from the end of the workgroup's previous solve, to here)
+    if (threadIdx.x == 0) prof_lds[omgx::PH_WG_HEAD] = t_begin - t_mark;
+    b_last = b;
 #endif
     const double* lbb = lb + (bounds_shared ? 0 : (size_t)b * d.n_con);
     const double* ubb = ub + (bounds_shared ? 0 : (size_t)b * d.n_con);
@@ -411,20 +440,26 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
       // the travelled trajectory of this update (omgx_batch_set_signals): the specification sits behind the store's
       const SignalArgs& sg = reinterpret_cast<const StoreBlock*>(stp)->sg;
       if (sg.log) signals_append_agent(sg, b, w.x + sg.coeff_off, p[(size_t)b * d.n_par + sg.p_t], w.kkt);
-      if (prep) { __syncthreads(); omgx::Kkt K0; K0.bind(d, T, w.kkt); omgx::kkt_describe(c, d, K0, w, true); }      // (the scratch may have reached the descriptors)
+      if (prep) { __syncthreads(); omgx::kkt_descriptors(c, d, T, w, true); }      // (the scratch may have reached the descriptors)
     }
 #ifdef OMGX_PROFILE
     __syncthreads();
     if (threadIdx.x == 0) prof_lds[omgx::PH_TOTAL] = clock64() - t_begin;
     __syncthreads();
     if (prof && threadIdx.x < omgx::PH_COUNT) prof[(size_t)b * omgx::PH_COUNT + threadIdx.x] = prof_lds[threadIdx.x];
+    t_mark = clock64();
 #endif
     __syncthreads();
+    next_agent();
   }
-  if (next_slot && threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(next_slot + 1, 1) == (int)gridDim.x - 1) { next_slot[0] = 0; next_slot[1] = 0; __threadfence(); }
-  }
+  if (next_slot && threadIdx.x == 0) queue_leave(next_slot);
+#ifdef OMGX_PROFILE
+  // from the end of the workgroup's last solve to its exit, on the account of that solve (the thread that zeroed the entry with
+  // the solve's other counters writes it: same thread, same address, program order)
+  if (threadIdx.x == 0) prof_lds[omgx::PH_WG_TAIL] = clock64() - t_mark;
+  __syncthreads();
+  if (prof && b_last >= 0 && threadIdx.x == omgx::PH_WG_TAIL) prof[(size_t)b_last * omgx::PH_COUNT + omgx::PH_WG_TAIL] = prof_lds[omgx::PH_WG_TAIL];
+#endif
 }
 
 // Round 6: the setup of a batch of solves as a kernel of its own -- north_star's "basis evaluation on the sample grid and the
@@ -1185,7 +1220,8 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
   omgx::work_carve_split<MODE>(w, lds, MODE == omgx::WS_LDS ? nullptr : slabs + (size_t)blockIdx.x * slab_doubles, d, kkt_doubles);
   omgx::CtxT<omgx::ws_kkt_hbm(MODE), WAVE_ONLY, omgx::ws_root_lds(MODE), GEN> c; c.red = w.red;
   c.prof = nullptr;
-  __shared__ int slot_lds;
+  __shared__ int slot_lds[2];      // (the slot queue as in the solve kernel: null when the grid covers the batch, else asked ahead)
+  int slot_par = 0;
   if (stagger > 0 && (__builtin_amdgcn_s_getreg(6148) & 1))
     for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
   const int K = rop->K;
@@ -1193,10 +1229,7 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
   // given a short one by the queue afterwards)
   for (int slot = blockIdx.x; slot < n_agents;) {
     const int b = order ? order[slot] : slot;
-    if (threadIdx.x == 0) slot_lds = gridDim.x + atomicAdd(next_slot, 1);
-    __syncthreads();
-    slot = slot_lds;
-    __syncthreads();
+    if (next_slot && threadIdx.x == 0) slot_lds[slot_par] = gridDim.x + atomicAdd(next_slot, 1);
     double* pb = p + (size_t)b * d.n_par;
     double* xb = x + (size_t)b * d.n_var;
     double* lamb = lam + (size_t)b * d.n_con;
@@ -1321,12 +1354,13 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
       }
       __syncthreads();
     }
+    // (a loop that ended early left without a barrier: this one parts the agent's last use of the scratch from the next agent's
+    // first, and publishes the slot thread 0 asked for)
+    __syncthreads();
+    slot = next_slot ? slot_lds[slot_par] : slot + (int)gridDim.x;
+    slot_par ^= 1;
   }
-  // (the last workgroup out resets the queue counter for the next launch, as in the solve kernel)
-  if (threadIdx.x == 0) {
-    __threadfence();
-    if (atomicAdd(next_slot + 1, 1) == (int)gridDim.x - 1) { next_slot[0] = 0; next_slot[1] = 0; }
-  }
+  if (next_slot && threadIdx.x == 0) queue_leave(next_slot);
 }
 
 // ---------------------------------------------------------------------------

@@ -33,6 +33,7 @@ struct HostPlan {
   std::vector<int32_t> jr_ptr, jr_pos, t_jidx, row_leaf, cpl_ptr, cpl_idx, cpl_map;
   std::vector<int32_t> d_off, b_off;
   std::vector<int32_t> lf_w, lf_ldb, lf_band, lf_kind, dl_pos;      // compact store of the wave path (Tables)
+  std::vector<int32_t> bmat_img;     // compact store: the matrix descriptors every solve starts from, [n_leaf + 1] BMat (Tables::bmat_img)
   std::vector<std::vector<std::vector<int>>> var_cpl;                // [leaf][variable]: root positions (but t) its entries of B_l can touch
   // ---- addresses and packed records ---------------------------------------------------------------
   std::vector<int32_t> pair4, eqe3, je_row, jt_addr, diag_addr, t_row, tq_addr;
@@ -885,6 +886,14 @@ struct HostPlan {
     }
     if (pair4.empty()) pair4.assign(4, 0);
     T.pair4 = pair4.data();
+    // The matrix descriptors of the wave path depend on the template alone: filled here, once, by the statements a workgroup
+    // of any other instance runs per solve (kkt_describe_fill), and copied by the kernels (kkt_descriptors).
+    bmat_img.assign(compact ? (size_t)(d.n_leaf + 1) * (sizeof(BMat) / sizeof(int32_t)) : 1, 0);
+    if (compact) {
+      Kkt K; K.bind(d, T, nullptr);
+      kkt_describe_fill<true, false, false>(d, K, (BMat*)bmat_img.data());
+    }
+    T.bmat_img = bmat_img.data();
     return true;
   }
 };
