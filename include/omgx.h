@@ -510,7 +510,7 @@ int  omgx_batch_signals_reduce(omgx_batch* b, const omgx_signals_spec* sp, const
  * `ode` under the plan's inputs plus an optional input disturbance (`Vehicle.simulate`, `vehicle.py:370-390`, `add_disturbance`,
  * 433-450), and the next solve starts from the state the vehicle had one update ago integrated under the undisturbed inputs
  * (`Vehicle.predict`, `vehicle.py:326-337`).  Integrator classes only (`ode` = input: Holonomic, Holonomic3D; parameters state0 /
- * input0 / poseT); no first-order actuator lag.  Per agent the plant carries state [n_spl] (where the vehicle is, at the last
+ * input0 / poseT); the first-order actuator lag: OMGX_HAS_PLANT_LAG below.  Per agent the plant carries state [n_spl] (where the vehicle is, at the last
  * simulated sample), state_prev [n_spl] (where it was one update earlier), input_last [n_spl] (the last applied input) and n_upd
  * (updates simulated so far; the caller zeroes n_upd and overflow).  n_samp = int(round(update_time / sample_time, 6)).
  *
@@ -557,6 +557,38 @@ int  omgx_batch_plant_simulate(omgx_batch* b, const double* x, const double* p, 
                                const omgx_signals_spec* log_sp);
 int  omgx_batch_plant_predict(omgx_batch* b, const double* x, double* p, double tau, double t_value, const omgx_plant_spec* sp);
 int  omgx_batch_set_plant(omgx_batch* b, const omgx_plant_spec* sp, const omgx_signals_spec* log_sp);
+
+/* (OMGX_HAS_PLANT_LAG) The plant's first-order actuator lag: the reference's vehicle option `{'1storder_delay': True, 'time_constant':
+ * ...}` (`vehicles/vehicle.py:378-381, 429-431`, set by `examples/p2p_holonomic_disturbances.py`) -- the vehicle does not apply the
+ * commanded input a(t) but v(t) with  v' = (a(t) - v) / time_constant,  a(t) the linear interpolation of the commanded samples,
+ * v(0) the last applied input.  The solver keeps predicting with `ode` = input: a systematic model mismatch.  Per agent b and spline
+ * k, with h = sample_time, tc = time_constant[b], E = decay[b] = exp(-h / tc) and a_i the applied-input samples of
+ * omgx_batch_plant_simulate (u_i + dist, i = 0 .. n_samp), simulate becomes:
+ *   v_0 = input_last[b, k]          (n_upd == 0: the plan's nominal u_0, without the disturbance: `signals['input'][:, -1]` then)
+ *   for i = 0 .. n_samp - 1:
+ *     s = (a_{i+1} - a_i) / h
+ *     r = tc * s
+ *     v_{i+1} = (a_{i+1} - r) + ((v_i - a_i) + r) * E
+ *   (the exact solution on the sample grid: a_i + s t - tc s is a particular solution under the interpolated command, the rest decays
+ *   by E per sample; every operation rounded on its own, in this order, no fused multiply-add.  The reference integrates the same
+ *   equation with odeint.)
+ *   state_prev <- state;  state <- state + sample_time * sum_{i < n_samp} (v_i + v_{i+1}) / 2   (the statements, partial sums, order
+ *   and rounding of simulate with v in the place of a: the reference integrates the state under the interpolated lagged samples);
+ *   input_last <- v_{n_samp};  n_upd += 1.
+ *   The log's input row takes v_1 .. v_{n_samp}, its state row the partial sums; the dinput row and column 0 stay the plan's.
+ * predict has no lag in it (`Vehicle.predict` knows none), and the stop rule keeps its statement: it reads input_last, the lagged one.
+ * omgx_batch_set_plant_lag: time_constant, decay: HOST arrays [n]; the handle keeps device copies of its own (copied on its stream).
+ * The caller forms decay = exp(-sample_time / time_constant) and hands the same numbers to whoever else replays the loop (two exp
+ * implementations may differ in the last bit): the library calls no exp on the device and only checks them.  The lag then applies
+ * to every following omgx_batch_plant_simulate and every following omgx_batch_rollout with a plant set, whichever of
+ * omgx_batch_set_plant and this entry came first; time_constant == NULL switches it off again.  While it is on,
+ * omgx_batch_plant_simulate / _plant_predict / omgx_batch_set_plant and a rollout with a plant refuse a plant whose sample_time is not
+ * the one given here.  One lag per batch (no mix of lagged and plain vehicles).
+ * Checks, in this order: decay not null; n >= 1; sample_time a positive number; every time_constant finite and > 0; every decay in
+ * [0, 1) (exp may underflow to 0 for a tiny time constant); |decay[b] - exp(-sample_time / time_constant[b])| <= 1e-12; the handle;
+ * n == n_agents. */
+#define OMGX_HAS_PLANT_LAG 1
+int  omgx_batch_set_plant_lag(omgx_batch* b, const double* time_constant, const double* decay, int32_t n, double sample_time);
 
 /* (OMGX_HAS_FEEDBACK) States measured outside the loop: the reference's deployment contract `Deployer.update(current_time, states,
  * inputs, ..., enforce_states, enforce_inputs)` (`execution/deployer.py:43-79`) -> `Vehicle.predict(state0 = ...)`

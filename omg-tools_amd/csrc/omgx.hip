@@ -2,6 +2,7 @@
 // argument structs and the selectors of their template instances are in omgx_kernels.h.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -123,6 +124,8 @@ struct omgx_batch {
   PlantBlock* d_plant = nullptr;    // ... their copy in device memory ...
   PlantBlock* d_plant_call = nullptr;      // ... and the copy of what a stand-alone omgx_batch_plant_simulate / _predict call was given
   bool plant_on = false;
+  double *d_lag_tc = nullptr, *d_lag_decay = nullptr;      // omgx_batch_set_plant_lag: the handle's copies [n_agents] of time constant and decay ...
+  double lag_sample_time = 0.0; bool lag_on = false;       // ... the sample time the decay was formed with, and whether the plant lags
   ObstacleScriptArgs script_host = {};      // omgx_batch_set_obstacle_script: the script as the rollout's script instances read it ...
   ObstacleScriptArgs* d_script = nullptr;   // ... its copy in device memory ...
   ObstacleScriptArgs* d_script_call = nullptr;      // ... and the copy of what a stand-alone omgx_batch_obstacles_advance call was given
@@ -1312,6 +1315,8 @@ int fill_plant(const omgx_batch* b, const omgx_plant_spec* sp, const omgx_signal
       return bad("plant: the log must be one of the plant's plan (coeff_off, n_spl, degree, n_knots, n_samp, sample_time, inv_T) with n_der >= 2");
   }
   if (!b) return bad("null handle");
+  if (b->lag_on && sp->sample_time != b->lag_sample_time)
+    return bad("plant: sample_time = %g is not the one the lag was set with (omgx_batch_set_plant_lag: %g)", sp->sample_time, b->lag_sample_time);
   TRY(check_plan_in_x(b, "plant", plan));
   if (!in_p(b, sp->p_state0, sp->n_spl) || !in_p(b, sp->p_input0, sp->n_spl) || !in_p(b, sp->p_poseT, sp->n_spl) || !in_p(b, sp->p_t, 1))
     return bad("plant: p_state0 / p_input0 / p_poseT / p_t outside p");
@@ -1321,6 +1326,7 @@ int fill_plant(const omgx_batch* b, const omgx_plant_spec* sp, const omgx_signal
   pl.overflow = sp->overflow; pl.under_way = sp->under_way; pl.n_samp = sp->n_samp; pl.max_updates = sp->max_updates;
   pl.p_t = sp->p_t; pl.p_state0 = sp->p_state0; pl.p_input0 = sp->p_input0; pl.p_poseT = sp->p_poseT;
   pl.sample_time = sp->sample_time; pl.stop_tol = sp->stop_tol;
+  pl.lag_tc = b->lag_on ? b->d_lag_tc : nullptr; pl.lag_decay = b->lag_on ? b->d_lag_decay : nullptr;
   blk->sg = SignalArgs{};
   return log_sp ? fill_signals(b, log_sp, &blk->sg) : OMGX_OK;
 }
@@ -1345,6 +1351,41 @@ int omgx_batch_set_plant(omgx_batch* b, const omgx_plant_spec* sp, const omgx_si
   b->plant_host = blk;
   TRY(push_args(b, &b->d_plant, b->plant_host));
   b->plant_on = true;
+  return OMGX_OK;
+}
+
+int omgx_batch_set_plant_lag(omgx_batch* b, const double* time_constant, const double* decay, int32_t n, double sample_time) {
+  if (!time_constant) {      // the lag off; a registered plant block is pushed again without it
+    if (!b) return bad("null handle");
+    b->lag_on = false;
+  } else {
+    if (!decay) return bad("plant_lag: null decay");
+    if (n < 1) return bad("plant_lag: n = %d must be positive", n);
+    if (!(sample_time > 0.0) || !std::isfinite(sample_time)) return bad("plant_lag: sample_time = %g must be a positive number", sample_time);
+    for (int i = 0; i < n; ++i)
+      if (!(time_constant[i] > 0.0) || !std::isfinite(time_constant[i])) return bad("plant_lag: time_constant[%d] = %g must be positive and finite", i, time_constant[i]);
+    for (int i = 0; i < n; ++i)
+      if (!(decay[i] >= 0.0 && decay[i] < 1.0)) return bad("plant_lag: decay[%d] = %g outside [0, 1)", i, decay[i]);
+    for (int i = 0; i < n; ++i)
+      if (!(fabs(decay[i] - exp(-sample_time / time_constant[i])) <= 1e-12))
+        return bad("plant_lag: decay[%d] = %.17g is not exp(-sample_time / time_constant[%d]) = %.17g", i, decay[i], i, exp(-sample_time / time_constant[i]));
+    if (!b) return bad("null handle");
+    if (n != b->n_agents) return bad("plant_lag: n = %d, the handle has %d agents", n, b->n_agents);
+    HIPCHK(hipSetDevice(b->device));
+    if (!b->d_lag_tc) TRY(dalloc(b, (size_t)n, &b->d_lag_tc));
+    if (!b->d_lag_decay) TRY(dalloc(b, (size_t)n, &b->d_lag_decay));
+    // (stream-ordered: a launch still running reads the previous values; pageable sources are staged before the calls return)
+    HIPCHK(hipMemcpyAsync(b->d_lag_tc, time_constant, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, b->stream));
+    HIPCHK(hipMemcpyAsync(b->d_lag_decay, decay, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, b->stream));
+    b->lag_sample_time = sample_time;
+    b->lag_on = true;
+  }
+  if (b->plant_on && b->d_plant) {      // (the order of the two registrations does not matter)
+    b->plant_host.pl.lag_tc = b->lag_on ? b->d_lag_tc : nullptr;
+    b->plant_host.pl.lag_decay = b->lag_on ? b->d_lag_decay : nullptr;
+    HIPCHK(hipSetDevice(b->device));
+    TRY(push_args(b, &b->d_plant, b->plant_host));
+  }
   return OMGX_OK;
 }
 
@@ -1449,6 +1490,8 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
                "omgx_batch_plant_predict / omgx_batch_solve / omgx_batch_plant_simulate");
   if (b->plant_on && (!same_plan(*sp, b->plant_host.pl) || sp->p_t != b->plant_host.pl.p_t))
     return bad("rollout: the plan of the specification (coeff_off, n_spl, degree, n_knots, p_t) is not the one the plant was set with");
+  if (b->plant_on && b->lag_on && b->plant_host.pl.sample_time != b->lag_sample_time)
+    return bad("rollout: the plant's sample_time = %g is not the one the lag was set with (omgx_batch_set_plant_lag: %g)", b->plant_host.pl.sample_time, b->lag_sample_time);
   if (b->script_on) {
     const ObstacleScriptArgs& sc = b->script_host;
     if (!(b->plant_on ? b->inst.rollout_plant_script : b->inst.rollout_script) || !b->d_script)

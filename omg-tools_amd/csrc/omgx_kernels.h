@@ -831,7 +831,8 @@ shift_kernel(double* __restrict__ x, int x_stride, const uint8_t* __restrict__ m
 // `Vehicle.simulate` / `Vehicle.predict` of the reference with its default options (`vehicles/vehicle.py:326-337, 370-390`),
 // `ode` = input (Holonomic, Holonomic3D).  Two routines, called by the whole workgroup of an agent with the same arguments;
 // thread k < n_spl owns spline k and adds its samples up in index order, every product and sum rounded on its own: the
-// stand-alone kernels and the rollout kernel write the same bits.
+// stand-alone kernels and the rollout kernel write the same bits.  With lag_tc set (omgx_batch_set_plant_lag) simulate passes the
+// applied inputs through the reference's first-order actuator lag (`vehicle.py:378-381, 429-431`) in closed form on the sample grid.
 // ---------------------------------------------------------------------------
 struct PlantArgs {
   double* state; double* state_prev; double* input_last;      // [B, n_spl]
@@ -840,6 +841,7 @@ struct PlantArgs {
   int coeff_off, n_spl, degree, n_knots, n_samp, max_updates, p_t, p_state0, p_input0, p_poseT;
   double sample_time, inv_T, stop_tol;
   KnotArg knots;
+  const double* lag_tc; const double* lag_decay;              // [B] (omgx_batch_set_plant_lag): time constant, exp(-sample_time / it); nullptr: no lag
 };
 // what the rollout kernel's plant instance reads from device memory: the plant and the log its simulate writes (sg.log == nullptr: none)
 struct PlantBlock { PlantArgs pl; SignalArgs sg; };
@@ -911,20 +913,50 @@ __device__ __noinline__ void plant_simulate_agent(const PlantArgs& pl, const Sig
       s0 = spline_der_at(c, kk, pl.degree, span_of(kk, pl.degree, pl.n_knots, u0), u0, 0);
     } else s0 = pl.state[(size_t)b * pl.n_spl + k];
     double a0 = plant_input_at(pl, kk, c, t_rel, 0);
-    if (db) a0 = a0 + db[0];
     double acc = 0.0, s = s0;
-    for (int i = 1; i <= n_samp; ++i) {
-      double a1 = plant_input_at(pl, kk, c, t_rel, i);
-      if (db) a1 = a1 + db[i];
-      const double h = (a0 + a1) / 2.0;
-      acc = acc + h;
-      const double m = pl.sample_time * acc;
-      s = s0 + m;
-      if (lg) {
-        lg[(size_t)k * sg->cap + i] = s;
-        if (sg->n_der >= 2) lg[((size_t)sg->n_spl + k) * sg->cap + i] = a1;
+    if (pl.lag_tc) {      // (the same branch in every thread of the launch) the first-order actuator lag, include/omgx.h OMGX_HAS_PLANT_LAG
+      const double tc = pl.lag_tc[b], decay = pl.lag_decay[b];
+      // the lagged input starts from the last applied one; ahead of the first simulate from the plan's own sample 0, undisturbed
+      double v0 = nu == 0 ? a0 : pl.input_last[(size_t)b * pl.n_spl + k];
+      if (db) a0 = a0 + db[0];
+      for (int i = 1; i <= n_samp; ++i) {
+        double a1 = plant_input_at(pl, kk, c, t_rel, i);
+        if (db) a1 = a1 + db[i];
+        const double d = a1 - a0;
+        const double sl = d / pl.sample_time;
+        const double r = tc * sl;
+        const double part = a1 - r;
+        const double e0 = v0 - a0;
+        const double hom = e0 + r;
+        const double dec = hom * decay;
+        const double v1 = part + dec;      // exact under the linearly interpolated command: particular solution + decayed rest
+        const double w = v0 + v1;
+        const double h = w / 2.0;
+        acc = acc + h;
+        const double m = pl.sample_time * acc;
+        s = s0 + m;
+        if (lg) {
+          lg[(size_t)k * sg->cap + i] = s;
+          if (sg->n_der >= 2) lg[((size_t)sg->n_spl + k) * sg->cap + i] = v1;
+        }
+        a0 = a1; v0 = v1;
       }
-      a0 = a1;
+      a0 = v0;      // (input_last <- v_n)
+    } else {
+      if (db) a0 = a0 + db[0];
+      for (int i = 1; i <= n_samp; ++i) {
+        double a1 = plant_input_at(pl, kk, c, t_rel, i);
+        if (db) a1 = a1 + db[i];
+        const double h = (a0 + a1) / 2.0;
+        acc = acc + h;
+        const double m = pl.sample_time * acc;
+        s = s0 + m;
+        if (lg) {
+          lg[(size_t)k * sg->cap + i] = s;
+          if (sg->n_der >= 2) lg[((size_t)sg->n_spl + k) * sg->cap + i] = a1;
+        }
+        a0 = a1;
+      }
     }
     pl.state_prev[(size_t)b * pl.n_spl + k] = s0;
     pl.state[(size_t)b * pl.n_spl + k] = s;

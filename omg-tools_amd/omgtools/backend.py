@@ -345,6 +345,7 @@ PROTOTYPES = {
     'omgx_batch_plant_simulate': (C.c_int, [_H, _P, _P, _PLA, _SIG]),
     'omgx_batch_plant_predict': (C.c_int, [_H, _P, _P, _D, _D, _PLA]),
     'omgx_batch_set_plant': (C.c_int, [_H, _PLA, _SIG]),
+    'omgx_batch_set_plant_lag': (C.c_int, [_H, _P, _P, _I, _D]),
     'omgx_batch_predict_measured': (C.c_int, [_H, _P, _P, _D, _D, C.POINTER(CFeedbackSpec)]),
     'omgx_batch_obstacles_advance': (C.c_int, [_H, _P, C.POINTER(CObstacleScript), _D, _D]),
     'omgx_batch_set_obstacle_script': (C.c_int, [_H, C.POINTER(CObstacleScript), _P, _I]),
@@ -845,6 +846,19 @@ class BatchSolver(object):
         lg = self._signals_spec(**log) if log is not None else None
         _check(self.lib, self.lib.omgx_batch_set_plant(self._h, C.byref(sp), C.byref(lg) if lg is not None else None), 'omgx_batch_set_plant')
         self._plant = (sp, lg)
+
+    def set_plant_lag(self, time_constant=None, decay=None, sample_time=0.0):
+        """The plant's first-order actuator lag (include/omgx.h omgx_batch_set_plant_lag; time_constant=None: off): host arrays [B] of
+        the time constants and of decay = exp(-sample_time / time_constant), formed by the caller; the library keeps device copies."""
+        if time_constant is None:
+            _check(self.lib, self.lib.omgx_batch_set_plant_lag(self._h, None, None, 0, 0.0), 'omgx_batch_set_plant_lag')
+            return
+        tc, dc = (np.ascontiguousarray(a, dtype=np.float64) for a in (time_constant, decay))
+        if tc.shape != (self.n_agents,) or dc.shape != tc.shape:
+            raise ValueError('time_constant and decay must be [n_agents] = [%d]' % self.n_agents)
+        _check(self.lib, self.lib.omgx_batch_set_plant_lag(self._h, tc.ctypes.data, dc.ctypes.data, len(tc), float(sample_time)),
+               'omgx_batch_set_plant_lag')
+        self._lag = (tc, dc)
 
     def sample(self, x, coeff_off, n_spl, degree, knots, n_der, t0, dt, n_samp,
                out=None, as_f32=False, device=False):

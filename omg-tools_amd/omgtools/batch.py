@@ -10,7 +10,7 @@ with a primal-dual warm start.
 Layout: `BatchP2P` states that protocol once -- tables and options from the template, `solve_cold`, `step`, `rollout`, the stop rule,
 the log -- and branches on no executor.  Where the [B, *] arrays live and who computes on them sits behind its hooks (`_allocate,
 _predict, _shift, _solve, _cold, _rollout, _norm, _stop_rule, _signals_alloc, _signals_fused, _signals_append_now,
-_signals_summary, _plant_alloc, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
+_signals_summary, _plant_alloc, _plant_lag, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
 being the allocator / stream only; no data leaves HBM between steps) and `HostP2P` (`ops=<a host solver object>`: the same
 statements in numpy, how the parity tests and the CPU baseline of bench.py replay the loop; this package never imports the
 oracle).  `BatchP2P(problem, P, ops=...)` hands out the executor `ops` names.  The clock of a step is `splines.step_clock`, the
@@ -18,12 +18,14 @@ obstacle motion `splines.advance_obstacles`: shared with the formation loops.
 
 `BatchP2P.plant` puts a simulated vehicle into the loop (the reference's default `ideal_prediction=False, ideal_update=False`, with an
 optional input disturbance): step (1) then starts the solve from the state the vehicle had one update ago integrated under the planned
-inputs, and after step (3) the vehicle travels the update under the applied inputs (include/omgx.h OMGX_HAS_PLANT has the statements).
+inputs, and after step (3) the vehicle travels the update under the applied inputs (include/omgx.h OMGX_HAS_PLANT has the statements);
+with `time_constant` the vehicle applies them through the reference's first-order actuator lag (OMGX_HAS_PLANT_LAG).
 `BatchP2P.feedback` lets `step` take states measured outside the loop instead (`step(states=...)`, the reference's
 `Deployer.update(current_time, states, ...)`; include/omgx.h OMGX_HAS_FEEDBACK): a loop has one source of states.
 `BatchP2P.obstacle_script` moves the obstacles by the reference's `simulation={'trajectories': ...}` -- jumps of position, velocity
 or acceleration at given times (include/omgx.h OMGX_HAS_OBSTACLE_SCRIPT; `splines.advance_obstacles_scripted` in numpy).
 """
+import math
 import os
 
 import numpy as np
@@ -440,7 +442,7 @@ class BatchP2P(object):
             self._signals_append_now()
 
     # -- the plant in the loop --------------------------------------------------------------------
-    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True):
+    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True, time_constant=None):
         """Put a simulated vehicle into every agent's loop, as the reference's `Simulator.run` keeps one with its default options
         `ideal_prediction=False, ideal_update=False` (`vehicles/vehicle.py:73-75`).  From now on, after every solve (`solve_cold`,
         `step`, every step inside a `rollout` launch) the vehicle travels the update under the plan's inputs plus `disturbance`
@@ -451,10 +453,21 @@ class BatchP2P(object):
         `max_updates` is not simulated and sets the plant's `overflow`.  `arrived` / `stop_at_arrival` test the travelled state and the
         last applied input; with `record_signals` the log takes the travelled state and the applied input (dinput: the plan's).  Call
         before `solve_cold`: the vehicle starts from the first plan's own sample 0.  Integrator classes (`ode` = input: Holonomic,
-        Holonomic3D) without the first-order actuator lag.  on=False takes the plant out again."""
+        Holonomic3D).
+
+        time_constant (a scalar, or one value per agent [B]; None: none): the reference's first-order actuator lag, the vehicle
+        options `{'1storder_delay': True, 'time_constant': ...}` (`vehicles/vehicle.py:378-381, 429-431`).  The vehicle then applies
+        not the commanded input a (plan + disturbance) but v with v' = (a - v) / time_constant, started from the last applied input,
+        and travels under v -- in closed form on the sample grid, exact for the linearly interpolated command (include/omgx.h
+        OMGX_HAS_PLANT_LAG has the statements; the reference integrates with odeint).  The prediction knows no lag, as the
+        reference's: a systematic model mismatch, per agent, for a robustness study of a fleet in one `rollout` launch.  `arrived` /
+        `stop_at_arrival` and the log see the lagged input.  The batch reads no vehicle option on its own: a vehicle with
+        '1storder_delay' set is refused unless its `time_constant` is passed here.  on=False takes the plant out again, the lag
+        with it."""
         if not on:
             if self._pl is not None:
                 self._pl = None
+                self._plant_lag(None)
                 self._plant_rollout()
                 if self.under_way is not None:
                     self._stop_rule(self._o_pose('stop_at_arrival'))
@@ -466,8 +479,9 @@ class BatchP2P(object):
         if any((label, nm) not in lay for nm in ('state0', 'input0', 'poseT')) or self.n_spl != self.n_dim:
             raise NotImplementedError('plant(): %s is not an integrator class (ode = input: Holonomic, Holonomic3D, parameters state0 / '
                                       'input0 / poseT); its own model is not simulated in the batched loop' % cls_name)
-        if getattr(self.veh, 'options', {}).get('1storder_delay'):
-            raise NotImplementedError("plant(): %s has '1storder_delay' set; the first-order actuator lag is not simulated in the batched loop" % cls_name)
+        if getattr(self.veh, 'options', {}).get('1storder_delay') and time_constant is None:
+            raise NotImplementedError("plant(): %s has '1storder_delay' set and the batched loop reads no vehicle option on its own; pass "
+                                      "time_constant=vehicle.options['time_constant'] to simulate the first-order actuator lag" % cls_name)
         if self._plan_ready:
             raise RuntimeError('plant(): the vehicle starts from the first plan -- call it before solve_cold')
         n_samp = int(round(self.update_time / float(sample_time), 6))
@@ -480,8 +494,23 @@ class BatchP2P(object):
         shape = (self.B, self.n_spl, int(max_updates), n_samp + 1)
         if disturbance is not None and tuple(disturbance.shape) != shape:
             raise ValueError('plant: disturbance must be [B, n_spl, max_updates, n_samp + 1] = %s, got %s' % (shape, tuple(disturbance.shape)))
-        pl = dict(sample_time=float(sample_time), n_samp=n_samp, max_updates=int(max_updates), o_pose=self._o_pose('plant'))
+        lag = None
+        if time_constant is not None:
+            tc = np.asarray(time_constant, dtype=float)
+            if tc.shape not in ((), (self.B,)):
+                raise ValueError('plant: time_constant must be a scalar or one value per agent [%d], got %s' % (self.B, list(tc.shape)))
+            tc = np.ascontiguousarray(np.broadcast_to(tc, (self.B,)))
+            if not (np.isfinite(tc).all() and (tc > 0.0).all()):
+                raise ValueError('plant: time_constant must be positive and finite')
+            # (formed once, element by element with one exp: every executor, and every sub-batch of a streamed loop, gets the same bits)
+            decay = np.array([math.exp(-float(sample_time) / t) for t in tc])
+            if not (decay < 1.0).all():
+                raise ValueError('plant: time_constant = %g is too long for sample_time %g (exp(-sample_time / time_constant) rounds to 1)'
+                                 % (tc[decay >= 1.0][0], float(sample_time)))
+            lag = (tc, decay)
+        pl = dict(sample_time=float(sample_time), n_samp=n_samp, max_updates=int(max_updates), o_pose=self._o_pose('plant'), lag=lag)
         pl.update(self._plant_alloc(disturbance))
+        self._plant_lag(pl)                                 # (may still refuse: the loop is as it was then)
         self._pl = pl
         if self._sig is not None:
             self._signals_fused(False)
@@ -502,7 +531,8 @@ class BatchP2P(object):
         states, inputs, ..., enforce_states, enforce_inputs)` -> `Vehicle.predict(state0=...)` (`execution/deployer.py:43-79`,
         `vehicles/vehicle.py:302-337`).  Fixes the sample grid the measured state is integrated on, n_samp = update_time /
         sample_time intervals per update (the trapezoid sum of the plan's inputs: exact for the reference's linearly interpolated
-        input).  Integrator classes (`ode` = input: Holonomic, Holonomic3D) without the first-order actuator lag; every agent on the
+        input).  Integrator classes (`ode` = input: Holonomic, Holonomic3D); a vehicle's '1storder_delay' option changes nothing here
+        (`Vehicle.predict(state0=...)` has no lag in it, and the measured vehicle is outside the loop); every agent on the
         batch's one clock (no `delay`).  `rollout` takes no states.  on=False: `step` takes none again."""
         if not on:
             self._fb = None
@@ -512,8 +542,6 @@ class BatchP2P(object):
         if any((label, nm) not in lay for nm in ('state0', 'input0', 'poseT')) or self.n_spl != self.n_dim:
             raise NotImplementedError('feedback(): %s is not an integrator class (ode = input: Holonomic, Holonomic3D, parameters state0 / '
                                       'input0 / poseT); its own model is not integrated in the batched loop' % cls_name)
-        if getattr(self.veh, 'options', {}).get('1storder_delay'):
-            raise NotImplementedError("feedback(): %s has '1storder_delay' set; the first-order actuator lag is not integrated in the batched loop" % cls_name)
         if getattr(self, 'pool', None) is not None:
             raise NotImplementedError('feedback: not with a host pool (its workers run the step glue themselves)')
         n_samp = int(round(self.update_time / float(sample_time), 6))
@@ -755,6 +783,12 @@ class DeviceP2P(BatchP2P):
     def _plant_simulate(self):
         self.solver.plant_simulate(self.x, self.p, self._plant_args(), self._plant_log_args())
 
+    def _plant_lag(self, pl):
+        """The lag of the plant `pl` (its time constants and decays, host arrays) handed to the handle; None, or a plant without: off."""
+        if pl is None or pl['lag'] is None:
+            return self.solver.set_plant_lag(None)
+        self.solver.set_plant_lag(pl['lag'][0], pl['lag'][1], pl['sample_time'])
+
     def _plant_rollout(self):
         """The plant (and the log its simulate writes) as the rollout kernel reads it, registered with the handle; taken off without one."""
         if self._pl is None:
@@ -943,6 +977,16 @@ class HostP2P(BatchP2P):
                 continue
             c, t_rel, u = self._plant_plan(b)
             a = u + g['dist'][b, :, nu, :] if g['dist'] is not None else u
+            if g['lag'] is not None:
+                # the first-order actuator lag (include/omgx.h OMGX_HAS_PLANT_LAG): the same statements in the same order, sample by sample
+                tc, E, h = g['lag'][0][b], g['lag'][1][b], g['sample_time']
+                v = np.empty_like(a)
+                v[:, 0] = u[:, 0] if nu == 0 else g['input_last'][b]
+                for i in range(g['n_samp']):
+                    s = (a[:, i + 1] - a[:, i]) / h
+                    r = tc * s
+                    v[:, i + 1] = (a[:, i + 1] - r) + ((v[:, i] - a[:, i]) + r) * E
+                a = v                                           # (the vehicle travels under the lagged input; the log takes it)
             s0 = c @ self.basis.eval_basis([t_rel / self.T])[0] if nu == 0 else g['state'][b].copy()
             samples = s0[:, None] + g['sample_time'] * np.cumsum((a[:, :-1] + a[:, 1:]) / 2.0, axis=1)
             if sig is not None:
@@ -966,6 +1010,9 @@ class HostP2P(BatchP2P):
             self.p[b, self.o_state0:self.o_state0 + self.n_spl] = s0 + g['sample_time'] * np.cumsum((u[:, :-1] + u[:, 1:]) / 2.0, axis=1)[:, -1]
             self.p[b, self.o_input0:self.o_input0 + self.n_spl] = c @ Ed
             self.p[b, self.o_t] = t_rel
+
+    def _plant_lag(self, pl):
+        pass                                              # (`_plant_simulate` reads the plant's own `lag`)
 
     def _plant_rollout(self):
         pass
@@ -1144,11 +1191,18 @@ class StreamedP2P(object):
         """`BatchP2P.record_signals` for every sub-batch (each logs on its own stream)."""
         self._each(lambda m: m.record_signals(sample_time, max_updates, on, cap))
 
-    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True):
-        """`BatchP2P.plant` for every sub-batch, each with its rows of the disturbance."""
+    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True, time_constant=None):
+        """`BatchP2P.plant` for every sub-batch, each with its rows of the disturbance and of a per-agent time constant."""
+        tc = None
+        if time_constant is not None:
+            n = self.bounds[-1][1]
+            tc = np.asarray(time_constant, dtype=float)
+            if tc.shape not in ((), (n,)) or not (np.isfinite(tc).all() and (tc > 0.0).all()):      # (ahead of the first sub-batch: a refused call changes none)
+                raise ValueError('plant: time_constant must be a positive finite scalar or one such value per agent [%d]' % n)
+            tc = np.broadcast_to(tc, (n,))
         for (lo, hi), m, st in zip(self.bounds, self.parts, self.streams):
             with self.torch.cuda.stream(st):
-                m.plant(sample_time, max_updates, None if disturbance is None else disturbance[lo:hi], on)
+                m.plant(sample_time, max_updates, None if disturbance is None else disturbance[lo:hi], on, None if tc is None else tc[lo:hi])
 
     def feedback(self, sample_time=0.01, on=True):
         """`BatchP2P.feedback` for every sub-batch; `step(states=...)` then hands each its rows."""
