@@ -450,9 +450,10 @@ int  omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, d
  * THE PLAN.  coeff_off, n_spl, degree, knots, n_knots and, where time derivatives are taken, inv_T say which coefficients of x
  * are the vehicle's splines and on which basis.  Every entry that takes them -- omgx_batch_sample, _store / _set_store,
  * _set_signals / _signals_append / _signals_reduce, _set_plant / _plant_simulate / _plant_predict, _predict / _predict_ex /
- * _predict_quadrotor, _predict_measured, _rollout -- holds them to one rule:
+ * _predict_quadrotor, _predict_measured, _plant_quadrotor_simulate / _plant_quadrotor_predict, _rollout -- holds them to one rule:
  *   knots is not null;
- *   min_degree <= degree <= 5, min_degree = 0 for omgx_batch_sample, 3 for omgx_batch_predict_quadrotor, 1 elsewhere;
+ *   min_degree <= degree <= 5, min_degree = 0 for omgx_batch_sample, 3 for omgx_batch_predict_quadrotor and the
+ *   omgx_batch_plant_quadrotor entries (which also ask for n_spl == 2), 1 elsewhere;
  *   2 * degree + 2 <= n_knots <= 40 (a clamped basis with at least one span; the kernels take the knots by value);
  *   1 <= n_spl, and n_spl <= 64 where a thread owns a spline (the plant entries, omgx_batch_predict_measured, omgx_batch_rollout);
  *   coeff_off >= 0;  inv_T > 0 wherever the entry carries one;
@@ -628,6 +629,75 @@ typedef struct omgx_feedback_spec {
 } omgx_feedback_spec;
 int  omgx_batch_predict_measured(omgx_batch* b, const double* x, double* p, double tau, double t_value,
                                  const omgx_feedback_spec* sp);
+
+/* (OMGX_HAS_PLANT_QUADROTOR) The Quadrotor's plant: the plant in the loop (OMGX_HAS_PLANT) and measured states (OMGX_HAS_FEEDBACK)
+ * for the one class of the batched loop whose model is not an integrator -- state (x, y, dx, dy, theta), inputs thrust u1 and pitch
+ * rate u2, `ode` = (dx, dy, u1 sin theta, u1 cos theta - g, u2) (`vehicles/quadrotor.py:149-152`), parameters spl0 / dspl0 / ddspl0 /
+ * poseT.  Stand-alone launches per step only: no rollout instance, no actuator lag.
+ * Quantities: h = sample_time, n_samp = int(round(update_time / sample_time, 6)), g = gravity; the plan is the two splines x, y at
+ * coeff_off (n_spl == 2, degree >= 3); time derivatives are spline-domain derivatives * inv_T^o.  Inputs of the plan at an
+ * abscissa (`quadrotor.py:136-139`):
+ *   u1 = sqrt(ddx^2 + (ddy + g)^2),   u2 = (dddx (ddy + g) - ddx dddy) / ((ddy + g)^2 + ddx^2).
+ * Per agent the plant carries state [5], state_prev [5], input_last [2], dspl_last [2] (the PLAN's velocity at the last travelled
+ * sample: the reference's `signals['dspl']` comes from the plan, not from the vehicle), n_upd and overflow (the caller zeroes both).
+ *
+ * simulate -- after the solve of an update, with that solve's plan and t_rel = p[p_t]:
+ *   nominal inputs   u_i at (t_rel + i h) * inv_T,  i = 0 .. n_samp
+ *   applied inputs   a_i = u_i + dist[b, :, n_upd, i]            (dist [B, 2, max_updates, n_samp + 1]; NULL: none)
+ *   state_prev <- state;  state advances by classical Runge-Kutta over the n_samp intervals, per interval k1 at a_i, k2 and k3 at
+ *     (a_i + a_{i+1}) / 2, k4 at a_{i+1} (the reference's odeint on the linearly interpolated input, `vehicle.py:412-423`); the state
+ *     after interval i is state sample i + 1.  input_last <- a_{n_samp};  dspl_last <- the plan's first time derivative at sample
+ *     n_samp;  n_upd += 1.  On the first simulate (n_upd == 0) the state starts from the plan's own sample 0,
+ *     (x, y, dx, dy, atan2(ddx, ddy + g)) (`vehicle.py:361-364`, `quadrotor.py:136-140`).
+ *   An update with n_upd >= max_updates writes nothing and sets overflow[b].
+ *   With a log (log_sp: an omgx_signals_spec of the plant's plan, n_samp and sample_time) the update's spline columns are appended
+ *   exactly as omgx_batch_signals_append writes them (the plan's rows: the reference's `dspl` / `ddspl` signals), and -- with
+ *   log_state [B, 5, cap], log_input [B, 2, cap] given -- the travelled state samples and a_1 .. a_{n_samp} go into these two arrays
+ *   at the same columns; column 0 is the plan's sample 0, undisturbed; count, cap and overflow are the log's.
+ * predict -- at the head of the next update, before obstacle motion and the knot-crossing shift; it reads the old plan and the old
+ *   p[p_t]: state_prev is integrated by the same Runge-Kutta statements under the nominal u_i (the same abscissae as simulate: the
+ *   same bits);  p[p_off[0] ..] <- the position of the result (only state[:2] of the prediction enters the parameters,
+ *   `quadrotor.py:112-117`);  p[p_off[1] ..], p[p_off[2] ..] <- the plan's first and second time derivative at tau;  p[p_t] <- t_value.
+ *   The disturbance of the interval just travelled reaches the solver one update late through state_prev, as in the reference.
+ * stop rule -- tested where predict runs (`quadrotor.py:104-110`): an agent with under_way[b] == 0 is left alone; one with
+ *   |state[:2] - p[p_poseT ..]| <= stop_tol and |dspl_last| <= stop_tol (n_upd >= 1) gets under_way[b] = 0 and is neither predicted,
+ *   solved nor simulated again (register the same under_way with omgx_batch_set_stop and a negative tolerance, as for the
+ *   integrator plant).
+ * measured states -- omgx_batch_plant_quadrotor_predict with states [B, 5] (device or pinned host memory; each value is read once,
+ *   by the thread that owns it): no stop test, the plant's arrays are not read.  fresh[b] != 0 (or fresh == NULL): the predict
+ *   statements with states[b] in the place of state_prev.  fresh[b] == 0: the ideal prediction, the statements of
+ *   omgx_batch_predict_ex for p_off[0 .. 2].  enforce != 0 (`Quadrotor.set_initial_conditions`): p[p_off[0] ..] <- states[b, :2],
+ *   p[p_off[1] ..] = p[p_off[2] ..] = 0 for the fresh agents.
+ * The chain is walked by one thread in index order, every product and sum rounded on its own.  One launch each on the handle's
+ * stream, one workgroup per agent (device pointers x, p); predict carries a pending omgx_batch_order_by_iters as
+ * omgx_batch_plant_predict does.
+ * Checks, in this order: x, p and the specification not null; predict: fresh / enforce only with states, tau and t_value numbers;
+ * the required arrays not null (state, state_prev, input_last, dspl_last, n_upd; not needed with states); the plan (the rule above
+ * omgx_store_spec, degree >= 3, then n_spl == 2); 1 <= n_samp and n_samp + 1 <= 64 (a lane per sample), max_updates >= 1 (not needed
+ * with states), sample_time > 0, g > 0, stop_tol a number; log_state and log_input both or neither, and only with the log
+ * specification, which must be one of the plant's plan, n_samp, sample_time and inv_T; the LDS need within 64 KiB; the handle; the plan
+ * inside x; p_off[0 .. 2] (2 wide), p_poseT (2 wide; not needed with states) and p_t inside p.  predict does not read log_state /
+ * log_input. */
+#define OMGX_HAS_PLANT_QUADROTOR 1
+typedef struct omgx_quad_plant_spec {
+  double*  state;          /* [B, 5] device */
+  double*  state_prev;     /* [B, 5] device */
+  double*  input_last;     /* [B, 2] device */
+  double*  dspl_last;      /* [B, 2] device */
+  const double* dist;      /* [B, 2, max_updates, n_samp + 1] device, or NULL */
+  int32_t* n_upd;          /* [B] device, in/out */
+  int32_t* overflow;       /* [B] device, or NULL */
+  int32_t* under_way;      /* [B] device, or NULL: no stop rule */
+  double*  log_state;      /* [B, 5, cap] device, or NULL */
+  double*  log_input;      /* [B, 2, cap] device, or NULL */
+  const double* knots;     /* [n_knots] host; the plan: the rule above omgx_store_spec */
+  int32_t coeff_off, n_spl, degree, n_knots, n_samp, max_updates, p_t, p_poseT, p_off[3], reserved;
+  double  sample_time, inv_T, stop_tol, g;
+} omgx_quad_plant_spec;
+int  omgx_batch_plant_quadrotor_simulate(omgx_batch* b, const double* x, const double* p, const omgx_quad_plant_spec* sp,
+                                         const omgx_signals_spec* log_sp);
+int  omgx_batch_plant_quadrotor_predict(omgx_batch* b, const double* x, double* p, double tau, double t_value,
+                                        const omgx_quad_plant_spec* sp, const double* states, const int32_t* fresh, int32_t enforce);
 
 /* (OMGX_HAS_OBSTACLE_SCRIPT) Obstacle scripts: the reference's obstacle trajectories `simulation={'trajectories': {...}}` -- at given
  * times a value is added to an obstacle's position, velocity or acceleration, between these jumps it moves with constant

@@ -1638,6 +1638,81 @@ int omgx_batch_predict_measured(omgx_batch* b, const double* x, double* p, doubl
 }
 
 namespace {
+// A Quadrotor plant specification (and the log that goes with a simulate) -> the arguments the two kernels take by value.  `who`
+// names the entry; with_plant: the plant's own arrays are read (not with measured states).  The checks that need no handle come first.
+int fill_quad_plant(const omgx_batch* b, const char* who, const omgx_quad_plant_spec* sp, const omgx_signals_spec* log_sp, bool with_plant,
+                    QuadPlantArgs* pl, SignalArgs* sg) {
+  if (with_plant && (!sp->state || !sp->state_prev || !sp->input_last || !sp->dspl_last || !sp->n_upd))
+    return bad("%s: null state / state_prev / input_last / dspl_last / n_upd", who);
+  const Plan plan = plan_of(*sp);
+  TRY(check_plan(who, plan, 3, kOwnedSpl));
+  if (sp->n_spl != 2) return bad("%s: n_spl = %d, the Quadrotor's plan is the two splines x, y", who, sp->n_spl);
+  if (sp->n_samp < 1 || sp->n_samp + 1 > 64) return bad("%s: n_samp = %d outside 1 .. 63 (a lane per sample, n_samp + 1 <= 64)", who, sp->n_samp);
+  if (with_plant && sp->max_updates < 1) return bad("%s: max_updates = %d must be positive", who, sp->max_updates);
+  if (!(sp->sample_time > 0.0)) return bad("%s: sample_time = %g must be positive", who, sp->sample_time);
+  if (!(sp->g > 0.0)) return bad("%s: g = %g must be positive", who, sp->g);
+  if (sp->stop_tol != sp->stop_tol) return bad("%s: stop_tol is not a number", who);
+  if ((sp->log_state == nullptr) != (sp->log_input == nullptr) || (sp->log_state && !log_sp))
+    return bad("%s: log_state / log_input go together, and with the log specification (count, cap)", who);
+  size_t lds = quad_plant_lds_doubles(sp->degree, sp->n_knots, sp->n_samp);
+  if (log_sp) {
+    TRY(check_signals_spec(log_sp));
+    if (!same_plan(*log_sp, *sp) || log_sp->inv_T != sp->inv_T || log_sp->n_samp != sp->n_samp || log_sp->sample_time != sp->sample_time)
+      return bad("%s: the log must be one of the plant's plan (coeff_off, n_spl, degree, n_knots, n_samp, sample_time, inv_T)", who);
+    lds += sample_scratch_doubles(log_sp->n_spl, log_sp->degree, log_sp->n_knots, log_sp->n_der);
+  }
+  if (lds * sizeof(double) > 64 * 1024) return bad("%s: the staged plan, samples and log scratch exceed 64 KiB of LDS", who);
+  if (!b) return bad("null handle");
+  TRY(check_plan_in_x(b, who, plan));
+  for (int o = 0; o < 3; ++o)
+    if (!in_p(b, sp->p_off[o], 2)) return bad("%s: p_off[%d] = %d outside p", who, o, sp->p_off[o]);
+  if (with_plant && !in_p(b, sp->p_poseT, 2)) return bad("%s: p_poseT = %d outside p", who, sp->p_poseT);
+  if (!in_p(b, sp->p_t, 1)) return bad("%s: p_t = %d outside p", who, sp->p_t);
+  *pl = QuadPlantArgs{};
+  put_plan(*pl, plan);
+  pl->state = sp->state; pl->state_prev = sp->state_prev; pl->input_last = sp->input_last; pl->dspl_last = sp->dspl_last; pl->dist = sp->dist;
+  pl->n_upd = sp->n_upd; pl->overflow = sp->overflow; pl->under_way = sp->under_way; pl->log_state = sp->log_state; pl->log_input = sp->log_input;
+  pl->n_samp = sp->n_samp; pl->max_updates = sp->max_updates; pl->p_t = sp->p_t; pl->p_poseT = sp->p_poseT;
+  for (int o = 0; o < 3; ++o) pl->p_off[o] = sp->p_off[o];
+  pl->sample_time = sp->sample_time; pl->stop_tol = sp->stop_tol; pl->g = sp->g;
+  *sg = SignalArgs{};
+  return log_sp ? fill_signals(b, log_sp, sg) : OMGX_OK;
+}
+}  // namespace
+
+int omgx_batch_plant_quadrotor_simulate(omgx_batch* b, const double* x, const double* p, const omgx_quad_plant_spec* sp,
+                                        const omgx_signals_spec* log_sp) {
+  if (!x || !p || !sp) return bad("plant_quadrotor_simulate: null x / p / specification");
+  QuadPlantArgs pl; SignalArgs sg;
+  TRY(fill_quad_plant(b, "plant_quadrotor_simulate", sp, log_sp, true, &pl, &sg));
+  const size_t lds = (quad_plant_lds_doubles(pl.degree, pl.n_knots, pl.n_samp) +
+                      (sg.log ? sample_scratch_doubles(sg.n_spl, sg.degree, sg.n_knots, sg.n_der) : 0)) * sizeof(double);
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(plant_quadrotor_simulate_kernel, dim3(b->n_agents), dim3(64), lds, b->stream, x, b->dims.n_var, p, b->dims.n_par, pl, sg);
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
+int omgx_batch_plant_quadrotor_predict(omgx_batch* b, const double* x, double* p, double tau, double t_value, const omgx_quad_plant_spec* sp,
+                                       const double* states, const int32_t* fresh, int32_t enforce) {
+  if (!x || !p || !sp) return bad("plant_quadrotor_predict: null x / p / specification");
+  if (!states && (fresh || enforce)) return bad("plant_quadrotor_predict: fresh / enforce go with states");
+  if (tau != tau || t_value != t_value) return bad("plant_quadrotor_predict: tau / t_value is not a number");
+  omgx_quad_plant_spec spec = *sp;
+  spec.log_state = spec.log_input = nullptr;      // (the simulate's: not read here)
+  QuadPlantArgs pl; SignalArgs sg;
+  TRY(fill_quad_plant(b, "plant_quadrotor_predict", &spec, nullptr, states == nullptr, &pl, &sg));
+  HIPCHK(hipSetDevice(b->device));
+  const int32_t* oi = b->pend_iters; int32_t* oo = b->pend_order;
+  b->pend_iters = nullptr; b->pend_order = nullptr;
+  hipLaunchKernelGGL(plant_quadrotor_predict_kernel, dim3(b->n_agents + (oi ? 1 : 0)), dim3(64),
+                     quad_plant_lds_doubles(pl.degree, pl.n_knots, pl.n_samp) * sizeof(double), b->stream, x, b->dims.n_var, p, b->dims.n_par,
+                     b->n_agents, pl, tau, t_value, states, fresh, enforce ? 1 : 0, oi, oo, (const double*)(b->order_dw ? b->d_dw : nullptr));
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
+namespace {
 // An obstacle script -> the block the kernels read.  The checks that need no handle come first; `who` names the entry.
 int fill_script(const omgx_batch* b, const char* who, const omgx_obstacle_script* sp, ObstacleScriptArgs* a) {
   if (!sp->time || !sp->what || !sp->value || !sp->obst) return bad("%s: null time / what / value / obst", who);

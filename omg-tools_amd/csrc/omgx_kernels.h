@@ -738,14 +738,19 @@ predict_kernel(const double* __restrict__ x, int n_var, double* __restrict__ p, 
 // linearly between the samples (the reference integrates with odeint on a linear interpolation of the sampled inputs,
 // `vehicle.py:412-423`), the position of the integrated state into spl0, the plan's own derivatives at tau into
 // dspl0 / ddspl0 (`quadrotor.py:110-114`: only state[:2] of the prediction enters the parameters).
-__device__ __forceinline__ void quad_inputs(const double* cx, const double* cy, const PredictArgs& a, double u, double g, double* u1, double* u2) {
-  const int j = span_of(a.knots.k, a.degree, a.n_knots, u);
-  const double s2 = a.inv_T * a.inv_T, s3 = s2 * a.inv_T;
-  const double ddx = spline_der_at(cx, a.knots.k, a.degree, j, u, 2) * s2, ddy = spline_der_at(cy, a.knots.k, a.degree, j, u, 2) * s2;
-  const double dddx = spline_der_at(cx, a.knots.k, a.degree, j, u, 3) * s3, dddy = spline_der_at(cy, a.knots.k, a.degree, j, u, 3) * s3;
+// (kk: the knots, wherever they lie -- the kernel argument, or LDS for the plant kernels below)
+__device__ __forceinline__ void quad_inputs(const double* cx, const double* cy, const double* kk, int degree, int n_knots, double inv_T, double u,
+                                            double g, double* u1, double* u2) {
+  const int j = span_of(kk, degree, n_knots, u);
+  const double s2 = inv_T * inv_T, s3 = s2 * inv_T;
+  const double ddx = spline_der_at(cx, kk, degree, j, u, 2) * s2, ddy = spline_der_at(cy, kk, degree, j, u, 2) * s2;
+  const double dddx = spline_der_at(cx, kk, degree, j, u, 3) * s3, dddy = spline_der_at(cy, kk, degree, j, u, 3) * s3;
   const double n2 = (ddy + g) * (ddy + g) + ddx * ddx;
   *u1 = sqrt(n2);
   *u2 = (dddx * (ddy + g) - ddx * dddy) / n2;
+}
+__device__ __forceinline__ void quad_inputs(const double* cx, const double* cy, const PredictArgs& a, double u, double g, double* u1, double* u2) {
+  quad_inputs(cx, cy, a.knots.k, a.degree, a.n_knots, a.inv_T, u, g, u1, u2);
 }
 
 __device__ __forceinline__ void quad_ode(const double* s, double u1, double u2, double g, double* k) {
@@ -1128,6 +1133,235 @@ feedback_predict_kernel(const double* __restrict__ x, int n_var, double* __restr
   const int b = blockIdx.x;
   if (b >= B) return;
   feedback_predict_agent(fb, b, x + (size_t)b * n_var + fb.coeff_off, p + (size_t)b * n_par, tau, t_value, lds);
+}
+
+// ---------------------------------------------------------------------------
+// The Quadrotor's plant (omgx_batch_plant_quadrotor_simulate / _predict; include/omgx.h OMGX_HAS_PLANT_QUADROTOR states the
+// semantics): `Vehicle.simulate` / `Vehicle.predict` of the reference with the model's own `ode` (`vehicles/quadrotor.py:149-152`) and
+// `Quadrotor.check_terminal_conditions` (104-110).  Stand-alone launches only, one workgroup of 64 threads per agent, shaped like
+// feedback_predict_kernel: knots and plan staged in LDS, lane i <= n_samp evaluates the inputs of sample i (quad_inputs: a function
+// of its arguments alone), one owner lane walks the Runge-Kutta chain in index order, lanes write the log columns.  The arguments
+// travel by value: every pointer is a kernel argument.
+// ---------------------------------------------------------------------------
+struct QuadPlantArgs {
+  double* state; double* state_prev;                          // [B, 5]
+  double* input_last; double* dspl_last;                      // [B, 2]
+  const double* dist;                                         // [B, 2, max_updates, n_samp + 1] or nullptr
+  int32_t* n_upd; int32_t* overflow; int32_t* under_way;      // [B]; overflow / under_way may be nullptr
+  double* log_state; double* log_input;                       // [B, 5, cap], [B, 2, cap] next to the spline log, or nullptr
+  int coeff_off, n_spl, degree, n_knots, n_samp, max_updates, p_t, p_poseT, p_off[3];
+  double sample_time, inv_T, stop_tol, g;
+  KnotArg knots;
+};
+
+// LDS doubles behind the staged knots and plan: inputs [2][n_samp + 1], state samples [5][n_samp + 1], the nominal inputs of sample 0 [2]
+__host__ __device__ inline size_t quad_plant_lds_doubles(int degree, int n_knots, int n_samp) {
+  return plant_stage_doubles(2, degree, n_knots) + 7 * ((size_t)n_samp + 1) + 2;
+}
+
+// abscissa of sample i of the update solved at t_rel: one statement for simulate and predict (the same bits)
+__device__ __forceinline__ double quad_sample_u(const QuadPlantArgs& pl, double t_rel, int i) {
+#pragma clang fp contract(off)
+  return (t_rel + i * pl.sample_time) * pl.inv_T;
+}
+
+// the plan's own state at u: (x, y, dx, dy, atan2(ddx, ddy + g)) (`quadrotor.py:136-140`); kk, cx, cy: LDS
+__device__ __forceinline__ void quad_plan_state(const QuadPlantArgs& pl, const double* kk, const double* cx, const double* cy, double u, double* s) {
+  const int j = span_of(kk, pl.degree, pl.n_knots, u);
+  const double s2 = pl.inv_T * pl.inv_T;
+  s[0] = spline_der_at(cx, kk, pl.degree, j, u, 0);
+  s[1] = spline_der_at(cy, kk, pl.degree, j, u, 0);
+  s[2] = spline_der_at(cx, kk, pl.degree, j, u, 1) * pl.inv_T;
+  s[3] = spline_der_at(cy, kk, pl.degree, j, u, 1) * pl.inv_T;
+  s[4] = atan2(spline_der_at(cx, kk, pl.degree, j, u, 2) * s2, spline_der_at(cy, kk, pl.degree, j, u, 2) * s2 + pl.g);
+}
+
+// one sample interval of the chain: the stage statements of predict_quadrotor_kernel, every product and sum rounded on its own
+__device__ __forceinline__ void quad_rk4_step(double* s, double u1a, double u2a, double u1b, double u2b, double h, double g) {
+#pragma clang fp contract(off)
+  double k1[5], k2[5], k3[5], k4[5], st[5];
+  const double u1m = 0.5 * (u1a + u1b), u2m = 0.5 * (u2a + u2b);
+  quad_ode(s, u1a, u2a, g, k1);
+#pragma unroll
+  for (int q = 0; q < 5; ++q) st[q] = s[q] + 0.5 * h * k1[q];
+  quad_ode(st, u1m, u2m, g, k2);
+#pragma unroll
+  for (int q = 0; q < 5; ++q) st[q] = s[q] + 0.5 * h * k2[q];
+  quad_ode(st, u1m, u2m, g, k3);
+#pragma unroll
+  for (int q = 0; q < 5; ++q) st[q] = s[q] + h * k3[q];
+  quad_ode(st, u1b, u2b, g, k4);
+#pragma unroll
+  for (int q = 0; q < 5; ++q) s[q] += (h / 6.0) * (k1[q] + 2.0 * k2[q] + 2.0 * k3[q] + k4[q]);
+}
+
+// simulate: the vehicle of agent blockIdx.x travels the update just solved.  sg.log == nullptr: no log.  Dynamic LDS:
+// sample_scratch_doubles() (with a log) + quad_plant_lds_doubles() doubles.
+__global__ void __launch_bounds__(64)
+plant_quadrotor_simulate_kernel(const double* __restrict__ x, int n_var, const double* __restrict__ p, int n_par, QuadPlantArgs pl, SignalArgs sg) {
+  extern __shared__ __align__(16) double lds[];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (pl.under_way && pl.under_way[b] == 0) return;
+  const int nu = pl.n_upd[b];      // (every thread reads n_upd[b] / count[b]; lane 0 moves them behind the last barrier)
+  if (nu < 0 || nu >= pl.max_updates) {      // (the same branch in every thread) no disturbance block left
+    if (lane == 0 && pl.overflow) pl.overflow[b] = 1;
+    return;
+  }
+  const int n_samp = pl.n_samp, n_u = n_samp + 1, L = pl.n_knots - pl.degree - 1;
+  int cnt = 0, first = 1, n_col = 0;
+  bool log_on = sg.log != nullptr;
+  if (log_on) {
+    cnt = sg.count[b];
+    first = cnt == 0 ? 0 : 1;
+    n_col = n_u - first;
+    if (cnt < 0 || cnt > sg.cap - n_col) {      // the log is full: this append is dropped as a whole, the vehicle travels on
+      if (lane == 0 && sg.overflow) sg.overflow[b] = 1;
+      log_on = false;
+    }
+  }
+  const double* coeffs = x + (size_t)b * n_var + pl.coeff_off;
+  const double t_rel = p[(size_t)b * n_par + pl.p_t];
+  double* stage = lds + (sg.log ? sample_scratch_doubles(sg.n_spl, sg.degree, sg.n_knots, sg.n_der) : 0);
+  plant_stage(pl, coeffs, stage);
+  if (log_on) {
+    // the plan's own columns (the reference's `dspl` / `ddspl` signals), as signals_append_agent writes them
+    sample_agent<double>(coeffs, lds, sg.n_spl, sg.degree, sg.knots, sg.n_knots, sg.n_der, t_rel * sg.inv_T, sg.sample_time * sg.inv_T, sg.inv_T,
+                         sg.cap, first, n_u, sg.log + (size_t)b * sg.n_der * sg.n_spl * sg.cap + (cnt - first), (double*)nullptr);
+  }
+  const double* kk = stage;
+  const double* cx = stage + pl.n_knots;
+  const double* cy = cx + L;
+  double* ua = stage + plant_stage_doubles(2, pl.degree, pl.n_knots);      // [2][n_u] applied inputs
+  double* ss = ua + 2 * n_u;                                                // [5][n_u] state samples
+  double* un0 = ss + 5 * n_u;                                               // [2] nominal inputs of sample 0
+  if (lane < n_u) {
+    double u1, u2;
+    quad_inputs(cx, cy, kk, pl.degree, pl.n_knots, pl.inv_T, quad_sample_u(pl, t_rel, lane), pl.g, &u1, &u2);
+    if (lane == 0) { un0[0] = u1; un0[1] = u2; }
+    if (pl.dist) {
+      const double* db = pl.dist + ((size_t)b * 2 * pl.max_updates + nu) * (size_t)n_u + lane;
+      u1 = u1 + db[0];
+      u2 = u2 + db[(size_t)pl.max_updates * n_u];
+    }
+    ua[lane] = u1; ua[n_u + lane] = u2;
+  }
+  __syncthreads();
+  if (lane == 0) {      // the owner lane: the chain in index order
+    double s[5], s0[5];
+    quad_plan_state(pl, kk, cx, cy, quad_sample_u(pl, t_rel, 0), s0);      // (column 0 of the log; the start of the first simulate)
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+      s[q] = nu == 0 ? s0[q] : pl.state[(size_t)b * 5 + q];
+      pl.state_prev[(size_t)b * 5 + q] = s[q];
+      ss[q * n_u] = s0[q];
+    }
+    for (int i = 0; i < n_samp; ++i) {
+      quad_rk4_step(s, ua[i], ua[n_u + i], ua[i + 1], ua[n_u + i + 1], pl.sample_time, pl.g);
+#pragma unroll
+      for (int q = 0; q < 5; ++q) ss[q * n_u + i + 1] = s[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 5; ++q) pl.state[(size_t)b * 5 + q] = s[q];
+    pl.input_last[(size_t)b * 2] = ua[n_samp];
+    pl.input_last[(size_t)b * 2 + 1] = ua[n_u + n_samp];
+  } else if (lane <= 2) {      // lanes 1, 2: the plan's velocity at the last travelled sample
+    const int k = lane - 1;
+    pl.dspl_last[(size_t)b * 2 + k] = plant_input_at(pl, kk, k ? cy : cx, t_rel, n_samp);
+  }
+  __syncthreads();
+  if (log_on && pl.log_state) {
+    double* ls = pl.log_state + (size_t)b * 5 * sg.cap + (cnt - first);
+    double* li = pl.log_input + (size_t)b * 2 * sg.cap + (cnt - first);
+    for (int e = lane; e < 5 * n_u; e += 64) {
+      const int q = e / n_u, i = e - q * n_u;
+      if (i >= first) ls[(size_t)q * sg.cap + i] = ss[e];
+    }
+    for (int e = lane; e < 2 * n_u; e += 64) {
+      const int q = e / n_u, i = e - q * n_u;
+      if (i >= first) li[(size_t)q * sg.cap + i] = i == 0 ? un0[q] : ua[e];      // (column 0: the plan's sample 0, undisturbed)
+    }
+  }
+  if (lane == 0) {
+    pl.n_upd[b] = nu + 1;
+    if (log_on) sg.count[b] = cnt + n_col;
+  }
+}
+
+// predict + stop test at the head of an update (states == nullptr), or the prediction from measured states [B, 5] (device or pinned
+// host memory: every value is read once, by the owner lane) with a `fresh` mask [B] (nullptr: all) and the `enforce` form.  Reads the
+// OLD plan and the OLD p[p_t], writes spl0 / dspl0 / ddspl0 and the new t into p.  The launch carries the launch order of the next
+// solve as plant_predict_kernel does (block B is not an agent).  Dynamic LDS: quad_plant_lds_doubles() doubles.
+__global__ void __launch_bounds__(64)
+plant_quadrotor_predict_kernel(const double* __restrict__ x, int n_var, double* __restrict__ p, int n_par, int B, QuadPlantArgs pl, double tau,
+                               double t_value, const double* __restrict__ states, const int32_t* __restrict__ fresh_mask, int enforce,
+                               const int32_t* __restrict__ ord_iters, int32_t* __restrict__ ord_out, const double* __restrict__ ord_dw) {
+  extern __shared__ __align__(16) double lds[];
+  if (ord_iters && blockIdx.x == gridDim.x - 1) { order_block(ord_iters, ord_dw, ord_out, B); return; }
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= B) return;
+  double* pb = p + (size_t)b * n_par;
+  int nu = 1;
+  if (!states) {
+    nu = pl.n_upd[b];
+    if (pl.under_way) {
+      bool go = pl.under_way[b] != 0;
+      if (go && nu >= 1) {
+#pragma clang fp contract(off)
+        const double ex = pl.state[(size_t)b * 5] - pb[pl.p_poseT], ey = pl.state[(size_t)b * 5 + 1] - pb[pl.p_poseT + 1];
+        const double vx = pl.dspl_last[(size_t)b * 2], vy = pl.dspl_last[(size_t)b * 2 + 1];
+        const double exx = ex * ex, eyy = ey * ey, vxx = vx * vx, vyy = vy * vy;
+        const double e2 = exx + eyy, v2 = vxx + vyy;
+        if (sqrt(e2) <= pl.stop_tol && sqrt(v2) <= pl.stop_tol) go = false;
+      }
+      __syncthreads();      // (every thread has read the flag before lane 0 clears it)
+      if (!go) {
+        if (lane == 0) pl.under_way[b] = 0;
+        return;
+      }
+    }
+  }
+  const bool fresh = !states || !fresh_mask || fresh_mask[b] != 0;      // (the same branch in every thread of the workgroup)
+  if (states && fresh && enforce) {      // `Quadrotor.set_initial_conditions`: the measured position, at rest
+    if (lane < 2) {
+      pb[pl.p_off[0] + lane] = states[(size_t)b * 5 + lane];
+      pb[pl.p_off[1] + lane] = 0.0;
+      pb[pl.p_off[2] + lane] = 0.0;
+      if (lane == 0) pb[pl.p_t] = t_value;
+    }
+    return;
+  }
+  const double t_rel = pb[pl.p_t];      // (the time the plan was solved at: read by every thread before lane 0 writes the new one)
+  plant_stage(pl, x + (size_t)b * n_var + pl.coeff_off, lds);
+  const int n_samp = pl.n_samp, n_u = n_samp + 1, L = pl.n_knots - pl.degree - 1;
+  const double* kk = lds;
+  const double* cx = lds + pl.n_knots;
+  const double* cy = cx + L;
+  double* ua = lds + plant_stage_doubles(2, pl.degree, pl.n_knots);      // [2][n_u] nominal inputs
+  if (fresh) {
+    if (lane < n_u) quad_inputs(cx, cy, kk, pl.degree, pl.n_knots, pl.inv_T, quad_sample_u(pl, t_rel, lane), pl.g, &ua[lane], &ua[n_u + lane]);
+    __syncthreads();
+    if (lane == 0) {
+      double s[5];
+      if (states || nu >= 1) {
+        const double* src = states ? states + (size_t)b * 5 : pl.state_prev + (size_t)b * 5;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) s[q] = src[q];
+      } else quad_plan_state(pl, kk, cx, cy, quad_sample_u(pl, t_rel, 0), s);      // (no simulate yet: the vehicle stands at the plan's own sample 0)
+      for (int i = 0; i < n_samp; ++i) quad_rk4_step(s, ua[i], ua[n_u + i], ua[i + 1], ua[n_u + i + 1], pl.sample_time, pl.g);
+      pb[pl.p_off[0]] = s[0];
+      pb[pl.p_off[0] + 1] = s[1];
+    }
+  }
+  if (lane >= 2) return;
+  const double* c = lane ? cy : cx;
+  const int j = span_of(kk, pl.degree, pl.n_knots, tau);
+  if (!fresh) pb[pl.p_off[0] + lane] = spline_der_at(c, kk, pl.degree, j, tau, 0);      // (the statements of predict_kernel)
+  double sc = pl.inv_T;
+  for (int o = 1; o < 3; ++o) {
+    pb[pl.p_off[o] + lane] = spline_der_at(c, kk, pl.degree, j, tau, o) * sc;
+    sc *= pl.inv_T;
+  }
+  if (lane == 0) pb[pl.p_t] = t_value;
 }
 
 // ---------------------------------------------------------------------------

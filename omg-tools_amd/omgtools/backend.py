@@ -217,6 +217,17 @@ class CFeedbackSpec(C.Structure):
                 ('sample_time', C.c_double), ('inv_T', C.c_double)]
 
 
+class CQuadPlantSpec(C.Structure):
+    """include/omgx.h omgx_quad_plant_spec"""
+    _fields_ = [('state', C.c_void_p), ('state_prev', C.c_void_p), ('input_last', C.c_void_p), ('dspl_last', C.c_void_p),
+                ('dist', C.c_void_p), ('n_upd', C.c_void_p), ('overflow', C.c_void_p), ('under_way', C.c_void_p),
+                ('log_state', C.c_void_p), ('log_input', C.c_void_p), ('knots', C.c_void_p),
+                ('coeff_off', C.c_int32), ('n_spl', C.c_int32), ('degree', C.c_int32), ('n_knots', C.c_int32),
+                ('n_samp', C.c_int32), ('max_updates', C.c_int32), ('p_t', C.c_int32), ('p_poseT', C.c_int32),
+                ('p_off', C.c_int32 * 3), ('reserved', C.c_int32), ('sample_time', C.c_double), ('inv_T', C.c_double),
+                ('stop_tol', C.c_double), ('g', C.c_double)]
+
+
 class CObstacleScript(C.Structure):
     """include/omgx.h omgx_obstacle_script"""
     _fields_ = [('time', C.c_void_p), ('what', C.c_void_p), ('value', C.c_void_p), ('what_host', C.c_void_p), ('obst', C.c_void_p),
@@ -347,6 +358,8 @@ PROTOTYPES = {
     'omgx_batch_set_plant': (C.c_int, [_H, _PLA, _SIG]),
     'omgx_batch_set_plant_lag': (C.c_int, [_H, _P, _P, _I, _D]),
     'omgx_batch_predict_measured': (C.c_int, [_H, _P, _P, _D, _D, C.POINTER(CFeedbackSpec)]),
+    'omgx_batch_plant_quadrotor_simulate': (C.c_int, [_H, _P, _P, C.POINTER(CQuadPlantSpec), _SIG]),
+    'omgx_batch_plant_quadrotor_predict': (C.c_int, [_H, _P, _P, _D, _D, C.POINTER(CQuadPlantSpec), _P, _P, _I]),
     'omgx_batch_obstacles_advance': (C.c_int, [_H, _P, C.POINTER(CObstacleScript), _D, _D]),
     'omgx_batch_set_obstacle_script': (C.c_int, [_H, C.POINTER(CObstacleScript), _P, _I]),
     'omgx_shift_rows': (C.c_int, [_H, _P, _I, _I, _P, _P, _I, _P, _I]),
@@ -792,6 +805,56 @@ class BatchSolver(object):
                            float(sample_time), float(inv_T))
         _check(self.lib, self.lib.omgx_batch_predict_measured(self._h, x.data_ptr(), p.data_ptr(), float(tau), float(t_value), C.byref(sp)),
                'omgx_batch_predict_measured')
+
+    def _quad_plant_spec(self, coeff_off, n_spl, degree, knots, inv_T, n_samp, sample_time, p_off, p_t, g, state=None, state_prev=None,
+                         input_last=None, dspl_last=None, n_upd=None, overflow=None, dist=None, under_way=None, max_updates=0, p_poseT=0,
+                         stop_tol=0.0, log_state=None, log_input=None):
+        """omgx_quad_plant_spec from device tensors: state / state_prev [B, 5], input_last / dspl_last [B, 2] fp64, n_upd / overflow /
+        under_way [B] int32, dist [B, 2, max_updates, n_samp + 1], log_state [B, 5, cap] / log_input [B, 2, cap] (the plant's arrays
+        may all be None for a prediction from measured states)."""
+        for nm, a, w in (('state', state, 5), ('state_prev', state_prev, 5), ('input_last', input_last, 2), ('dspl_last', dspl_last, 2)):
+            _need(nm, a, (self._B, w), 'float64 device', optional=True)
+        for nm, a in (('n_upd', n_upd), ('overflow', overflow), ('under_way', under_way)):
+            _need(nm, a, (self._B,), 'int32 device', optional=True)
+        _need('dist', dist, (self._B, 2, ('max_updates', max_updates), ('n_samp + 1', int(n_samp) + 1)), 'float64 device', optional=True)
+        _need('log_state', log_state, (self._B, 5, 'cap'), 'float64 device', optional=True)
+        _need('log_input', log_input, (self._B, 2, 'cap'), 'float64 device', optional=True)
+        knots = _host_knots(knots)
+        off = [int(o) for o in p_off]
+        if len(off) != 3:
+            raise ValueError('p_off must be the offsets of spl0, dspl0, ddspl0')
+        sp = CQuadPlantSpec(_ptr(state), _ptr(state_prev), _ptr(input_last), _ptr(dspl_last), _ptr(dist), _ptr(n_upd), _ptr(overflow),
+                            _ptr(under_way), _ptr(log_state), _ptr(log_input), knots.ctypes.data, int(coeff_off), int(n_spl), int(degree),
+                            len(knots), int(n_samp), int(max_updates), int(p_t), int(p_poseT), (C.c_int32 * 3)(*off), 0, float(sample_time),
+                            float(inv_T), float(stop_tol), float(g))
+        sp._keep = (knots, state, state_prev, input_last, dspl_last, n_upd, overflow, dist, under_way, log_state, log_input)
+        return sp
+
+    def plant_quadrotor_simulate(self, x, p, plant, log=None):
+        """The Quadrotors travel the update just solved (include/omgx.h omgx_batch_plant_quadrotor_simulate): x, p device tensors,
+        plant: the keyword arguments of `_quad_plant_spec`, log: those of `_signals_spec` (the spline log) or None."""
+        _need('x', x, (self._B, self.template.n_var), 'float64 device')
+        _need('p', p, (self._B, self.template.n_par), 'float64 device')
+        sp = self._quad_plant_spec(**plant)
+        lg = self._signals_spec(**log) if log is not None else None
+        _check(self.lib, self.lib.omgx_batch_plant_quadrotor_simulate(self._h, x.data_ptr(), p.data_ptr(), C.byref(sp),
+                                                                       C.byref(lg) if lg is not None else None),
+               'omgx_batch_plant_quadrotor_simulate')
+
+    def plant_quadrotor_predict(self, x, p, tau, t_value, plant, states=None, fresh=None, enforce=False):
+        """Initial conditions of the next solve from the Quadrotor's plant and its stop test, or -- states [B, 5] fp64, fresh [B]
+        int32 or None, device or pinned host tensors -- from measured states (include/omgx.h omgx_batch_plant_quadrotor_predict)."""
+        _need('x', x, (self._B, self.template.n_var), 'float64 device')
+        _need('p', p, (self._B, self.template.n_par), 'float64 device')
+        _need('states', states, (self._B, 5), 'float64 device', optional=True)
+        _need('fresh', fresh, (self._B,), 'int32 device', optional=True)
+        for nm, a, pinned_ok in (('x', x, False), ('p', p, False), ('states', states, True), ('fresh', fresh, True)):
+            if a is not None and not (a.is_cuda or (pinned_ok and a.is_pinned())):      # (a pageable host address would fault the kernel)
+                raise ValueError('%s must be a device tensor%s' % (nm, ' or a pinned host tensor' if pinned_ok else ''))
+        sp = self._quad_plant_spec(**plant)
+        _check(self.lib, self.lib.omgx_batch_plant_quadrotor_predict(self._h, x.data_ptr(), p.data_ptr(), float(tau), float(t_value), C.byref(sp),
+                                                                      _ptr(states), _ptr(fresh), int(bool(enforce))),
+               'omgx_batch_plant_quadrotor_predict')
 
     def _script_spec(self, time, what, value, obstacles, what_host=None):
         """omgx_obstacle_script from device tensors: time [B, n_ev] fp64, what [B, n_ev] int32, value [B, n_ev, 3] fp64; obstacles:

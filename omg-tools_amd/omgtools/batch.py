@@ -10,7 +10,7 @@ with a primal-dual warm start.
 Layout: `BatchP2P` states that protocol once -- tables and options from the template, `solve_cold`, `step`, `rollout`, the stop rule,
 the log -- and branches on no executor.  Where the [B, *] arrays live and who computes on them sits behind its hooks (`_allocate,
 _predict, _shift, _solve, _cold, _rollout, _norm, _stop_rule, _signals_alloc, _signals_fused, _signals_append_now,
-_signals_summary, _plant_alloc, _plant_lag, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
+_signals_summary, _zeros, _plant_alloc, _plant_lag, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
 being the allocator / stream only; no data leaves HBM between steps) and `HostP2P` (`ops=<a host solver object>`: the same
 statements in numpy, how the parity tests and the CPU baseline of bench.py replay the loop; this package never imports the
 oracle).  `BatchP2P(problem, P, ops=...)` hands out the executor `ops` names.  The clock of a step is `splines.step_clock`, the
@@ -19,7 +19,8 @@ obstacle motion `splines.advance_obstacles`: shared with the formation loops.
 `BatchP2P.plant` puts a simulated vehicle into the loop (the reference's default `ideal_prediction=False, ideal_update=False`, with an
 optional input disturbance): step (1) then starts the solve from the state the vehicle had one update ago integrated under the planned
 inputs, and after step (3) the vehicle travels the update under the applied inputs (include/omgx.h OMGX_HAS_PLANT has the statements);
-with `time_constant` the vehicle applies them through the reference's first-order actuator lag (OMGX_HAS_PLANT_LAG).
+with `time_constant` the vehicle applies them through the reference's first-order actuator lag (OMGX_HAS_PLANT_LAG); with
+`model='quadrotor'` the vehicle is the Quadrotor's own model, per step (OMGX_HAS_PLANT_QUADROTOR; `feedback(model='quadrotor')` likewise).
 `BatchP2P.feedback` lets `step` take states measured outside the loop instead (`step(states=...)`, the reference's
 `Deployer.update(current_time, states, ...)`; include/omgx.h OMGX_HAS_FEEDBACK): a loop has one source of states.
 `BatchP2P.obstacle_script` moves the obstacles by the reference's `simulation={'trajectories': ...}` -- jumps of position, velocity
@@ -230,7 +231,9 @@ class BatchP2P(object):
                 raise ValueError('step(states=...): the plant is in the loop; a loop has one source of states')
             if inputs is not None and not enforce:
                 raise ValueError('step: inputs are read with enforce=True only')
-            for nm, a, shape in (('states', states, (self.B, self.n_spl)), ('inputs', inputs, (self.B, self.n_spl)), ('fresh', fresh, (self.B,))):
+            if inputs is not None and self._fb.get('model') == 'quadrotor':
+                raise ValueError("step: inputs are not read with model='quadrotor' (`Quadrotor.set_initial_conditions` ignores them)")
+            for nm, a, shape in (('states', states, (self.B, self._state_width())), ('inputs', inputs, (self.B, self.n_spl)), ('fresh', fresh, (self.B,))):
                 if a is not None and tuple(a.shape) != shape:
                     raise ValueError('step: %s must be %s, got %s' % (nm, list(shape), list(a.shape)))
         t_now, tau, t_rel, crossed = step_clock(self.time, self.update_time, self.knot_time, self.T)
@@ -263,6 +266,8 @@ class BatchP2P(object):
         travelled state, input disturbance, stop test on the travelled state: a disturbance study of a whole fleet in one launch.  A
         deployment that feeds states measured outside back steps with `step` (`feedback`, `step(states=...)`): a rollout takes none.
         Returns the number of knot crossings."""
+        if self._pl is not None and self._pl.get('model') == 'quadrotor':
+            raise NotImplementedError("rollout: the Quadrotor's plant runs per step only (`step`): the rollout kernel has no instance for it")
         clock, t, t_abs = [], self.time, [self.time]
         for _ in range(int(n_steps)):
             t, tau, t_rel, crossed = step_clock(t, self.update_time, self.knot_time, self.T)
@@ -381,9 +386,14 @@ class BatchP2P(object):
         `vehicles/vehicle.py:72`) on the state the last prediction wrote into p -- the state the vehicle is in at the time of
         the current update (with `step(states=...)`: the state predicted from the measurement, or the enforced one) -- or, after `plant`,
         on the travelled state and the last applied input.  Boolean tensor (device loop) / array (host loop); the reference's `Simulator.run` ends a vehicle's
-        loop at the first update for which this holds (`execution/simulator.py:39-62`).  Point-mass classes (state0 / input0 / poseT)."""
-        st, inp, pose = (self.p[:, o:o + self.n_dim] for o in (self.o_state0, self.o_input0, self._o_pose('arrived')))
+        loop at the first update for which this holds (`execution/simulator.py:39-62`).  Point-mass classes (state0 / input0 / poseT);
+        with `plant(model='quadrotor')` the Quadrotor's own rule (`vehicles/quadrotor.py:104-110`): the travelled position against poseT
+        and the plan's velocity at the last travelled sample."""
         pl = getattr(self, '_pl', None)
+        if pl is not None and pl.get('model') == 'quadrotor':
+            pose = self.p[:, pl['o_pose']:pl['o_pose'] + 2]
+            return (self._norm(pl['state'][:, :2] - pose) <= stop_tol) & (self._norm(pl['dspl_last']) <= stop_tol)
+        st, inp, pose = (self.p[:, o:o + self.n_dim] for o in (self.o_state0, self.o_input0, self._o_pose('arrived')))
         if pl is not None:      # (with the plant in the loop: the travelled state and the last applied input, `signals[...][:, -1]`)
             st, inp = pl['state'], pl['input_last']
         return (self._norm(st - pose) <= stop_tol) & (self._norm(inp) <= stop_tol)
@@ -397,7 +407,10 @@ class BatchP2P(object):
         loop inside the launch ends at the step its state meets the criterion (its plan stays as it is at that step).  With
         `step(states=...)` the rule still tests p[state0], p[input0]: now the state predicted from the measurement (or the enforced
         state and input), not the measurement itself."""
-        o_pose = self._o_pose('stop_at_arrival') if on else None
+        if on and self._pl is not None and self._pl.get('model') == 'quadrotor':
+            o_pose = self._pl['o_pose']                     # (the rule of `plant(model='quadrotor')`, on the travelled state)
+        else:
+            o_pose = self._o_pose('stop_at_arrival') if on else None
         if on:
             self.stop_tol = float(stop_tol)
         self._stop_rule(o_pose)
@@ -442,7 +455,57 @@ class BatchP2P(object):
             self._signals_append_now()
 
     # -- the plant in the loop --------------------------------------------------------------------
-    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True, time_constant=None):
+    def _quad_model(self, who, model):
+        """The check behind `plant(model=...)` / `feedback(model=...)`: the one model there is, on a class that can carry it."""
+        if model != 'quadrotor':
+            raise ValueError("%s: model must be None (an integrator class) or 'quadrotor', got %r" % (who, model))
+        lay, label = self.tpl.par_layout, self.veh.label
+        if any((label, nm) not in lay for nm in ('spl0', 'dspl0', 'ddspl0', 'poseT')) or self.n_spl != 2 or self.basis.degree < 3:
+            raise ValueError("%s: model='quadrotor' needs the parameters spl0 / dspl0 / ddspl0 / poseT, two splines and degree >= 3; %s has "
+                             'n_spl = %d, degree = %d' % (who, label, self.n_spl, self.basis.degree))
+
+    def _state_width(self):
+        """Entries of a measured state in `step(states=...)`: n_spl for the integrator classes, 5 with `feedback(model='quadrotor')`."""
+        return 5 if self._fb is not None and self._fb.get('model') == 'quadrotor' else self.n_spl
+
+    def _plant_quadrotor(self, sample_time, max_updates, disturbance, time_constant, gravity):
+        """`plant(model='quadrotor')`: the Quadrotor's own model in the loop (include/omgx.h OMGX_HAS_PLANT_QUADROTOR)."""
+        self._quad_model('plant', 'quadrotor')
+        if time_constant is not None:
+            raise NotImplementedError("plant(): the first-order actuator lag is not simulated with model='quadrotor'")
+        if self._plan_ready:
+            raise RuntimeError('plant(): the vehicle starts from the first plan -- call it before solve_cold')
+        n_samp = int(round(self.update_time / float(sample_time), 6))
+        if n_samp < 1 or int(max_updates) < 1:
+            raise ValueError('plant: sample_time must not exceed update_time and max_updates must be positive')
+        if n_samp + 1 > 64:
+            raise ValueError("plant: model='quadrotor' takes at most 63 samples per update, got %d" % n_samp)
+        if not float(gravity) > 0.0:
+            raise ValueError('plant: gravity must be positive')
+        for what, g in (('log is kept', self._sig), ('measured states are integrated', self._fb)):
+            if g is not None and g['sample_time'] != float(sample_time):
+                raise ValueError('plant: the %s with sample_time %g' % (what, g['sample_time']))
+        shape = (self.B, 2, int(max_updates), n_samp + 1)
+        if disturbance is not None and tuple(disturbance.shape) != shape:
+            raise ValueError('plant: disturbance must be [B, 2, max_updates, n_samp + 1] = %s, got %s' % (shape, tuple(disturbance.shape)))
+        pl = dict(sample_time=float(sample_time), n_samp=n_samp, max_updates=int(max_updates), lag=None, model='quadrotor', g=float(gravity),
+                  o_pose=self.tpl.entry_range(self.veh.label, 'poseT', 'par')[0])
+        pl.update(self._plant_alloc(disturbance, 'quadrotor'))
+        self._pl = pl
+        self._signals_fused(False)                          # (the simulate writes the log, whichever of `record_signals` and this came first)
+
+    def _plant_log(self):
+        """(state [B, 5, cap], input [B, 2, cap]): the arrays the Quadrotor's simulate logs into next to the spline log, made when the
+        log is first met; (None, None) without a log."""
+        pl, sig = self._pl, self._sig
+        if sig is None:
+            pl.pop('log_state', None), pl.pop('log_input', None)
+            return None, None
+        if 'log_state' not in pl or pl['log_state'].shape[2] != sig['cap']:
+            pl['log_state'], pl['log_input'] = self._zeros((self.B, 5, sig['cap'])), self._zeros((self.B, 2, sig['cap']))
+        return pl['log_state'], pl['log_input']
+
+    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True, time_constant=None, model=None, gravity=9.81):
         """Put a simulated vehicle into every agent's loop, as the reference's `Simulator.run` keeps one with its default options
         `ideal_prediction=False, ideal_update=False` (`vehicles/vehicle.py:73-75`).  From now on, after every solve (`solve_cold`,
         `step`, every step inside a `rollout` launch) the vehicle travels the update under the plan's inputs plus `disturbance`
@@ -463,22 +526,36 @@ class BatchP2P(object):
         reference's: a systematic model mismatch, per agent, for a robustness study of a fleet in one `rollout` launch.  `arrived` /
         `stop_at_arrival` and the log see the lagged input.  The batch reads no vehicle option on its own: a vehicle with
         '1storder_delay' set is refused unless its `time_constant` is passed here.  on=False takes the plant out again, the lag
-        with it."""
+        with it.
+
+        model='quadrotor', gravity=...: the Quadrotor's own model (`vehicles/quadrotor.py:149-152`: state (x, y, dx, dy, theta), inputs
+        thrust and pitch rate as the plan holds them) -- the vehicle travels by classical Runge-Kutta under the linearly interpolated
+        applied inputs, the next solve starts from the position of `state_prev` integrated under the nominal ones, `arrived` /
+        `stop_at_arrival` test the travelled position and the plan's velocity at the last travelled sample (`quadrotor.py:104-110`),
+        and `signals()` gains `state` [B, 5, cap] and `input` [B, 2, cap] (include/omgx.h OMGX_HAS_PLANT_QUADROTOR has the statements).
+        disturbance: [B, 2, max_updates, n_samp + 1].  The batch reads no vehicle option on its own -- a batch from a problem bundle
+        knows neither `ode` nor `g` --, so the model is named here; without `model` a Quadrotor batch is refused as before.  Per step
+        only (`rollout` is refused), no `time_constant`."""
         if not on:
             if self._pl is not None:
+                quad = self._pl.get('model') == 'quadrotor'
                 self._pl = None
                 self._plant_lag(None)
                 self._plant_rollout()
                 if self.under_way is not None:
-                    self._stop_rule(self._o_pose('stop_at_arrival'))
+                    self._stop_rule(None if quad else self._o_pose('stop_at_arrival'))      # (the Quadrotor has no rule without its plant)
                 if self._sig is not None:
                     self._signals_fused(True)
             return
+        if model is not None:
+            self._quad_model('plant', model)
+            return self._plant_quadrotor(sample_time, max_updates, disturbance, time_constant, gravity)
         lay, label = self.tpl.par_layout, self.veh.label
         cls_name = type(self.veh).__name__ if hasattr(self.veh, 'ode') else label
         if any((label, nm) not in lay for nm in ('state0', 'input0', 'poseT')) or self.n_spl != self.n_dim:
             raise NotImplementedError('plant(): %s is not an integrator class (ode = input: Holonomic, Holonomic3D, parameters state0 / '
-                                      'input0 / poseT); its own model is not simulated in the batched loop' % cls_name)
+                                      "input0 / poseT); its own model is not simulated in the batched loop unless it is named: pass "
+                                      "model='quadrotor' for the Quadrotor's" % cls_name)
         if getattr(self.veh, 'options', {}).get('1storder_delay') and time_constant is None:
             raise NotImplementedError("plant(): %s has '1storder_delay' set and the batched loop reads no vehicle option on its own; pass "
                                       "time_constant=vehicle.options['time_constant'] to simulate the first-order actuator lag" % cls_name)
@@ -520,37 +597,52 @@ class BatchP2P(object):
     def plant_state(self):
         """dict `state`, `state_prev`, `input_last` [B, n_spl] (where every vehicle is at its last simulated sample, where it was one
         update earlier, the last applied input), `n_upd` [B] (updates simulated), `overflow` [B] (1: an update beyond `max_updates` was
-        asked for).  Device tensors on the device loop, arrays on the host loop."""
+        asked for).  Device tensors on the device loop, arrays on the host loop.  With `plant(model='quadrotor')`: state / state_prev
+        [B, 5], input_last [B, 2], and `dspl_last` [B, 2], the plan's velocity at the last travelled sample."""
         if self._pl is None:
             raise RuntimeError('plant_state(): call plant() first')
-        return dict((nm, self._pl[nm]) for nm in ('state', 'state_prev', 'input_last', 'n_upd', 'overflow'))
+        names = ('state', 'state_prev', 'input_last', 'n_upd', 'overflow') + (('dspl_last',) if self._pl.get('model') == 'quadrotor' else ())
+        return dict((nm, self._pl[nm]) for nm in names)
 
     # -- states measured outside the loop ------------------------------------------------------------
-    def feedback(self, sample_time=0.01, on=True):
+    def feedback(self, sample_time=0.01, on=True, model=None, gravity=9.81):
         """Let `step` take measured states (`step(states=...)`): the reference's deployment contract, `Deployer.update(current_time,
         states, inputs, ..., enforce_states, enforce_inputs)` -> `Vehicle.predict(state0=...)` (`execution/deployer.py:43-79`,
         `vehicles/vehicle.py:302-337`).  Fixes the sample grid the measured state is integrated on, n_samp = update_time /
         sample_time intervals per update (the trapezoid sum of the plan's inputs: exact for the reference's linearly interpolated
         input).  Integrator classes (`ode` = input: Holonomic, Holonomic3D); a vehicle's '1storder_delay' option changes nothing here
         (`Vehicle.predict(state0=...)` has no lag in it, and the measured vehicle is outside the loop); every agent on the
-        batch's one clock (no `delay`).  `rollout` takes no states.  on=False: `step` takes none again."""
+        batch's one clock (no `delay`).  `rollout` takes no states.  on=False: `step` takes none again.
+        model='quadrotor', gravity=...: the Quadrotor's own model (as `plant(model='quadrotor')`): `step(states=...)` takes [B, 5]
+        states (x, y, dx, dy, theta), integrates them by the Runge-Kutta statements of the plant's prediction and writes the position
+        into spl0, the plan's derivatives into dspl0 / ddspl0; `enforce` is `Quadrotor.set_initial_conditions` (the position, at
+        rest); `inputs` are refused, the reference ignores them."""
         if not on:
             self._fb = None
             return
         lay, label = self.tpl.par_layout, self.veh.label
         cls_name = type(self.veh).__name__ if hasattr(self.veh, 'ode') else label
-        if any((label, nm) not in lay for nm in ('state0', 'input0', 'poseT')) or self.n_spl != self.n_dim:
+        if model is not None:
+            self._quad_model('feedback', model)
+            if not float(gravity) > 0.0:
+                raise ValueError('feedback: gravity must be positive')
+        elif any((label, nm) not in lay for nm in ('state0', 'input0', 'poseT')) or self.n_spl != self.n_dim:
             raise NotImplementedError('feedback(): %s is not an integrator class (ode = input: Holonomic, Holonomic3D, parameters state0 / '
-                                      'input0 / poseT); its own model is not integrated in the batched loop' % cls_name)
+                                      "input0 / poseT); its own model is not integrated in the batched loop unless it is named: pass "
+                                      "model='quadrotor' for the Quadrotor's" % cls_name)
         if getattr(self, 'pool', None) is not None:
             raise NotImplementedError('feedback: not with a host pool (its workers run the step glue themselves)')
         n_samp = int(round(self.update_time / float(sample_time), 6))
         if n_samp < 1:
             raise ValueError('feedback: sample_time must not exceed update_time')
+        if model is not None and n_samp + 1 > 64:
+            raise ValueError("feedback: model='quadrotor' takes at most 63 samples per update, got %d" % n_samp)
         for what, g in (('log', self._sig), ('plant', self._pl)):
             if g is not None and g['sample_time'] != float(sample_time):
                 raise ValueError('feedback: the %s is kept with sample_time %g' % (what, g['sample_time']))
         self._fb = dict(sample_time=float(sample_time), n_samp=n_samp)
+        if model is not None:
+            self._fb.update(model='quadrotor', g=float(gravity))
 
     def signals(self):
         """The log of `record_signals`: dict with `count` [B] (columns written per agent), `time` [cap] (the time of the first logged
@@ -567,6 +659,9 @@ class BatchP2P(object):
         if (self.veh.label, 'state0') in self.tpl.par_layout:
             for o, nm in enumerate(('state', 'input', 'dinput')[:g['n_der']]):
                 out[nm] = g['log'][:, o]
+        if self._pl is not None and self._pl.get('model') == 'quadrotor':
+            # (the Quadrotor's travelled state [B, 5, cap] and applied input [B, 2, cap], at the columns of `splines`)
+            out['state'], out['input'] = self._plant_log()
         return out
 
     def summary(self):
@@ -740,13 +835,28 @@ class DeviceP2P(BatchP2P):
         g = self._sig
         self.solver.signals_append(self.x, self.p, g['log'], g['count'], g['overflow'], under_way=self.under_way, **self._signals_args())
 
-    def _plant_alloc(self, disturbance):
+    def _zeros(self, shape):
+        return self.torch.zeros(shape, dtype=self.torch.float64, device=self.dev)
+
+    def _plant_alloc(self, disturbance, model=None):
         t = self.torch
         f64 = dict(dtype=t.float64, device=self.dev)
-        out = dict((nm, t.zeros((self.B, self.n_spl), **f64)) for nm in ('state', 'state_prev', 'input_last'))
+        widths = dict(state=5, state_prev=5, input_last=2, dspl_last=2) if model == 'quadrotor' else \
+            dict((nm, self.n_spl) for nm in ('state', 'state_prev', 'input_last'))
+        out = dict((nm, t.zeros((self.B, w), **f64)) for nm, w in widths.items())
         out.update((nm, t.zeros(self.B, dtype=t.int32, device=self.dev)) for nm in ('n_upd', 'overflow'))
         out['dist'] = None if disturbance is None else t.as_tensor(disturbance, **f64).contiguous()
         return out
+
+    def _quad_args(self, g, plant=True, log=False):
+        """The keyword arguments of `BatchSolver._quad_plant_spec`: g = the plant (`self._pl`) or the feedback grid (`self._fb`)."""
+        kw = dict(self._plan, n_samp=g['n_samp'], sample_time=g['sample_time'], p_off=self.p_offs, p_t=self.o_t, g=g['g'])
+        if plant:
+            kw.update(dict((nm, g[nm]) for nm in ('state', 'state_prev', 'input_last', 'dspl_last', 'n_upd', 'overflow', 'dist')),
+                      under_way=self.under_way, max_updates=g['max_updates'], p_poseT=g['o_pose'], stop_tol=self.stop_tol)
+        if log:
+            kw['log_state'], kw['log_input'] = self._plant_log()
+        return kw
 
     def _plant_args(self):
         g = self._pl
@@ -762,6 +872,8 @@ class DeviceP2P(BatchP2P):
         # (as `_predict`: the launch carries the ordering of the next solve as one more workgroup)
         if self.straggler_first:
             self.solver.order_by_iters(self.iters, self._order)
+        if self._pl.get('model') == 'quadrotor':
+            return self.solver.plant_quadrotor_predict(self.x, self.p, tau, t_rel, self._quad_args(self._pl))
         self.solver.plant_predict(self.x, self.p, tau, t_rel, self._plant_args())
 
     def _feedback_predict(self, tau, t_rel, states, inputs, fresh, enforce):
@@ -777,10 +889,15 @@ class DeviceP2P(BatchP2P):
         if self.straggler_first:
             self.solver.order_by_iters(self.iters, self._order)
         g = self._fb
+        if g.get('model') == 'quadrotor':
+            return self.solver.plant_quadrotor_predict(self.x, self.p, tau, t_rel, self._quad_args(g, plant=False), states=states, fresh=fresh,
+                                                       enforce=enforce)
         self.solver.predict_measured(self.x, self.p, tau, t_rel, states, input=inputs, fresh=fresh, enforce=enforce, n_samp=g['n_samp'],
                                      sample_time=g['sample_time'], p_off=self.p_offs, p_t=self.o_t, **self._plan)
 
     def _plant_simulate(self):
+        if self._pl.get('model') == 'quadrotor':
+            return self.solver.plant_quadrotor_simulate(self.x, self.p, self._quad_args(self._pl, log=True), self._plant_log_args())
         self.solver.plant_simulate(self.x, self.p, self._plant_args(), self._plant_log_args())
 
     def _plant_lag(self, pl):
@@ -947,10 +1064,15 @@ class HostP2P(BatchP2P):
         return cnt - first
 
     # -- the plant: `omgx_batch_plant_simulate / _predict` in numpy, the same statements in the same summation order ---------------
-    def _plant_alloc(self, disturbance):
+    def _zeros(self, shape):
+        return np.zeros(shape)
+
+    def _plant_alloc(self, disturbance, model=None):
         if self.pool is not None:
             raise NotImplementedError('plant: not with a host pool (its workers run the step glue themselves)')
-        out = dict((nm, np.zeros((self.B, self.n_spl))) for nm in ('state', 'state_prev', 'input_last'))
+        widths = dict(state=5, state_prev=5, input_last=2, dspl_last=2) if model == 'quadrotor' else \
+            dict((nm, self.n_spl) for nm in ('state', 'state_prev', 'input_last'))
+        out = dict((nm, np.zeros((self.B, w))) for nm, w in widths.items())
         out.update((nm, np.zeros(self.B, dtype=np.int32)) for nm in ('n_upd', 'overflow'))
         out['dist'] = None if disturbance is None else np.ascontiguousarray(disturbance, dtype=float).copy()
         return out
@@ -966,7 +1088,90 @@ class HostP2P(BatchP2P):
         tau = (t_rel + np.arange(g['n_samp'] + 1) * g['sample_time']) * inv_T
         return c, t_rel, c @ (dbasis.eval_basis(tau) @ P1 * inv_T).T
 
+    # -- the Quadrotor's plant: `omgx_batch_plant_quadrotor_simulate / _predict` in numpy (include/omgx.h OMGX_HAS_PLANT_QUADROTOR) -----
+    def _quad_plan(self, b, g):
+        """(c, t_rel, u, s0, d1): the plan of agent b [2, L], the time it was solved at, its inputs (u1, u2) at the samples 0 .. n_samp of
+        the update [2, n_samp + 1], its own state at sample 0 [5] and its velocity at the samples [2, n_samp + 1].  g: whose sample grid
+        and gravity (the plant's or the feedback's)."""
+        inv_T = 1.0 / self.T
+        c = self.x[b, self.o_spl:self.o_spl + 2 * self.L].reshape(2, self.L)
+        t_rel = float(self.p[b, self.o_t])
+        tau = (t_rel + np.arange(g['n_samp'] + 1) * g['sample_time']) * inv_T
+        der = [c @ self.basis.eval_basis(tau).T]
+        for o in (1, 2, 3):
+            dbasis, Po = self.basis.derivative(o)
+            der.append(c @ (dbasis.eval_basis(tau) @ Po).T)
+        s2 = inv_T * inv_T
+        s3 = s2 * inv_T
+        d1, dd, ddd = der[1] * inv_T, der[2] * s2, der[3] * s3
+        u = quad_inputs_numpy(dd, ddd, g['g'])
+        s0 = np.array([der[0][0, 0], der[0][1, 0], d1[0, 0], d1[1, 0], np.arctan2(dd[0, 0], dd[1, 0] + g['g'])])
+        return c, t_rel, u, s0, d1
+
+    def _quad_simulate(self):
+        g, sig = self._pl, self._sig
+        log_state, log_input = self._plant_log()
+        for b in range(self.B):
+            if self.under_way is not None and not self.under_way[b]:
+                continue
+            nu = int(g['n_upd'][b])
+            if nu >= g['max_updates']:
+                g['overflow'][b] = 1
+                continue
+            c, t_rel, u, s0, d1 = self._quad_plan(b, g)
+            a = u + g['dist'][b, :, nu, :] if g['dist'] is not None else u
+            start = s0 if nu == 0 else g['state'][b].copy()
+            samples = quad_rk4_numpy(start, a, g['sample_time'], g['g'])
+            if sig is not None:
+                first = 0 if int(sig['count'][b]) == 0 else 1
+                col = self._signals_append_agent(b)             # (the plan's own columns: the reference's `dspl` / `ddspl` signals)
+                if col is not None:
+                    log_state[b, :, col + 1:col + 1 + g['n_samp']] = samples[:, 1:]
+                    log_input[b, :, col + 1:col + 1 + g['n_samp']] = a[:, 1:]
+                    if first == 0:                              # (column 0: the plan's sample 0, undisturbed)
+                        log_state[b, :, col], log_input[b, :, col] = s0, u[:, 0]
+            g['state_prev'][b], g['state'][b], g['input_last'][b], g['dspl_last'][b] = start, samples[:, -1], a[:, -1], d1[:, -1]
+            g['n_upd'][b] = nu + 1
+
+    def _quad_predict(self, tau, t_rel):
+        g = self._pl
+        if self.under_way is not None:
+            self.under_way &= ~(self.arrived(self.stop_tol) & (g['n_upd'] >= 1))
+        rows = self._eval_rows(tau)
+        for b in range(self.B):
+            if self.under_way is not None and not self.under_way[b]:
+                continue
+            c, _, u, s0, _ = self._quad_plan(b, g)
+            start = g['state_prev'][b] if g['n_upd'][b] >= 1 else s0
+            self._quad_write(b, c, rows, quad_rk4_numpy(start, u, g['sample_time'], g['g'])[:2, -1], t_rel)
+
+    def _quad_write(self, b, c, rows, pos, t_rel):
+        """spl0 <- pos, dspl0 / ddspl0 <- the plan's derivatives (rows: `_eval_rows(tau)`), t <- t_rel."""
+        self.p[b, self.p_offs[0]:self.p_offs[0] + 2] = pos
+        for o in (1, 2):
+            self.p[b, self.p_offs[o]:self.p_offs[o] + 2] = c @ rows[o]
+        self.p[b, self.o_t] = t_rel
+
+    def _quad_feedback_predict(self, tau, t_rel, states, fresh, enforce):
+        g = self._fb
+        states = np.asarray(states, dtype=float)
+        go = np.ones(self.B, dtype=bool) if fresh is None else np.asarray(fresh) != 0
+        new = {}
+        if not enforce:                                   # (ahead of `_predict`: `_quad_plan` reads the time the plan was solved at)
+            for b in np.flatnonzero(go):
+                u = self._quad_plan(b, g)[2]
+                new[b] = quad_rk4_numpy(states[b], u, g['sample_time'], g['g'])[:2, -1]
+        self._predict(tau, t_rel)                         # (an agent without a fresh measurement; dspl0 / ddspl0 / t of every agent)
+        if enforce:
+            self.p[go, self.p_offs[0]:self.p_offs[0] + 2] = states[go, :2]
+            for o in (1, 2):
+                self.p[go, self.p_offs[o]:self.p_offs[o] + 2] = 0.0
+        for b, pos in new.items():
+            self.p[b, self.p_offs[0]:self.p_offs[0] + 2] = pos
+
     def _plant_simulate(self):
+        if self._pl.get('model') == 'quadrotor':
+            return self._quad_simulate()
         g, sig = self._pl, self._sig
         for b in range(self.B):
             if self.under_way is not None and not self.under_way[b]:
@@ -999,6 +1204,8 @@ class HostP2P(BatchP2P):
 
     def _plant_predict(self, tau, t_rel):
         g = self._pl
+        if g.get('model') == 'quadrotor':
+            return self._quad_predict(tau, t_rel)
         if self.under_way is not None:
             self.under_way &= ~(self.arrived(self.stop_tol) & (g['n_upd'] >= 1))
         Ed = self._eval_rows(tau)[1]
@@ -1026,6 +1233,8 @@ class HostP2P(BatchP2P):
     def _feedback_predict(self, tau, t_rel, states, inputs, fresh, enforce):
         """`omgx_batch_predict_measured` in numpy: an agent without a fresh measurement as `_predict`, one with as `_plant_predict`
         with the measured state in the place of `state_prev` (the same statements: the same bits), or the given values (enforce)."""
+        if self._fb.get('model') == 'quadrotor':
+            return self._quad_feedback_predict(tau, t_rel, states, fresh, enforce)
         states = np.asarray(states, dtype=float)
         go = np.ones(self.B, dtype=bool) if fresh is None else np.asarray(fresh) != 0
         st, new = self._fb['sample_time'], {}
@@ -1044,6 +1253,37 @@ class HostP2P(BatchP2P):
 
     def _signals_summary(self, target):
         return signals_summary_numpy(self._sig['log'], self._sig['count'], target, self._sig['sample_time'])
+
+
+def quad_inputs_numpy(dd, ddd, g):
+    """The Quadrotor's inputs (u1, u2) [2, ...] from the plan's second and third time derivatives dd, ddd [2, ...]: the statements of
+    `quad_inputs` (csrc/omgx_kernels.h), which are `vehicles/quadrotor.py:136-139`."""
+    n2 = (dd[1] + g) * (dd[1] + g) + dd[0] * dd[0]
+    return np.array([np.sqrt(n2), (ddd[0] * (dd[1] + g) - dd[0] * ddd[1]) / n2])
+
+
+def quad_ode_numpy(s, u1, u2, g):
+    """`Quadrotor.ode` (`vehicles/quadrotor.py:149-152`): state (x, y, dx, dy, theta), inputs thrust and pitch rate."""
+    return np.array([s[2], s[3], u1 * math.sin(s[4]), u1 * math.cos(s[4]) - g, u2])
+
+
+def quad_rk4_numpy(s0, a, h, g):
+    """State samples 0 .. n [5, n + 1] of the Quadrotor from s0 [5] under the linearly interpolated input samples a [2, n + 1]: classical
+    Runge-Kutta per sample interval, the statements of `quad_rk4_step` (csrc/omgx_kernels.h) in the same order."""
+    n = a.shape[1] - 1
+    out = np.empty((5, n + 1))
+    s = np.array(s0, dtype=float)
+    out[:, 0] = s
+    for i in range(n):
+        u1a, u2a, u1b, u2b = a[0, i], a[1, i], a[0, i + 1], a[1, i + 1]
+        u1m, u2m = 0.5 * (u1a + u1b), 0.5 * (u2a + u2b)
+        k1 = quad_ode_numpy(s, u1a, u2a, g)
+        k2 = quad_ode_numpy(s + 0.5 * h * k1, u1m, u2m, g)
+        k3 = quad_ode_numpy(s + 0.5 * h * k2, u1m, u2m, g)
+        k4 = quad_ode_numpy(s + h * k3, u1b, u2b, g)
+        s = s + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
+        out[:, i + 1] = s
+    return out
 
 
 def signals_summary_numpy(log, count, target, sample_time):
@@ -1169,7 +1409,7 @@ class StreamedP2P(object):
         hooks = before_solve if isinstance(before_solve, (list, tuple)) else [before_solve] * len(self.parts)
         fed = {}
         if states is not None or inputs is not None or fresh is not None or enforce:
-            for nm, a, shape in (('states', states, (self.B, self.parts[0].n_spl)), ('inputs', inputs, (self.B, self.parts[0].n_spl)), ('fresh', fresh, (self.B,))):
+            for nm, a, shape in (('states', states, (self.B, self.parts[0]._state_width())), ('inputs', inputs, (self.B, self.parts[0].n_spl)), ('fresh', fresh, (self.B,))):
                 if a is not None and tuple(a.shape) != shape:
                     raise ValueError('step: %s must be %s, got %s' % (nm, list(shape), list(a.shape)))
             self.fork()
@@ -1191,8 +1431,12 @@ class StreamedP2P(object):
         """`BatchP2P.record_signals` for every sub-batch (each logs on its own stream)."""
         self._each(lambda m: m.record_signals(sample_time, max_updates, on, cap))
 
-    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True, time_constant=None):
+    def plant(self, sample_time=0.01, max_updates=200, disturbance=None, on=True, time_constant=None, model=None, gravity=9.81):
         """`BatchP2P.plant` for every sub-batch, each with its rows of the disturbance and of a per-agent time constant."""
+        if on and model is not None:                         # (ahead of the first sub-batch: a refused call changes none)
+            self.parts[0]._quad_model('plant', model)
+            if time_constant is not None:
+                raise NotImplementedError("plant(): the first-order actuator lag is not simulated with model='quadrotor'")
         tc = None
         if time_constant is not None:
             n = self.bounds[-1][1]
@@ -1202,12 +1446,13 @@ class StreamedP2P(object):
             tc = np.broadcast_to(tc, (n,))
         for (lo, hi), m, st in zip(self.bounds, self.parts, self.streams):
             with self.torch.cuda.stream(st):
-                m.plant(sample_time, max_updates, None if disturbance is None else disturbance[lo:hi], on, None if tc is None else tc[lo:hi])
+                m.plant(sample_time, max_updates, None if disturbance is None else disturbance[lo:hi], on, None if tc is None else tc[lo:hi],
+                        model=model, gravity=gravity)
 
-    def feedback(self, sample_time=0.01, on=True):
+    def feedback(self, sample_time=0.01, on=True, model=None, gravity=9.81):
         """`BatchP2P.feedback` for every sub-batch; `step(states=...)` then hands each its rows."""
         for m in self.parts:
-            m.feedback(sample_time, on)
+            m.feedback(sample_time, on, model=model, gravity=gravity)
 
     def obstacle_script(self, events=None, on=True):
         """`BatchP2P.obstacle_script` for every sub-batch, each with its rows of the events."""
