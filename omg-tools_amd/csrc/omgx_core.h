@@ -1429,8 +1429,11 @@ OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w) {
       continue;
     }
     const WPanel P = wpanel_leaf(Ms[l]);
-    // hyperplane leaves are banded (half bandwidth 5 in reverse Cuthill-McKee order): compile-time band of 8
-    badl |= (kind_bw <= 8) ? wave_ldl<OMGX_WAVE_COLS, 8, true>(koff, P) : wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, true>(koff, P);
+    // hyperplane leaves are banded (half bandwidth 5 in reverse Cuthill-McKee order): the instance of 36 columns and band 5
+    // where the leaf fits it, a compile-time band of 8 on 40 columns for the other banded ones
+    const int leaf_n = __builtin_amdgcn_readfirstlane(Ms[l].nfact);
+    if (wave_leaf_small(leaf_n, kind_bw)) badl |= wave_ldl<OMGX_LEAF_COLS_SMALL, OMGX_LEAF_BW_SMALL, true, 2>(koff, P);
+    else badl |= (kind_bw <= 8) ? wave_ldl<OMGX_WAVE_COLS, 8, true, 2>(koff, P) : wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, true, 2>(koff, P);
     wave_fence();
     const double dl = wave_dinv<true>(w.kkt, P);
     if (lane < P.n) w.dinv[Ms[l].dinv + lane] = dl;
@@ -1542,7 +1545,7 @@ OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w) {
 #ifdef OMGX_PROFILE
     const long long tr0_ = clock64();
 #endif
-    badr = wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, false>(koff, P);
+    badr = wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, false, 1>(koff, P);
 #ifdef OMGX_PROFILE
     if (c.tid() == 0) c.prof[PH_F_SWEEP] += clock64() - tr0_;      // raw root time
 #endif
@@ -1561,7 +1564,7 @@ OMGX_FN int kkt_refactor_root_wave(const C& c, const Dims& d, const Kkt& K, Work
   const int koff = (int)(w.kkt - omgx_lds);
   OMGX_TIC();
   int badr = 0;
-  if (c.wave() == 0) badr = wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, false>(koff, wpanel_root(Ms[d.n_leaf], d.n_root));
+  if (c.wave() == 0) badr = wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, false, 1>(koff, wpanel_root(Ms[d.n_leaf], d.n_root));
   const int bad = c.rmax(badr ? 1.0 : 0.0) > 0.0 ? 2 : 0;
   OMGX_TOC(PH_F_ROOT);
   return bad;
@@ -1613,7 +1616,9 @@ OMGX_FN void kkt_solve_wave(const C& c, const Dims& d, const Kkt& K, Work& w, do
     for (int a = 0; a < nc; ++a) acc = fma(-Wt[a * ld], xg[a], acc);
     const int dv = __builtin_amdgcn_readfirstlane(M.dinv);
     const double dl = w.dinv[dv + j];
-    const double x = wave_bwd<OMGX_WAVE_COLS, true>(koff, P, dl, acc * dl);
+    // (the leaf instance that factorised it, kkt_factor_wave: 36 positions instead of 40 where the leaf has no more)
+    const double x = wave_leaf_small(n, P.bw) ? wave_bwd<OMGX_LEAF_COLS_SMALL, true>(koff, P, dl, acc * dl)
+                                              : wave_bwd<OMGX_WAVE_COLS, true>(koff, P, dl, acc * dl);
     if (lane < n) sol[dv + lane] = x;
     wave_fence();
   }

@@ -31,9 +31,43 @@ __device__ __forceinline__ void wave_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Sign test of a pivot on its two words -- integer arithmetic, so that a wave-uniform pivot (v_readlane leaves it in
+// scalar registers) is judged by the scalar unit, and the flag kept in a scalar register.  The same decision as
+// !(pos ? d > 0.0 : d < 0.0) for every double (+-0, denormals, +-inf and NaN included): with the sign bit flipped where
+// a negative pivot is wanted, d passes iff its sign bit is clear and its magnitude lies in (0, inf] -- k = high word |
+// (low word != 0) orders the magnitudes the way the doubles are ordered wherever it matters (0 -> 0, inf -> 0x7ff00000,
+// every NaN above, a set sign bit above all): wrong iff k - 1 > 0x7fefffff (unsigned).
+//   j, npos, n: column, number of positive pivots, order (pos = j < npos; columns j >= n are padding and raise no flag:
+//   their bound is 0xffffffff, which nothing exceeds).
+// Returns `bad`, set to 1 if the pivot of a live column has the wrong sign.
+// On the device the six instructions are written out: from C the compiler turns every form tried (selects, or compare-free
+// shifts and adds) back into wave-uniform booleans, which it keeps as lane masks and combines on the vector pipe (v_cndmask /
+// v_or / v_cmp around v_rcp_f64, the masks spilled across the column).
+__host__ __device__ __forceinline__ unsigned pivot_wrong_sign(unsigned bad, int hi, int lo, int j, int npos, int n) {
+  const unsigned flip = (unsigned)(npos - 1 - j) & 0x80000000u;          // j >= npos: a negative pivot is wanted
+  const unsigned lim = j < n ? 0x7fefffffu : 0xffffffffu;
+#if defined(__HIP_DEVICE_COMPILE__)
+  unsigned w, t;
+  // (both are wave-uniform; where the compiler has them in a vector register all the same, an "s" operand is not moved for us)
+  const unsigned flip_s = __builtin_amdgcn_readfirstlane(flip), lim_s = __builtin_amdgcn_readfirstlane(lim);
+  asm("s_min_u32 %2, %4, 1\n\t"               // low word != 0
+      "s_xor_b32 %1, %3, %5\n\t"
+      "s_or_b32 %1, %1, %2\n\t"               // k
+      "s_add_u32 %1, %1, -1\n\t"
+      "s_cmp_gt_u32 %1, %6\n\t"
+      "s_cselect_b32 %0, 1, %0"
+      : "+s"(bad), "=&s"(w), "=&s"(t) : "s"(hi), "s"(lo), "s"(flip_s), "s"(lim_s) : "scc");
+  return bad;
+#else
+  const unsigned k = ((unsigned)hi ^ flip) | (lo != 0 ? 1u : 0u);
+  return (k - 1u > lim) ? 1u : bad;
+#endif
+}
+
 // A panel of the KKT store as one wave sees it.  Rows [0, n): the symmetric block (lower part stored);
 // rows [n, nreg): carried rows held one per lane; rows [nreg, nreg + nvec): carried rows held as lane
-// vectors.  Pivots j < npos must be positive, the others negative.  Two storage forms:
+// vectors (nvec <= the NVEC of the wave_ldl instance the panel goes through: a leaf has two, the root one).
+// Pivots j < npos must be positive, the others negative.  Two storage forms:
 //   packed (root block, band < 0): row r starts at base + r (r + 1) / 2;
 //   banded (leaf panels, band >= 0): row i of the symmetric block keeps its entries (i, i - band) .. (i, i) at
 //     base + i * ldb (a leaf in reverse Cuthill-McKee order has no fill outside its band), the carried rows are
@@ -53,6 +87,12 @@ __device__ __forceinline__ WPanel wpanel_uniform(const WPanel& Q) {
   P.ldb = __builtin_amdgcn_readfirstlane(Q.ldb); P.wbase = __builtin_amdgcn_readfirstlane(Q.wbase);
   return P;
 }
+
+// The leaf instances sized to the hyperplane leaves of the headline class (order 36, half bandwidth 5 in reverse
+// Cuthill-McKee order): a leaf takes them iff it fits both bounds (n, bw: wave-uniform descriptor fields).
+#define OMGX_LEAF_COLS_SMALL 36
+#define OMGX_LEAF_BW_SMALL   5
+__host__ __device__ __forceinline__ bool wave_leaf_small(int n, int bw) { return n <= OMGX_LEAF_COLS_SMALL && bw <= OMGX_LEAF_BW_SMALL; }
 
 // start of carried row r >= n (a dense row of n entries)
 template <bool BANDED>
@@ -88,9 +128,15 @@ extern __shared__ double omgx_lds[];
 //     garbage then, but nothing traps).
 // On return the panel holds U = L D (rows < n, lower part and diagonal) / W = B L^{-T} (carried rows), the
 // vector rows are stored forward-substituted.  Returns 1 if a pivot had the wrong sign.  `off`: offset of
-// the KKT store in the dynamic LDS (doubles).  BANDED: storage form of the panel (WPanel).
-template <int NC, int BW, bool BANDED>
+// the KKT store in the dynamic LDS (doubles).  BANDED: storage form of the panel (WPanel).  NVEC: vector rows the instance
+// carries (1: the root, which has its right-hand side alone; 2: a leaf) -- a row it does not carry costs nothing.
+// Instances: <40, 40, false, 1> the root; <40, 40, true, 2> and <40, 8, true, 2> leaves of any order / of half bandwidth
+// <= 8; <36, 5, true, 2> hyperplane leaves of order <= 36 and half bandwidth <= 5 (wave_leaf_small: the headline class --
+// four columns, and three broadcast-and-FMA pairs per pivot, fewer than <40, 8>; the entries skipped are exact zeros of
+// the band, so every stored entry sees the same operands in the same order).
+template <int NC, int BW, bool BANDED, int NVEC>
 __device__ __forceinline__ int wave_ldl(int off, const WPanel Pin) {
+  static_assert(NC % 4 == 0 && NVEC >= 1 && NVEC <= 2, "columns go in chunks of four; one or two vector rows");
   const double* A = omgx_lds + off;
   double* Aw = omgx_lds + off;
   const WPanel P = wpanel_uniform(Pin);
@@ -110,20 +156,25 @@ __device__ __forceinline__ int wave_ldl(int off, const WPanel Pin) {
     const double v = A[ra + kk];
     a[k] = (has_row && k >= klo && k <= khi) ? v : 0.0;
   }
-  const int v0a = wcarried<BANDED>(P, P.vrow), v1a = wcarried<BANDED>(P, P.vrow + (P.nvec > 1 ? 1 : 0));
-  double yv0, yv1;
+  const int v0a = wcarried<BANDED>(P, P.vrow), v1a = wcarried<BANDED>(P, P.vrow + (NVEC > 1 && P.nvec > 1 ? 1 : 0));
+  double yv0, yv1 = 0.0;
   {
     const int c = sym_row ? lane : 0;
-    const double v0 = A[v0a + c], v1 = A[v1a + c];
+    const double v0 = A[v0a + c];
     yv0 = (P.nvec > 0 && sym_row) ? v0 : 0.0;
-    yv1 = (P.nvec > 1 && sym_row) ? v1 : 0.0;
+    if (NVEC > 1) {
+      const double v1 = A[v1a + c];
+      yv1 = (P.nvec > 1 && sym_row) ? v1 : 0.0;
+    }
   }
-  int bad = 0;
+  unsigned bad = 0;
 #pragma unroll
   for (int j = 0; j < NC; ++j) {
-    const double dj = readlane_d(a[j], j);
-    const bool okp = (j < P.npos) ? (dj > 0.0) : (dj < 0.0);
-    bad |= (j < n && !okp) ? 1 : 0;                    // (columns >= n: padding, whatever they compute is never stored)
+    // the pivot as the two scalar words the broadcast leaves: its sign is tested on the scalar unit, beside the chain
+    // (rcp -> l_ij -> the FMAs of the column) and not in front of it
+    const int dlo = __builtin_amdgcn_readlane(__double2loint(a[j]), j), dhi = __builtin_amdgcn_readlane(__double2hiint(a[j]), j);
+    const double dj = __hiloint2double(dhi, dlo);
+    bad = pivot_wrong_sign(bad, dhi, dlo, j, P.npos, n);      // (columns >= n: padding, whatever they compute is never stored)
     const double inv = rcp_pivot(dj);
     const double li = a[j] * inv;                      // l_ij of every row i > j (lanes <= j: unused upper part)
     {
@@ -132,9 +183,12 @@ __device__ __forceinline__ int wave_ldl(int off, const WPanel Pin) {
       asm volatile("" : "+v"(ln));
       const double lm = ln > j ? li : 0.0;
       // (columns >= n broadcast zero: their garbage may hold NaN, and 0 * NaN would reach the real lanes)
-      const double y0j = readlane_d(yv0, j), y1j = readlane_d(yv1, j);
+      const double y0j = readlane_d(yv0, j);
       yv0 = fma(-lm, j < n ? y0j : 0.0, yv0);
-      yv1 = fma(-lm, j < n ? y1j : 0.0, yv1);
+      if (NVEC > 1) {
+        const double y1j = readlane_d(yv1, j);
+        yv1 = fma(-lm, j < n ? y1j : 0.0, yv1);
+      }
     }
 #pragma unroll
     for (int c = j / 4; c < NC / 4; ++c) {             // columns in chunks of four
@@ -156,16 +210,18 @@ __device__ __forceinline__ int wave_ldl(int off, const WPanel Pin) {
       for (int k = 0; k < NC; ++k) {
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        // (a row of the symmetric block: its stored part [klo, lane]; a carried row: all n columns)
-        if (k < n && (sym_row ? (k <= ln && k >= klo) : true)) Aw[ra + k] = a[k];
+        // (a row of the symmetric block: its stored part [klo, lane]; a carried row: all n columns -- [klo, khi] either
+        // way, so the order n takes no part in the decision: no wave-uniform k < n kept as a lane mask per column)
+        const int kh = sym_row ? ln : khi;
+        if (k >= klo && k <= kh) Aw[ra + k] = a[k];
       }
     }
     if (sym_row) {
       if (P.nvec > 0) Aw[v0a + lane] = yv0;
-      if (P.nvec > 1) Aw[v1a + lane] = yv1;
+      if (NVEC > 1 && P.nvec > 1) Aw[v1a + lane] = yv1;
     }
   }
-  return bad;
+  return (int)bad;
 }
 
 // Round 6: the packed root block by FOUR waves.  wave_ldl<40, 40, false> on one wave is a chain of 39 pivots at ~770 cycles each (two

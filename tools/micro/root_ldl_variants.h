@@ -7,6 +7,84 @@
 // Same contract as wave_ldl<NC, NC, false>.  Correct (<= 3e-15 against a host LDL'), and no faster: kept for the record.
 #pragma once
 namespace omgx {
+// wave_ldl as it stood before the instances sized to the plan (all NC columns whatever the order, two vector rows in every
+// instance, the pivot's sign tested with fp64 compares on the vector pipe): what the instances of omgx_wave.h must
+// reproduce to the bit.  Same contract as wave_ldl<NC, BW, BANDED, 2>.
+template <int NC, int BW, bool BANDED>
+__device__ __forceinline__ int wave_ldl_ref(int off, const WPanel Pin) {
+  const double* A = omgx_lds + off;
+  double* Aw = omgx_lds + off;
+  const WPanel P = wpanel_uniform(Pin);
+  const int lane = threadIdx.x & 63;
+  const int n = P.n;
+  const bool has_row = lane < P.nreg;
+  const bool sym_row = lane < n;
+  const int rl = has_row ? lane : 0;
+  const int ra = rl < n ? wsym<BANDED>(P, rl) : wcarried<BANDED>(P, rl);
+  const int klo = (BANDED && rl < n && rl > P.band) ? rl - P.band : 0;
+  const int khi = rl < n ? rl : n - 1;
+  double a[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    const int kk = k < klo ? klo : (k > khi ? khi : k);
+    const double v = A[ra + kk];
+    a[k] = (has_row && k >= klo && k <= khi) ? v : 0.0;
+  }
+  const int v0a = wcarried<BANDED>(P, P.vrow), v1a = wcarried<BANDED>(P, P.vrow + (P.nvec > 1 ? 1 : 0));
+  double yv0, yv1;
+  {
+    const int c = sym_row ? lane : 0;
+    const double v0 = A[v0a + c], v1 = A[v1a + c];
+    yv0 = (P.nvec > 0 && sym_row) ? v0 : 0.0;
+    yv1 = (P.nvec > 1 && sym_row) ? v1 : 0.0;
+  }
+  int bad = 0;
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    const double dj = readlane_d(a[j], j);
+    const bool okp = (j < P.npos) ? (dj > 0.0) : (dj < 0.0);
+    bad |= (j < n && !okp) ? 1 : 0;
+    const double inv = rcp_pivot(dj);
+    const double li = a[j] * inv;
+    {
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      const double lm = ln > j ? li : 0.0;
+      const double y0j = readlane_d(yv0, j), y1j = readlane_d(yv1, j);
+      yv0 = fma(-lm, j < n ? y0j : 0.0, yv0);
+      yv1 = fma(-lm, j < n ? y1j : 0.0, yv1);
+    }
+#pragma unroll
+    for (int c = j / 4; c < NC / 4; ++c) {
+      if (4 * c > j + BW) continue;
+      double s[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) s[q] = readlane_d(a[j], 4 * c + q);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int k = 4 * c + q;
+        if (k > j && k <= j + BW) a[k] = fma(-li, s[q], a[k]);
+      }
+      asm volatile("" : "+v"(a[4 * c]), "+v"(a[4 * c + 1]), "+v"(a[4 * c + 2]), "+v"(a[4 * c + 3]));
+    }
+  }
+  if (!bad) {
+    if (has_row) {
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        if (k < n && (sym_row ? (k <= ln && k >= klo) : true)) Aw[ra + k] = a[k];
+      }
+    }
+    if (sym_row) {
+      if (P.nvec > 0) Aw[v0a + lane] = yv0;
+      if (P.nvec > 1) Aw[v1a + lane] = yv1;
+    }
+  }
+  return bad;
+}
+
 template <int NC>
 __device__ __forceinline__ int wave_ldl_packed16(int off, const WPanel Pin, int soff) {
   typedef double v4d __attribute__((ext_vector_type(4)));
