@@ -219,6 +219,15 @@ int  omgx_template_block(const omgx_template* tpl, int32_t kind, const char* nam
                          int32_t* cols);
 
 int  omgx_plan_describe(const omgx_template* tpl, omgx_plan_info* info, int32_t* order);
+/* (OMGX_HAS_SCHUR_TILES) Which form of the Schur phase the plan of a template selects (host only): *n_banded = the number of banded
+ * leaves whose Schur complements are formed by tile owners -- on the wave path, when every banded leaf precedes the one diagonal
+ * leaf, all banded leaves couple to the same root positions in the same order (one coupling row), that row + the right-hand-side row
+ * fit two 16-row blocks, the workgroup has at least three waves and the two index tables fit the free descriptor slots (DESIGN.md
+ * §4.1) --, 0 = one leaf per barrier-separated round.  The same bits either way.  For tests and diagnostics.
+ * Developer knob, like OMGX_NO_COMPACT: with OMGX_NO_SCHUR_TILES in the environment when the plan is made, every plan selects the
+ * round form, and this entry reports 0 (the A/B runs of profiles/schur_tiles_ab.txt). */
+#define OMGX_HAS_SCHUR_TILES 1
+int  omgx_plan_schur_tiles(const omgx_template* tpl, int32_t* n_banded);
 
 /* Create a batch of n_agents independent problems sharing one template. */
 int  omgx_batch_create(const omgx_template* tpl, int32_t n_agents, int32_t device,

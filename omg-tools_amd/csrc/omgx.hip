@@ -505,6 +505,17 @@ int omgx_plan_describe(const omgx_template* tpl, omgx_plan_info* info, int32_t* 
   return OMGX_OK;
 }
 
+int omgx_plan_schur_tiles(const omgx_template* tpl, int32_t* n_banded) {
+  if (!n_banded) { g_err = "null argument"; return OMGX_E_INVALID; }
+  TRY(check_template(tpl));
+  omgx::HostPlan plan;
+  size_t nl = 0, ng = 0;
+  int mode = 0, per_cu = 1;
+  if (!plan_for_mode(plan, *tpl, &mode, &nl, &ng, &per_cu)) { g_err = "inconsistent template: " + plan.error; return OMGX_E_INVALID; }
+  *n_banded = plan.dims.schur_tiles;
+  return OMGX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Template files: the counts and arrays of omgx_template, written by the Python front end
 // (omgtools.backend.save_template) once per problem class and read by C/C++ callers -- the role the

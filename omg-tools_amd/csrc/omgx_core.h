@@ -77,6 +77,11 @@ struct Dims {
   int kg_side_dinv;  // 1: the side sums of the Gershgorin pass live in w.dinv, 0: in the side slots behind the KKT store
   int n_owner;       // owner bins in use (<= OMGX_NBIN, the stride of the record tables): the threads of the workgroup the plan was made for
   int n_lift, lift_depth;   // auxiliary variables of lifted products / quotients (omgx_template::n_lift) and the length of their longest chain
+  // Schur phase by tile owners (wave path; HostPlan::schur_rule, kkt_factor_wave): schur_tiles = number of banded leaves (they all
+  // couple to the same root positions in the same order), 0 = the round form.  The descriptor image then carries, as int32 behind
+  // its (n_leaf + 1) descriptors: that coupling row at schur_row, the dl_pos slice of the diagonal leaf at schur_dl (offsets in ints
+  // from the start of the image), schur_ints = length of the whole image
+  int schur_tiles, schur_row, schur_dl, schur_ints;
 };
 
 // one parameter monomial coef * prod atoms[a_k] as a single 16-byte record (a_k = -1: unused): one
@@ -490,6 +495,7 @@ enum { PH_JAC = 0, PH_RESID, PH_ASSEMBLE, PH_FACTOR, PH_SOLVE, PH_STEP, PH_LINES
        PH_K_FWD, PH_K_ROOTRHS, PH_K_ROOT, PH_K_LEAFRHS, PH_K_BWD, PH_L_TERMS, PH_L_ROWS,
        PH_F_PARK, PH_F_SWEEP, PH_F_SCALE, PH_A_TCOL, PH_A_HESS, PH_P_LOAD, PH_P_DIV, PH_P_BSPL, PH_P_SLOTS,
        PH_WG_HEAD, PH_WG_TAIL,      // outside PH_TOTAL: kernel entry (or the workgroup's previous solve) to the start of a solve; its last solve to its exit
+       PH_F_SCHUR_MFMA, PH_F_SCHUR_SUB,      // PH_F_SCHUR split by wave 0's clock: forming the tiles of S_l on the matrix pipe; subtracting them from the root (with its barriers)
        PH_COUNT };
 #if defined(OMGX_PROFILE) && !defined(OMGX_HOST_PORT)
 #define OMGX_TIC() long long tic_ = (c.sync(), clock64())
@@ -1361,14 +1367,16 @@ OMGX_FN void kkt_describe(const C& c, const Dims& d, const Kkt& K, Work& w, bool
   if (sync_after) c.sync();
 }
 
-// The descriptors of a solve: on the wave path the image the plan made, (n_leaf + 1) descriptors of 10 ints copied by the second
+// The descriptors of a solve: on the wave path the image the plan made, (n_leaf + 1) descriptors of 10 ints (and, behind them, the
+// index tables of the tile-owner Schur phase: Dims::schur_ints) copied by the second
 // wave with coalesced loads (one round trip instead of a chain of them; the second wave for kkt_describe's reason);
 // kkt_describe for every other instance.
 template <class C>
 OMGX_FN void kkt_descriptors(const C& c, const Dims& d, const Tables& T, Work& w, bool sync_after = true) {
   if constexpr (C::wave_only) {
     const int t0 = c.nthr() > 64 ? 64 : 0, nt = c.nthr() > 64 ? 64 : c.nthr();
-    const int i0 = c.tid() - t0, n = (d.n_leaf + 1) * (int)(sizeof(BMat) / sizeof(int32_t));
+    // (with the tile-owner Schur phase the image goes on behind the descriptors: Dims::schur_ints, still inside the descriptor slots)
+    const int i0 = c.tid() - t0, n = d.schur_tiles ? d.schur_ints : (d.n_leaf + 1) * (int)(sizeof(BMat) / sizeof(int32_t));
     int32_t* Ms = (int32_t*)w.col;
     if (i0 >= 0 && i0 < nt) for (int i = i0; i < n; i += nt) Ms[i] = T.bmat_img[i];
     if (sync_after) c.sync();
@@ -1382,9 +1390,10 @@ OMGX_FN void kkt_descriptors(const C& c, const Dims& d, const Tables& T, Work& w
 // ---------------------------------------------------------------------------
 // Wave path (every panel of the store fits one wave, Dims::wave_ok): register-resident factorisation
 // (omgx_wave.h).  Leaf l is factorised by wave l % nwaves -- all leaves at once, no workgroup barrier inside
-// --, its Schur complement S_l = Wt Delta^{-1} Wt' is formed by the same wave on the matrix pipe
-// (16x16x4 fp64 MFMA tiles) and subtracted from the root in leaf order (one leaf per barrier-separated
-// round: fixed order of the sums); the root is factorised by wave 0.
+// --, the Schur complements S_l = Wt Delta^{-1} Wt' are formed on the matrix pipe (16x16x4 fp64 MFMA tiles)
+// and subtracted from the root in leaf order (fixed order of the sums): by tile owners where the plan allows
+// it (Dims::schur_tiles), else by the wave that factorised the leaf, one leaf per barrier-separated round;
+// the root is factorised by wave 0.
 // ---------------------------------------------------------------------------
 OMGX_FN WPanel wpanel_leaf(const BMat& M) {
   WPanel P; P.base = M.a; P.ld = M.ld; P.n = M.nfact; P.nreg = M.rows - 2; P.nvec = 2; P.npos = M.nfact; P.bw = M.bw;
@@ -1408,10 +1417,244 @@ OMGX_FN DiagLeaf diag_leaf(const BMat& M) {
   L.S = __builtin_amdgcn_readfirstlane(M.pan); L.dinv = __builtin_amdgcn_readfirstlane(M.dinv); L.dl = 4 * L.dinv;
   return L;
 }
+// slot s of variable j of the diagonal leaf: the root position it is coupled to (-1: none).  From the LDS copy of the table
+// behind the descriptors where the plan put one (Dims::schur_tiles), from the global table otherwise.
+OMGX_FN int diag_leaf_pos(const Dims& d, const Kkt& K, const Work& w, const DiagLeaf& L, int s, int j) {
+  if (d.schur_tiles) return ((const int32_t*)w.col)[d.schur_dl + s * L.n + j];
+  return K.dl_pos[L.dl + s * L.n + j];
+}
+// entry i of the coupling index list of a banded leaf (BMat::cpl): of the one row every banded leaf has, in LDS, or of the global table
+OMGX_FN int leaf_cpl_at(const Dims& d, const Kkt& K, const Work& w, int cpl, int i) {
+  if (d.schur_tiles) return ((const int32_t*)w.col)[d.schur_row + i];
+  return K.cpl_idx[__builtin_amdgcn_readfirstlane(cpl) + i];
+}
+
+// Schur complement of the sparse diagonal leaf: lane j owns variable j.  v_0 .. v_{S-1} at root positions p_0 .. p_{S-1},
+// v_t at the position of t (n_root - 1), the right-hand side r_j at row nr of the root.  load() reads the leaf (and forms
+// the two wave sums every variable shares), apply() subtracts from the root: a caller may put a barrier between them.
+struct DiagSchur {
+  double vs[4], di, vt, rj, stt, srt;
+  int ps[4], S;
+  bool on;
+  template <class C>
+  OMGX_FN void load(const C& c, const Dims& d, const Kkt& K, const Work& w, const BMat& M) {
+    const DiagLeaf L = diag_leaf(M);
+    const int lane = c.lane(), j = lane < L.n ? lane : 0;
+    on = lane < L.n; S = L.S;
+    const double* A = w.kkt + L.base + j;
+    di = w.dinv[L.dinv + j];
+    vt = A[(1 + L.S) * L.n]; rj = A[(2 + L.S) * L.n];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const bool has = s < L.S;
+      ps[s] = has ? diag_leaf_pos(d, K, w, L, s, j) : -1;
+      const double v = A[(1 + (has ? s : 0)) * L.n];
+      vs[s] = (has && on && ps[s] >= 0) ? v : 0.0;
+    }
+    // shared targets: fixed-order wave sums
+    stt = c.wave_sum(on ? vt * di * vt : 0.0); srt = c.wave_sum(on ? rj * di * vt : 0.0);
+  }
+  template <class C>
+  OMGX_FN void apply(const C& c, const Dims& d, double* R) const {
+    const int pt = d.n_root - 1;
+    if (on) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        if (ps[s] < 0 || s >= S) continue;
+        const double u = vs[s] * di;
+#pragma unroll
+        for (int s2 = 0; s2 <= s; ++s2) {
+          if (ps[s2] < 0) continue;
+          const int pa = ps[s] > ps[s2] ? ps[s] : ps[s2], pb = ps[s] > ps[s2] ? ps[s2] : ps[s];
+          R[tri(pa, pb)] -= u * vs[s2];
+        }
+        R[tri(pt, ps[s])] -= u * vt;                  // (t is the last root variable: pt > every p_s)
+        R[tri(d.nr, ps[s])] -= u * rj;
+      }
+    }
+    if (c.lane() == 0) { R[tri(pt, pt)] -= stt; R[tri(d.nr, pt)] -= srt; }
+  }
+};
+
+// One tile of the Schur complements S_l = W_l D_l^-1 W_l' of CNT banded leaves (descriptors Ms[0 .. CNT-1]), formed side by side on
+// the matrix pipe -- rows ra of W_l against rows cb, four columns j0 .. j0+3 of the leaf per MFMA, a zero accumulator per leaf: per
+// entry the products and the j0 order of the round form in kkt_factor_wave -- and subtracted from r in leaf order.
+// No branch inside the loops, so the loads of the CNT leaves go out together, and the operands of the next four columns are
+// requested before the MFMAs of these four (the loads clamp their index: the request behind the last columns is harmless).
+// Whole blocks of four columns need no predicate; behind the end of a leaf (its order is no multiple of four, or it is shorter
+// than the longest of the group) both operands are zero as in the round form (acc + 0 * 0: the same bits).  Rows at or beyond
+// nc1 read the last row instead of zeros: entry (a, b) of a tile is a sum over row a and row b alone, and the caller never stores
+// such a row.
+template <int CNT>
+OMGX_FN void schur_tile_group(const Work& w, const BMat* Ms, int ra, int cb, int nc1, int q, double (&r)[4]) {
+  typedef double v4d __attribute__((ext_vector_type(4)));
+  const int rac = ra < nc1 ? ra : nc1 - 1, cbc = cb < nc1 ? cb : nc1 - 1;
+  v4d acc[CNT];
+  int n[CNT], ao[CNT], bo[CNT], dv[CNT], nmax = 0, nfull = OMGX_WAVE_ROWS;
+#pragma unroll
+  for (int k = 0; k < CNT; ++k) {
+    const int ld = __builtin_amdgcn_readfirstlane(Ms[k].ld), wo = __builtin_amdgcn_readfirstlane(Ms[k].pan);
+    acc[k] = (v4d){0.0, 0.0, 0.0, 0.0};
+    n[k] = __builtin_amdgcn_readfirstlane(Ms[k].nfact); dv[k] = __builtin_amdgcn_readfirstlane(Ms[k].dinv);
+    ao[k] = wo + rac * ld; bo[k] = wo + cbc * ld;
+    nmax = n[k] > nmax ? n[k] : nmax; nfull = (n[k] & ~3) < nfull ? (n[k] & ~3) : nfull;
+  }
+  double wa[CNT], wb[CNT], dj[CNT];
+  auto request = [&](int j) {
+#pragma unroll
+    for (int k = 0; k < CNT; ++k) {
+      const int jc = j < n[k] ? j : n[k] - 1;
+      wa[k] = w.kkt[ao[k] + jc]; wb[k] = w.kkt[bo[k] + jc]; dj[k] = w.dinv[dv[k] + jc];       // unconditional loads
+    }
+  };
+  request(q);
+  int j0 = 0;
+  for (; j0 < nfull; j0 += 4) {
+    double a[CNT], b[CNT];
+#pragma unroll
+    for (int k = 0; k < CNT; ++k) { a[k] = wa[k] * dj[k]; b[k] = wb[k]; }
+    request(j0 + 4 + q);
+#pragma unroll
+    for (int k = 0; k < CNT; ++k) acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[k], b[k], acc[k], 0, 0, 0);
+  }
+  for (; j0 < nmax; j0 += 4) {
+    const int j = j0 + q;
+    double a[CNT], b[CNT];
+#pragma unroll
+    for (int k = 0; k < CNT; ++k) { const bool in = j < n[k]; a[k] = (in ? wa[k] : 0.0) * dj[k]; b[k] = in ? wb[k] : 0.0; }
+    request(j + 4);
+#pragma unroll
+    for (int k = 0; k < CNT; ++k) acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[k], b[k], acc[k], 0, 0, 0);
+  }
+#pragma unroll
+  for (int k = 0; k < CNT; ++k) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r[i] -= acc[k][i];
+  }
+}
+
+// The Schur phase of kkt_factor_wave: the leaves are factorised (Wt = B L^-T in their carried rows, inverse pivots in w.dinv), the
+// packed root R -= sum_l S_l.  Every wave of the workgroup calls it and passes the same number of barriers whichever form
+// runs; the last statement of either form is a barrier.  ts0_ / tm_: wave 0's clock at the start of the phase and its cycles
+// up to the end of its MFMA loops (profiling build; dead otherwise).  A routine of its own so that tools/micro/schur_tiles.hip
+// can run the two forms against each other.
+template <class C>
+OMGX_FN void kkt_schur_wave(const C& c, const Dims& d, const Kkt& K, Work& w, [[maybe_unused]] long long ts0_, [[maybe_unused]] long long& tm_) {
+  typedef double v4d __attribute__((ext_vector_type(4)));
+  const BMat* Ms = (const BMat*)w.col;
+  const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
+  double* R = K.R();
+  if (d.schur_tiles && nw >= 3) {
+    // Tile owners: the banded leaves (0 .. nb-1, in front of the diagonal leaf) all couple to the same root positions in the same
+    // order, so tile (row block, column block) of every S_l lands on the same root entries.  Wave T = 0, 1, 2 owns tile (0,0),
+    // (1,0), (1,1): it forms that tile for every leaf (the statements and the j0 order of the round form below, a zero
+    // accumulator per leaf, three leaves in flight) and subtracts them in leaf order from a register copy of its root entries
+    // -- per root entry the operands and the order of the round form, hence its bits -- and stores once.  Then the diagonal
+    // leaf, read by its wave while the tiles are formed.  Two barriers, whatever the wave and whatever it had to do.
+    const int nb = d.schur_tiles;
+    const int32_t* si = (const int32_t*)w.col + d.schur_row;
+    const int nc1 = __builtin_amdgcn_readfirstlane(Ms[0].rows) - __builtin_amdgcn_readfirstlane(Ms[0].nfact);      // coupling rows + the right-hand-side row (last)
+    if (wave == 0 || (wave < 3 && nc1 > 16)) {
+      const int rb = wave >= 1 ? 16 : 0, kb = wave == 2 ? 16 : 0;
+      const int cb = kb + (lane & 15), ci_b = si[cb < nc1 - 1 ? cb : 0];
+      int ad[4]; bool ok[4]; double r[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int ca = rb + (lane >> 4) + 4 * i;
+        const int ci_a = ca < nc1 - 1 ? si[ca] : d.nr;
+        ok[i] = ca < nc1 && cb < nc1 - 1 && (rb != kb || cb <= ca);
+        ad[i] = ok[i] ? tri(ci_a, ci_b) : 0;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) r[i] = R[ad[i]];
+      const int ra = rb + (lane & 15), q = lane >> 4;
+      for (int l0 = 0; l0 < nb; l0 += 3) {
+        const int cnt = nb - l0;
+        if (cnt >= 3) schur_tile_group<3>(w, Ms + l0, ra, cb, nc1, q, r);
+        else if (cnt == 2) schur_tile_group<2>(w, Ms + l0, ra, cb, nc1, q, r);
+        else schur_tile_group<1>(w, Ms + l0, ra, cb, nc1, q, r);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) if (ok[i]) R[ad[i]] = r[i];
+    }
+#ifdef OMGX_PROFILE
+    tm_ = clock64() - ts0_;
+#endif
+    const int dw = nw > 3 ? 3 : 0;
+    const bool diag = nb < d.n_leaf && wave == dw;
+    DiagSchur D;
+    if (diag) D.load(c, d, K, w, Ms[nb]);
+    c.sync();
+    if (diag) D.apply(c, d, R);
+    c.sync();
+  } else for (int base = 0; base < d.n_leaf; base += nw) {      // the round form
+    const int l = base + wave;
+#ifdef OMGX_PROFILE
+    const long long tb_ = clock64();
+#endif
+    v4d acc00 = {0.0, 0.0, 0.0, 0.0}, acc10 = acc00, acc11 = acc00;
+    int nc1 = 0, ci_b0 = 0, ci_b1 = 0, ci_a[8];
+    bool sparse = false;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ci_a[i] = 0;
+    if (l < d.n_leaf) {
+      const BMat M = Ms[l];
+      sparse = __builtin_amdgcn_readfirstlane(M.bw) < 0;
+      if (!sparse) {
+      const int n = __builtin_amdgcn_readfirstlane(M.nfact), ld = __builtin_amdgcn_readfirstlane(M.ld);
+      nc1 = __builtin_amdgcn_readfirstlane(M.rows) - n;            // coupling rows + the right-hand-side row (last)
+      const double* Wt = w.kkt + __builtin_amdgcn_readfirstlane(M.pan);
+      const double* di = w.dinv + __builtin_amdgcn_readfirstlane(M.dinv);
+      // root positions of this lane's rows / columns (global table, or its LDS copy: requested before the MFMA loop)
+      const int cb0 = lane & 15, cb1 = 16 + (lane & 15);
+      ci_b0 = leaf_cpl_at(d, K, w, M.cpl, cb0 < nc1 - 1 ? cb0 : 0); ci_b1 = leaf_cpl_at(d, K, w, M.cpl, cb1 < nc1 - 1 ? cb1 : 0);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int ca = 16 * (i >> 2) + (lane >> 4) + 4 * (i & 3);
+        ci_a[i] = ca < nc1 - 1 ? leaf_cpl_at(d, K, w, M.cpl, ca) : d.nr;
+      }
+      const int r0 = lane & 15, r1 = 16 + (lane & 15), q = lane >> 4;
+      const int r0c = r0 < nc1 ? r0 : nc1 - 1, r1c = r1 < nc1 ? r1 : nc1 - 1;
+      const bool two = nc1 > 16;
+      for (int j0 = 0; j0 < n; j0 += 4) {
+        const int j = j0 + q, jc = j < n ? j : n - 1;
+        const double w0 = Wt[r0c * ld + jc], w1 = Wt[r1c * ld + jc], dj = di[jc];       // unconditional loads
+        const double b0 = (r0 < nc1 && j < n) ? w0 : 0.0, b1 = (r1 < nc1 && j < n) ? w1 : 0.0;
+        acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(b0 * dj, b0, acc00, 0, 0, 0);
+        if (two) {
+          acc10 = __builtin_amdgcn_mfma_f64_16x16x4f64(b1 * dj, b0, acc10, 0, 0, 0);
+          acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(b1 * dj, b1, acc11, 0, 0, 0);
+        }
+      }
+      }
+    }
+#ifdef OMGX_PROFILE
+    tm_ += clock64() - tb_;
+#endif
+    // subtract from the root, one leaf per round
+    const int lend = base + nw < d.n_leaf ? base + nw : d.n_leaf;
+    for (int lr = base; lr < lend; ++lr) {
+      if (l == lr && !sparse) {
+        const int cb0 = lane & 15, cb1 = 16 + (lane & 15);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int ca0 = (lane >> 4) + 4 * i, ca1 = 16 + ca0;
+          if (ca0 < nc1 && cb0 < nc1 - 1 && cb0 <= ca0) R[tri(ci_a[i], ci_b0)] -= acc00[i];
+          if (ca1 < nc1 && cb0 < nc1 - 1) R[tri(ci_a[4 + i], ci_b0)] -= acc10[i];
+          if (ca1 < nc1 && cb1 < nc1 - 1 && cb1 <= ca1) R[tri(ci_a[4 + i], ci_b1)] -= acc11[i];
+        }
+      } else if (l == lr) {
+        DiagSchur D;
+        D.load(c, d, K, w, Ms[l]);
+        D.apply(c, d, R);
+      }
+      c.sync();
+    }
+  }
+}
 
 template <class C>
 OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w) {
-  typedef double v4d __attribute__((ext_vector_type(4)));
   const BMat* Ms = (const BMat*)w.col;
   const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
   const int koff = (int)(w.kkt - omgx_lds);            // the out-of-line wave routines address the LDS by offset
@@ -1443,99 +1686,16 @@ OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w) {
 #endif
   if (c.rmax(badl ? 1.0 : 0.0) > 0.0) return 1;       // (two barriers: the panels and inverse pivots are visible)
   OMGX_TOC(PH_F_LEAF);
-  double* R = K.R();
-  for (int base = 0; base < d.n_leaf; base += nw) {
-    const int l = base + wave;
-    v4d acc00 = {0.0, 0.0, 0.0, 0.0}, acc10 = acc00, acc11 = acc00;
-    int nc1 = 0, ci_b0 = 0, ci_b1 = 0, ci_a[8];
-    bool sparse = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ci_a[i] = 0;
-    if (l < d.n_leaf) {
-      const BMat M = Ms[l];
-      sparse = __builtin_amdgcn_readfirstlane(M.bw) < 0;
-      if (!sparse) {
-      const int n = __builtin_amdgcn_readfirstlane(M.nfact), ld = __builtin_amdgcn_readfirstlane(M.ld);
-      nc1 = __builtin_amdgcn_readfirstlane(M.rows) - n;            // coupling rows + the right-hand-side row (last)
-      const double* Wt = w.kkt + __builtin_amdgcn_readfirstlane(M.pan);
-      const double* di = w.dinv + __builtin_amdgcn_readfirstlane(M.dinv);
-      const int32_t* ci = K.cpl_idx + __builtin_amdgcn_readfirstlane(M.cpl);
-      // root positions of this lane's rows / columns (global table: requested before the MFMA loop)
-      const int cb0 = lane & 15, cb1 = 16 + (lane & 15);
-      ci_b0 = ci[cb0 < nc1 - 1 ? cb0 : 0]; ci_b1 = ci[cb1 < nc1 - 1 ? cb1 : 0];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int ca = 16 * (i >> 2) + (lane >> 4) + 4 * (i & 3);
-        ci_a[i] = ca < nc1 - 1 ? ci[ca] : d.nr;
-      }
-      const int r0 = lane & 15, r1 = 16 + (lane & 15), q = lane >> 4;
-      const int r0c = r0 < nc1 ? r0 : nc1 - 1, r1c = r1 < nc1 ? r1 : nc1 - 1;
-      const bool two = nc1 > 16;
-      for (int j0 = 0; j0 < n; j0 += 4) {
-        const int j = j0 + q, jc = j < n ? j : n - 1;
-        const double w0 = Wt[r0c * ld + jc], w1 = Wt[r1c * ld + jc], dj = di[jc];       // unconditional loads
-        const double b0 = (r0 < nc1 && j < n) ? w0 : 0.0, b1 = (r1 < nc1 && j < n) ? w1 : 0.0;
-        acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(b0 * dj, b0, acc00, 0, 0, 0);
-        if (two) {
-          acc10 = __builtin_amdgcn_mfma_f64_16x16x4f64(b1 * dj, b0, acc10, 0, 0, 0);
-          acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(b1 * dj, b1, acc11, 0, 0, 0);
-        }
-      }
-      }
-    }
-    // subtract from the root, one leaf per round
-    const int lend = base + nw < d.n_leaf ? base + nw : d.n_leaf;
-    for (int lr = base; lr < lend; ++lr) {
-      if (l == lr && !sparse) {
-        const int cb0 = lane & 15, cb1 = 16 + (lane & 15);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int ca0 = (lane >> 4) + 4 * i, ca1 = 16 + ca0;
-          if (ca0 < nc1 && cb0 < nc1 - 1 && cb0 <= ca0) R[tri(ci_a[i], ci_b0)] -= acc00[i];
-          if (ca1 < nc1 && cb0 < nc1 - 1) R[tri(ci_a[4 + i], ci_b0)] -= acc10[i];
-          if (ca1 < nc1 && cb1 < nc1 - 1 && cb1 <= ca1) R[tri(ci_a[4 + i], ci_b1)] -= acc11[i];
-        }
-      } else if (l == lr) {
-        // sparse diagonal leaf: lane j owns variable j.  v_0 .. v_{S-1} at root positions p_0 .. p_{S-1}, v_t at
-        // the position of t (n_root - 1), the right-hand side r_j at row nr of the root
-        const DiagLeaf L = diag_leaf(Ms[l]);
-        const int j = lane < L.n ? lane : 0;
-        const bool on = lane < L.n;
-        const double* A = w.kkt + L.base + j;
-        const double di = w.dinv[L.dinv + j];
-        const double vt = A[(1 + L.S) * L.n], rj = A[(2 + L.S) * L.n];
-        const int pt = d.n_root - 1;
-        double vs[4]; int ps[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const bool has = s < L.S;
-          ps[s] = has ? K.dl_pos[L.dl + s * L.n + j] : -1;
-          const double v = A[(1 + (has ? s : 0)) * L.n];
-          vs[s] = (has && on && ps[s] >= 0) ? v : 0.0;
-        }
-        if (on) {
-#pragma unroll
-          for (int s = 0; s < 4; ++s) {
-            if (ps[s] < 0 || s >= L.S) continue;
-            const double u = vs[s] * di;
-#pragma unroll
-            for (int s2 = 0; s2 <= s; ++s2) {
-              if (ps[s2] < 0) continue;
-              const int pa = ps[s] > ps[s2] ? ps[s] : ps[s2], pb = ps[s] > ps[s2] ? ps[s2] : ps[s];
-              R[tri(pa, pb)] -= u * vs[s2];
-            }
-            R[tri(pt, ps[s])] -= u * vt;                  // (t is the last root variable: pt > every p_s)
-            R[tri(d.nr, ps[s])] -= u * rj;
-          }
-        }
-        // shared targets: fixed-order wave sums
-        const double stt = c.wave_sum(on ? vt * di * vt : 0.0), srt = c.wave_sum(on ? rj * di * vt : 0.0);
-        if (lane == 0) { R[tri(pt, pt)] -= stt; R[tri(d.nr, pt)] -= srt; }
-      }
-      c.sync();
-    }
-  }
+  [[maybe_unused]] long long ts0_ = 0, tm_ = 0;      // (wave 0's own clock: start of the Schur phase, cycles up to the end of its MFMA loops)
+#ifdef OMGX_PROFILE
+  ts0_ = clock64();
+#endif
+  kkt_schur_wave(c, d, K, w, ts0_, tm_);
   OMGX_TOC(PH_F_SCHUR);
+#ifdef OMGX_PROFILE
+  // (the split of f_schur by wave 0's clock: up to the end of its MFMA loops, and the rest -- subtraction and barriers)
+  if (c.tid() == 0) { c.prof[PH_F_SCHUR_MFMA] += tm_; c.prof[PH_F_SCHUR_SUB] += tic_ - ts0_ - tm_; }
+#endif
   // (Round 6 measured the root on the four waves of the workgroup -- root_ldl_4w, omgx_wave.h: the same bits, 30.2 k -> 22.1 k cycles alone
   // on a CU -- and did not adopt it: inside the solve kernel f_root drops by 3.4 k only while the phases of the agent that shares the CU
   // lose what the three parked waves used to leave it, 342 k -> 349 k cycles per solve: profiles/r06_micro_root_ldl.txt)
@@ -1598,7 +1758,7 @@ OMGX_FN void kkt_solve_wave(const C& c, const Dims& d, const Kkt& K, Work& w, do
       const double* A = w.kkt + L.base + j;
       double acc = A[(2 + L.S) * L.n] - A[(1 + L.S) * L.n] * sol[d.root_off + d.n_root - 1];
       for (int s = 0; s < L.S; ++s) {
-        const int ps = K.dl_pos[L.dl + s * L.n + j];
+        const int ps = diag_leaf_pos(d, K, w, L, s, j);
         acc = fma(-A[(1 + s) * L.n], sol[d.root_off + (ps < 0 ? 0 : ps)] * (ps < 0 ? 0.0 : 1.0), acc);
       }
       if (lane < L.n) sol[L.dinv + lane] = acc * w.dinv[L.dinv + j];
@@ -1606,8 +1766,7 @@ OMGX_FN void kkt_solve_wave(const C& c, const Dims& d, const Kkt& K, Work& w, do
     }
     const WPanel P = wpanel_uniform(wpanel_leaf(M));
     const int n = P.n, nc = P.nreg + 1 - P.n, ld = P.ld;          // (wave-uniform values: scalar loop bounds)
-    const int32_t* ci = K.cpl_idx + __builtin_amdgcn_readfirstlane(M.cpl);
-    if (lane < nc) xg[lane] = sol[d.root_off + ci[lane]];
+    if (lane < nc) xg[lane] = sol[d.root_off + leaf_cpl_at(d, K, w, M.cpl, lane)];
     wave_fence();
     const int j = lane < n ? lane : 0;
     const double* Wt = w.kkt + P.wbase + j;
@@ -1669,9 +1828,8 @@ OMGX_FN void kkt_solve2_wave(const C& c, const Dims& d, const Kkt& K, Work& w, d
         const BMat M = Ms[lr];
         if (__builtin_amdgcn_readfirstlane(M.bw) >= 0) {
           const int nc = __builtin_amdgcn_readfirstlane(M.rows) - 1 - __builtin_amdgcn_readfirstlane(M.nfact);
-          const int32_t* ci = K.cpl_idx + __builtin_amdgcn_readfirstlane(M.cpl);
           const double* xs = xg0 + (lr - base) * 64;
-          if (lane < nc) R[rrow + ci[lane]] -= xs[lane];
+          if (lane < nc) R[rrow + leaf_cpl_at(d, K, w, M.cpl, lane)] -= xs[lane];
         } else {
           // sparse diagonal leaf: y = r; lane j owns variable j and the root positions it is coupled to
           const DiagLeaf L = diag_leaf(M);
@@ -1680,7 +1838,7 @@ OMGX_FN void kkt_solve2_wave(const C& c, const Dims& d, const Kkt& K, Work& w, d
           const double* A = w.kkt + L.base + j;
           const double u = A[(2 + L.S) * L.n] * w.dinv[L.dinv + j];
           for (int s = 0; s < L.S; ++s) {
-            const int ps = K.dl_pos[L.dl + s * L.n + j];
+            const int ps = diag_leaf_pos(d, K, w, L, s, j);
             if (on && ps >= 0) R[rrow + ps] -= A[(1 + s) * L.n] * u;
           }
           const double st = c.wave_sum(on ? A[(1 + L.S) * L.n] * u : 0.0);
@@ -1709,7 +1867,7 @@ OMGX_FN void kkt_solve2_wave(const C& c, const Dims& d, const Kkt& K, Work& w, d
       const double* A = w.kkt + L.base + j;
       double acc = A[(2 + L.S) * L.n] - A[(1 + L.S) * L.n] * out[d.root_off + d.n_root - 1];
       for (int s = 0; s < L.S; ++s) {
-        const int ps = K.dl_pos[L.dl + s * L.n + j];
+        const int ps = diag_leaf_pos(d, K, w, L, s, j);
         acc = fma(-A[(1 + s) * L.n], out[d.root_off + (ps < 0 ? 0 : ps)] * (ps < 0 ? 0.0 : 1.0), acc);
       }
       if (lane < L.n) out[L.dinv + lane] = acc * w.dinv[L.dinv + j];
@@ -1717,8 +1875,7 @@ OMGX_FN void kkt_solve2_wave(const C& c, const Dims& d, const Kkt& K, Work& w, d
     }
     const WPanel P = wpanel_uniform(wpanel_leaf(M));
     const int n = P.n, nc = P.nreg + 1 - P.n, ld = P.ld;
-    const int32_t* ci = K.cpl_idx + __builtin_amdgcn_readfirstlane(M.cpl);
-    if (lane < nc) xg[lane] = out[d.root_off + ci[lane]];
+    if (lane < nc) xg[lane] = out[d.root_off + leaf_cpl_at(d, K, w, M.cpl, lane)];
     wave_fence();
     const int j = lane < n ? lane : 0;
     const double* Wt = w.kkt + P.wbase + j;

@@ -892,9 +892,39 @@ struct HostPlan {
     if (compact) {
       Kkt K; K.bind(d, T, nullptr);
       kkt_describe_fill<true, false, false>(d, K, (BMat*)bmat_img.data());
+      // Schur phase by tile owners: the image also carries the one coupling row of the banded leaves and the dl_pos slice of the
+      // diagonal leaf, in the descriptor slots the plan leaves unused (Dims::schur_*)
+      const int nb = schur_rule();
+      if (nb > 0) {
+        d.schur_tiles = nb; d.schur_row = (int)bmat_img.size();
+        bmat_img.insert(bmat_img.end(), cpl_idx.begin() + cpl_ptr[0], cpl_idx.begin() + cpl_ptr[1]);
+        d.schur_dl = (int)bmat_img.size();
+        if (nb < d.n_leaf) bmat_img.insert(bmat_img.end(), dl_pos.begin() + 4 * (size_t)leaf_off[nb], dl_pos.begin() + 4 * (size_t)leaf_off[nb] + (size_t)lf_w[nb] * (leaf_off[nb + 1] - leaf_off[nb]));
+        d.schur_ints = (int)bmat_img.size();
+      }
     }
     T.bmat_img = bmat_img.data();
     return true;
+  }
+
+  // The rule of the tile-owner Schur phase (kkt_factor_wave): > 0 (the number of banded leaves) iff the plan is on the wave path
+  // with the compact store, every banded leaf precedes the diagonal leaf (at most one: its dl_pos slice is the one the image
+  // carries), all banded leaves have the identical coupling row, nc + 1 <= 32, the workgroup the plan was made for has at least
+  // three waves, and the two index tables fit the free descriptor slots.  Otherwise 0: rounds and global index loads.
+  int schur_rule() const {
+    const Dims& d = dims;
+    if (!compact || !d.wave_ok || d.n_leaf < 1 || owners / 64 < 3 || getenv("OMGX_NO_SCHUR_TILES")) return 0;      // (the knob: developer A/B of the two forms)
+    int nb = 0;
+    while (nb < d.n_leaf && !lf_kind[nb]) ++nb;
+    if (nb == 0 || d.n_leaf - nb > 1) return 0;
+    for (int l = nb; l < d.n_leaf; ++l) if (!lf_kind[l]) return 0;
+    const int nc = cpl_ptr[1] - cpl_ptr[0];
+    if (nc + 1 > 32) return 0;
+    for (int l = 1; l < nb; ++l)
+      if (cpl_ptr[l + 1] - cpl_ptr[l] != nc || !std::equal(cpl_idx.begin() + cpl_ptr[l], cpl_idx.begin() + cpl_ptr[l + 1], cpl_idx.begin())) return 0;
+    const int dl_ints = nb < d.n_leaf ? lf_w[nb] * (leaf_off[nb + 1] - leaf_off[nb]) : 0;
+    const int free_ints = (OMGX_MAX_LEAF - d.n_leaf) * (int)(sizeof(BMat) / sizeof(int32_t));
+    return nc + dl_ints <= free_ints ? nb : 0;
   }
 };
 

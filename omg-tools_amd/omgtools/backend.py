@@ -275,6 +275,16 @@ def describe_plan(tpl, lib=None):
                 ka_len=info.ka_len, kh_len=info.kh_len, kg_len=info.kg_len)
 
 
+def plan_schur_tiles(tpl, lib=None):
+    """The form of the Schur phase the plan selects (include/omgx.h OMGX_HAS_SCHUR_TILES): the number of banded leaves formed by tile
+    owners, 0 = one leaf per round."""
+    lib = lib or load_library()
+    ct, keep = make_ctemplate(tpl)
+    n = C.c_int32(-1)
+    _check(lib, lib.omgx_plan_schur_tiles(C.byref(ct), C.byref(n)), 'omgx_plan_schur_tiles')
+    return int(n.value)
+
+
 class AdmmLayoutC(C.Structure):
     """include/omgx.h omgx_admm_layout"""
     _fields_ = [(n, C.c_int32) for n in ('n_dim', 'L', 'n_nghb', 'x_spl', 'p_rel',
@@ -322,6 +332,7 @@ PROTOTYPES = {
     'omgx_template_block_at': (C.c_int, [_TPL, _I, _I, C.POINTER(C.c_char_p), _P, _P, _P]),
     'omgx_template_block': (C.c_int, [_TPL, _I, C.c_char_p, _P, _P, _P]),
     'omgx_plan_describe': (C.c_int, [_TPL, C.POINTER(CPlanInfo), _P]),
+    'omgx_plan_schur_tiles': (C.c_int, [_TPL, _P]),
     'omgx_batch_create': (C.c_int, [_TPL, _I, _I, C.POINTER(C.c_void_p)]),
     'omgx_batch_destroy': (None, [_H]),
     'omgx_batch_set_options': (C.c_int, [_H, C.POINTER(COptions)]),
@@ -373,7 +384,7 @@ PROTOTYPES = {
     'omgx_admm_communicate_ex': (C.c_int, [_H, _LAY] + [_P] * 4 + [_I] + [_P] * 2 + [_I, _I, _P]),
 }
 # (entries of ABI 8 and 9 and the lean-instance query: a library built before them still loads, calling one raises AttributeError)
-_NEWER_ENTRIES = ('omgx_batch_set_prepare', 'omgx_batch_set_stop', 'omgx_batch_last_instance')
+_NEWER_ENTRIES = ('omgx_batch_set_prepare', 'omgx_batch_set_stop', 'omgx_batch_last_instance', 'omgx_plan_schur_tiles')
 
 
 _lib = None

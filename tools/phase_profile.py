@@ -18,7 +18,9 @@ PHASES = ['jac', 'resid', 'assemble', 'factor', 'solve', 'step', 'linesearch', '
           'f_park', 'f_sweep', 'f_scale', 'a_tcol', 'a_hess', 's_p_load', 's_p_div', 's_p_bspl', 's_p_slots',
           # outside 'total': kernel entry (or the end of the workgroup's previous solve) to the start of a solve -- slot hand-out,
           # descriptors --, and the workgroup's last solve to its exit (queue counter, fences)
-          'wg_head', 'wg_tail']
+          'wg_head', 'wg_tail',
+          # 'f_schur' split by wave 0's clock: forming the tiles of the Schur complements on the matrix pipe; subtracting them from the root, with its barriers
+          'f_schur_mfma', 'f_schur_sub']
 
 
 def mpc_mode(problem, P, B, steps=20, warmup=3, rounds=False):
