@@ -751,6 +751,55 @@ typedef struct omgx_obstacle_script {
 int  omgx_batch_obstacles_advance(omgx_batch* b, double* p, const omgx_obstacle_script* sp, double t_prev, double dt);
 int  omgx_batch_set_obstacle_script(omgx_batch* b, const omgx_obstacle_script* sp, const double* t_abs, int32_t n_t);
 
+/* (OMGX_HAS_MISSION) Missions: a list of goals per agent, flown inside the rollout launch -- what the reference does with a second
+ * `simulator.run()` after `vehicle.set_terminal_conditions(...)` (`examples/p2p_holonomic_multiproblem.py`) or with `deployer.reset()`
+ * at every via point (`examples/deployer_example.py`).  Point-mass classes (parameters state0 / input0 / poseT, one spline per axis).
+ * Per agent b: goals[b] [G][n_spl], the goals AFTER the one in p[poseT]; n_goals[b] in 0 .. G of them are flown; leg[b] = index of the
+ * goal being flown (0: the one in p); clock[b] = receding-horizon steps the current leg has had behind its first solve (the index of
+ * its next step record; the first leg carries on from the batch's own count); arrivals[b][0 .. G] = the step at whose head goal j was
+ * found reached (-1: not yet).  The stop rule must be set (omgx_batch_set_stop): arriving is that rule -- with a plant set, the plant's
+ * rule on the travelled state.
+ *
+ * The leg switch, for an agent under way for which the rule holds while leg[b] < n_goals[b] (`Problem.reinitialize`,
+ * `problems/point2point.py:79-86`, then the first update with `enforce_states`, `problems/problem.py:160-161`):
+ *   s      <- p[state0] as the PREVIOUS update left it (the reference's `prediction['state']`: one update stale; read before this
+ *             step's prediction overwrites it)
+ *   g      <- goals[b][leg[b]];  p[poseT] <- g
+ *   x      <- x_reset outside the spline block; spline k, coefficient i:  s_k + i * ((g_k - s_k) / (L - 1))  for i < L - 1, g_k for
+ *             i = L - 1 -- numpy's linspace statement, every product and sum rounded on its own: the bits of np.linspace(s_k, g_k, L)
+ *   lam_g  <- 0
+ *   p[state0] <- the state the vehicle is in now (this step's prediction; with a plant its travelled state), p[input0] <- 0, p[t] <- 0
+ *   clock[b] <- 0;  arrivals[b][leg[b]] <- the step;  leg[b] <- leg[b] + 1
+ * There is no prediction from the old plan and no horizon shift in that step, and its solve is the cold one: the option set `cold`
+ * with warm_start = 0, no multipliers, no status, no carried inertia correction.  A leg-start solve that fails is any failed solve:
+ * the next step restarts cold.  The arrival test is not repeated on the new goal in the step that starts a leg: a leg has at least
+ * one update.  When the rule holds with leg[b] = n_goals[b] the agent's loop ends: under_way[b] <- 0, arrivals[b][leg[b]] <- the step.
+ * Not mirrored: at the update that ends a run the reference's `Simulator.run` moves its own clock by update_time - sample_time
+ * (`execution/simulator.py:45-49`); nothing in a solve reads that clock, and the batch's absolute clock stays on the update grid.
+ *
+ * omgx_batch_set_mission: every following omgx_batch_rollout runs the mission instance of its kernel (wave-path classes, with and
+ * without a plant; refused together with an obstacle script): each agent takes n_steps steps, step k stamped step_index + k; the
+ * step record of a step is steps[clock[b]] -- the rollout specification's tau / t_rel / crossed are then the TABLE of a leg's own
+ * clock, filled from the leg-local time 0, its n_steps entries at least max(clock) + the mission's n_steps (an agent whose clock
+ * leaves the table ends its loop for this launch) -- and clock[b] is incremented behind every solve that does not start a leg.
+ * iters_log / status_log / stats have the mission's n_steps rows.  sp == NULL switches it off.  goals, n_goals, leg, clock, arrivals are
+ * DEVICE arrays that stay valid while the mission is set; x_reset [n_var] and cold are host data read during the call.
+ * omgx_batch_mission_advance: the arrival test and the switch WITHOUT a solve, one launch on the handle's stream, one wave per agent:
+ * s = p[state0] as it stands, the state now = p[state0] (with a plant set: its travelled state); stamps step_index. */
+#define OMGX_HAS_MISSION 1
+typedef struct omgx_mission_spec {
+  const double*  goals;     /* [B, G, n_spl] device */
+  const int32_t* n_goals;   /* [B] device */
+  int32_t* leg;             /* [B] device */
+  int32_t* clock;           /* [B] device */
+  int32_t* arrivals;        /* [B, 1 + G] device */
+  const double*  x_reset;   /* [n_var] host */
+  const omgx_options* cold; /* host: the option set of a leg's first solve */
+  int32_t G, o_state0, o_input0, o_poseT, p_t, coeff_off, n_spl, L, n_steps, step_index;
+} omgx_mission_spec;
+int  omgx_batch_set_mission(omgx_batch* b, const omgx_mission_spec* sp);
+int  omgx_batch_mission_advance(omgx_batch* b, double* p, double* x, double* lam_g, int32_t step_index);
+
 /* Same shift on any device-resident row-major array (stride doubles per row, n_rows rows):
  * used for the ADMM consensus state on a knot crossing (`problems/admm.py:477-491`).
  * The handle keeps the table sets it has seen on the device (16, found again by content): a loop that shifts with the

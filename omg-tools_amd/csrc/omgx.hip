@@ -55,6 +55,7 @@ struct Instances {
   ipm_eval_kernel_t eval = nullptr;
   ipm_rollout_t rollout = nullptr, rollout_plant = nullptr;      // (rollout_plant: the instance with the plant in the loop, omgx_batch_set_plant)
   ipm_rollout_t rollout_script = nullptr, rollout_plant_script = nullptr;      // (the two with an obstacle script, omgx_batch_set_obstacle_script)
+  ipm_rollout_t rollout_mission = nullptr, rollout_plant_mission = nullptr;      // (the two with a mission, omgx_batch_set_mission)
   decltype(&ipm_prepare_kernel<true>) prepare = nullptr;
 };
 static Instances instances_for(int mode, int wave_ok, int general) {
@@ -68,6 +69,8 @@ static Instances instances_for(int mode, int wave_ok, int general) {
   in.rollout_plant = rollout_kernel_for(mode, wave_ok, general, 1);
   in.rollout_script = rollout_kernel_for(mode, wave_ok, general, 0, 1);
   in.rollout_plant_script = rollout_kernel_for(mode, wave_ok, general, 1, 1);
+  in.rollout_mission = rollout_kernel_for(mode, wave_ok, general, 0, 0, 1);
+  in.rollout_plant_mission = rollout_kernel_for(mode, wave_ok, general, 1, 0, 1);
   in.prepare = general ? ipm_prepare_kernel<true> : ipm_prepare_kernel<false>;
   return in;
 }
@@ -131,6 +134,10 @@ struct omgx_batch {
   ObstacleScriptArgs* d_script_call = nullptr;      // ... and the copy of what a stand-alone omgx_batch_obstacles_advance call was given
   DevBuf script_t; int script_t_cap = 0;    // (t_abs of the script set: grows with the longest step list registered)
   bool script_on = false;
+  MissionArgs mission_host = {};            // omgx_batch_set_mission: the mission as the rollout's mission instances read it ...
+  MissionArgs* d_mission = nullptr;         // ... its copy in device memory ...
+  double* d_x_reset = nullptr;              // ... and the handle's copy of the reset row [n_var]
+  bool mission_on = false;
   StopArgs* d_stop = nullptr;      // omgx_batch_set_stop: device copy of the arguments
   StopArgs stop_host = {};          // (and the host copy: omgx_batch_rollout hands it to its kernel inside RolloutArgs)
   bool stop_on = false;
@@ -717,8 +724,9 @@ int create_batch(omgx_batch* b, const omgx_template* tpl) {
   static int lds_reserved[4 * omgx::WS_MODES] = {0};
   int& reserved = lds_reserved[4 * b->ws_mode + (d.wave_ok ? 1 : 0) + (d.general ? 2 : 0)];
   if ((int)b->lds_bytes > reserved) reserved = (int)b->lds_bytes;
-  const void* const launched[7] = {(const void*)b->inst.full, (const void*)b->inst.refine, (const void*)b->inst.lean, (const void*)b->inst.rollout,
-                                   (const void*)b->inst.rollout_plant, (const void*)b->inst.rollout_script, (const void*)b->inst.rollout_plant_script};
+  const void* const launched[9] = {(const void*)b->inst.full, (const void*)b->inst.refine, (const void*)b->inst.lean, (const void*)b->inst.rollout,
+                                   (const void*)b->inst.rollout_plant, (const void*)b->inst.rollout_script, (const void*)b->inst.rollout_plant_script,
+                                   (const void*)b->inst.rollout_mission, (const void*)b->inst.rollout_plant_mission};
   for (const void* k : launched)
     if (k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, reserved) != hipSuccess) {
       g_err = (k != (const void*)b->inst.full && k != (const void*)b->inst.refine && k != (const void*)b->inst.lean) ? "cannot reserve dynamic LDS for ipm_rollout_kernel" : "cannot reserve dynamic LDS for ipm_solve_kernel";
@@ -814,12 +822,17 @@ void omgx_batch_destroy(omgx_batch* b) {
   delete b;
 }
 
-int omgx_batch_set_options(omgx_batch* b, const omgx_options* o) {
-  if (!b || !o || !(o->tol > 0) || o->max_iter < 0) { g_err = "bad options"; return OMGX_E_INVALID; }
-  b->opts = {o->tol, o->max_iter, o->mu_init, o->kappa_push, o->nu_init, o->scale_gmax, o->warm_start, o->kappa_warm,
+// the caller's options as the kernels take them
+static omgx::Opts opts_of(const omgx_options* o) {
+  return {o->tol, o->max_iter, o->mu_init, o->kappa_push, o->nu_init, o->scale_gmax, o->warm_start, o->kappa_warm,
              o->dw_leaf_ratio_cold > 0 ? o->dw_leaf_ratio_cold : 1.0, 0, o->warm_mu_factor >= 0 ? o->warm_mu_factor : 0.0,
              o->warm_z_floor >= 0 ? o->warm_z_floor : 0.0, o->warm_z_cap >= 0 ? o->warm_z_cap : 0.0, o->max_soc > 0 ? (o->max_soc > 8 ? 8 : o->max_soc) : 0, o->hess_approx > 0 ? 1 : 0,
              o->compl_inf_tol > 0 ? o->compl_inf_tol : 0.0, o->constr_viol_tol > 0 ? o->constr_viol_tol : 0.0, o->refine > 0 ? 1 : 0};
+}
+
+int omgx_batch_set_options(omgx_batch* b, const omgx_options* o) {
+  if (!b || !o || !(o->tol > 0) || o->max_iter < 0) { g_err = "bad options"; return OMGX_E_INVALID; }
+  b->opts = opts_of(o);
   return OMGX_OK;
 }
 
@@ -1515,6 +1528,20 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
       for (int k = 0; k < 4; ++k) same = same && sp->obst[4 * q + k] == sc.obst[q][k];
     if (!same) return bad("rollout: the obstacle table of the specification is not the one the obstacle script was set with");
   }
+  // with a mission the specification's step list is the TABLE of a leg's clock and the mission says how many steps an agent takes
+  const int n_run = b->mission_on ? b->mission_host.K : sp->n_steps;
+  if (b->mission_on) {
+    const MissionArgs& ms = b->mission_host;
+    if (b->script_on) return bad("rollout: a mission and an obstacle script are both set: the rollout kernel has no instance for the two");
+    if (!(b->plant_on ? b->inst.rollout_plant_mission : b->inst.rollout_mission) || !b->d_mission)
+      return bad("rollout: a mission is set (omgx_batch_set_mission) but this template class has no mission instance of the rollout kernel");
+    if (!b->stop_on) return bad("rollout: a mission is set but the stop rule is off (omgx_batch_set_stop): arriving is that rule");
+    if (ms.K > sp->n_steps) return bad("rollout: the mission runs %d steps per agent but the step table holds %d", ms.K, sp->n_steps);
+    if (ms.coeff_off != sp->coeff_off || ms.n_spl != sp->n_spl || ms.L != sp->n_knots - sp->degree - 1 || ms.p_t != sp->p_t)
+      return bad("rollout: the plan of the specification (coeff_off, n_spl, n_knots - degree - 1, p_t) is not the one the mission was set with");
+    if (ms.o_state0 != b->stop_host.o_state || ms.o_input0 != b->stop_host.o_input || ms.o_poseT != b->stop_host.o_pose || ms.n_spl != b->stop_host.n_dim)
+      return bad("rollout: o_state0 / o_input0 / o_poseT / n_spl of the mission are not those of the stop rule");
+  }
   RolloutArgs a;
   memset(&a, 0, sizeof a);
   TRY(check_predict_in_xp(b, "rollout", pl, sp->n_out, sp->p_off, sp->p_t, a.p_off));
@@ -1552,7 +1579,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   }
   std::vector<RolloutStep> steps((size_t)sp->n_steps);
   for (int k = 0; k < sp->n_steps; ++k) { steps[k].tau = sp->tau[k]; steps[k].t_rel = sp->t_rel[k]; steps[k].crossed = sp->crossed[k] ? 1 : 0; steps[k].pad = 0; }
-  a.steps = (const RolloutStep*)b->ro_steps.p; a.K = sp->n_steps;
+  a.steps = (const RolloutStep*)b->ro_steps.p; a.K = n_run; a.n_table = sp->n_steps;
   b->opts.prio_iter = b->prio_iter;
   a.o_cross = b->opts;
   if (sp->cross_options) {
@@ -1564,14 +1591,15 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   a.stop_on = b->stop_on ? 1 : 0; a.stop = b->stop_host;
   a.stats = nullptr;
   if (b->d_stats) {
-    if (sp->n_steps > b->stats_slots - (int)(b->stats_launch % b->stats_slots)) { g_err = "rollout: the stats array has fewer free slots than steps"; return OMGX_E_INVALID; }
+    if (n_run > b->stats_slots - (int)(b->stats_launch % b->stats_slots)) { g_err = "rollout: the stats array has fewer free slots than steps"; return OMGX_E_INVALID; }
     a.stats = (unsigned long long*)b->d_stats + 4 * (size_t)(b->stats_launch % b->stats_slots);
-    b->stats_launch += sp->n_steps;
+    b->stats_launch += n_run;
   }
   a.iters_log = sp->iters_log; a.status_log = sp->status_log;
   a.plant = b->plant_on ? b->d_plant : nullptr;
   a.script = b->script_on ? b->d_script : nullptr;
-  const ipm_rollout_t kern = b->script_on ? (b->plant_on ? b->inst.rollout_plant_script : b->inst.rollout_script)
+  a.mission = b->mission_on ? b->d_mission : nullptr;
+  const ipm_rollout_t kern = b->mission_on ? (b->plant_on ? b->inst.rollout_plant_mission : b->inst.rollout_mission) : b->script_on ? (b->plant_on ? b->inst.rollout_plant_script : b->inst.rollout_script)
                                           : (b->plant_on ? b->inst.rollout_plant : b->inst.rollout);
   // Two small copies per call (one call is n_steps steps of the whole batch), ORDERED ON THE HANDLE'S STREAM: the persistent
   // kernel of a previous rollout reads these tables for its whole run, and on a non-blocking caller stream a null-stream
@@ -1787,6 +1815,61 @@ int omgx_batch_set_obstacle_script(omgx_batch* b, const omgx_obstacle_script* sp
   b->script_host = a;
   TRY(push_args(b, &b->d_script, b->script_host));
   b->script_on = true;
+  return OMGX_OK;
+}
+
+int omgx_batch_set_mission(omgx_batch* b, const omgx_mission_spec* sp) {
+  if (!sp) {
+    if (!b) return bad("null handle");
+    b->mission_on = false;
+    return OMGX_OK;
+  }
+  if (!sp->goals || !sp->n_goals || !sp->leg || !sp->clock || !sp->arrivals || !sp->x_reset || !sp->cold)
+    return bad("set_mission: null goals / n_goals / leg / clock / arrivals / x_reset / cold");
+  if (sp->G < 1) return bad("set_mission: G = %d must be positive", sp->G);
+  if (sp->n_spl < 1 || sp->n_spl > kOwnedSpl || sp->L < 2) return bad("set_mission: n_spl = %d outside 1 .. %d or L = %d below 2", sp->n_spl, kOwnedSpl, sp->L);
+  if (sp->n_steps < 1 || sp->step_index < 0) return bad("set_mission: n_steps = %d must be positive and step_index = %d not negative", sp->n_steps, sp->step_index);
+  if (!(sp->cold->tol > 0) || sp->cold->max_iter < 0) return bad("set_mission: bad cold options");
+  if (!b) return bad("null handle");
+  const omgx::Dims& d = b->dims;
+  if (sp->coeff_off < 0 || sp->coeff_off + (long long)sp->n_spl * sp->L > d.n_var)
+    return bad("set_mission: coefficients outside x (coeff_off = %d, %d splines of %d, n_var = %d)", sp->coeff_off, sp->n_spl, sp->L, d.n_var);
+  if (!in_p(b, sp->o_state0, sp->n_spl) || !in_p(b, sp->o_input0, sp->n_spl) || !in_p(b, sp->o_poseT, sp->n_spl) || !in_p(b, sp->p_t, 1))
+    return bad("set_mission: o_state0 / o_input0 / o_poseT / p_t outside p");
+  b->mission_on = false;      // (a failed registration leaves the mission OFF)
+  HIPCHK(hipSetDevice(b->device));
+  if (!b->d_x_reset) TRY(dalloc(b, (size_t)d.n_var, &b->d_x_reset));
+  // (stream-ordered: a rollout still running reads the previous row)
+  HIPCHK(hipMemcpyAsync(b->d_x_reset, sp->x_reset, sizeof(double) * (size_t)d.n_var, hipMemcpyHostToDevice, b->stream));
+  MissionArgs a = {};
+  a.goals = sp->goals; a.n_goals = sp->n_goals; a.leg = sp->leg; a.clock = sp->clock; a.arrivals = sp->arrivals; a.x_reset = b->d_x_reset;
+  a.G = sp->G; a.o_state0 = sp->o_state0; a.o_input0 = sp->o_input0; a.o_poseT = sp->o_poseT; a.p_t = sp->p_t;
+  a.coeff_off = sp->coeff_off; a.n_spl = sp->n_spl; a.L = sp->L; a.n_var = d.n_var; a.n_con = d.n_con;
+  a.K = sp->n_steps; a.step0 = sp->step_index;
+  a.o_cold = opts_of(sp->cold);
+  a.o_cold.warm_start = 0; a.o_cold.prio_iter = b->prio_iter;
+  b->mission_host = a;
+  TRY(push_args(b, &b->d_mission, b->mission_host));
+  b->mission_on = true;
+  return OMGX_OK;
+}
+
+int omgx_batch_mission_advance(omgx_batch* b, double* p, double* x, double* lam_g, int32_t step_index) {
+  if (!p || !x || !lam_g) return bad("mission_advance: null p / x / lam_g");
+  if (step_index < 0) return bad("mission_advance: step_index = %d is negative", step_index);
+  if (!b) return bad("null handle");
+  if (!b->mission_on || !b->d_mission) return bad("mission_advance: no mission is set (omgx_batch_set_mission)");
+  if (!b->stop_on) return bad("mission_advance: the stop rule is off (omgx_batch_set_stop): arriving is that rule");
+  if (b->n_range > 0) return bad("mission_advance: not with two-sided rows (the caller's multipliers are not the kernel's rows)");
+  const MissionArgs& ms = b->mission_host;
+  if (ms.o_state0 != b->stop_host.o_state || ms.o_input0 != b->stop_host.o_input || ms.o_poseT != b->stop_host.o_pose || ms.n_spl != b->stop_host.n_dim)
+    return bad("mission_advance: o_state0 / o_input0 / o_poseT / n_spl of the mission are not those of the stop rule");
+  if (b->plant_on && (b->plant_host.pl.n_spl != ms.n_spl || b->plant_host.pl.p_poseT != ms.o_poseT || !b->plant_host.pl.under_way))
+    return bad("mission_advance: the plant set (omgx_batch_set_plant) is not one of the mission's splines and goal, or has no under_way");
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(mission_advance_kernel, dim3((b->n_agents + 3) / 4), dim3(256), 0, b->stream, p, x, lam_g, b->dims.n_par, b->n_agents,
+                     (const MissionArgs*)b->d_mission, b->stop_host, (const PlantBlock*)(b->plant_on ? b->d_plant : nullptr), step_index);
+  HIPCHK(hipGetLastError());
   return OMGX_OK;
 }
 

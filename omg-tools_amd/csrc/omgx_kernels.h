@@ -1444,6 +1444,95 @@ obstacles_advance_kernel(double* __restrict__ p, int n_par, int B, const Obstacl
 }
 
 // ---------------------------------------------------------------------------
+// Missions (omgx_batch_set_mission; include/omgx.h OMGX_HAS_MISSION states the semantics): a list of goals per agent.  When the stop
+// rule holds for an agent that has a goal left, the next leg starts: what the reference does between two `simulator.run()` calls --
+// `set_terminal_conditions`, `reinitialize`, the first update with `enforce_states`.  mission_next_leg_agent is the only statement
+// of that switch; its two callers are the stand-alone kernel below and the rollout kernel's MISSION instances.
+// ---------------------------------------------------------------------------
+struct MissionArgs {
+  const double* goals; const int32_t* n_goals;      // [B, G, n_spl], [B]
+  int32_t* leg; int32_t* clock; int32_t* arrivals;  // [B], [B], [B, 1 + G]
+  const double* x_reset;                            // [n_var]: the agent-independent row of the first guess (the handle's device copy)
+  int G, o_state0, o_input0, o_poseT, p_t, coeff_off, n_spl, L, n_var, n_con;
+  int K, step0;                                     // the following rollout: steps per agent, and the count its first step is stamped with
+  omgx::Opts o_cold;                                // the option set of a leg's first solve
+};
+
+// The leg switch of agent b, called by `nthr` threads tid = 0 .. nthr - 1 that own the agent (a workgroup, or one wave) with the same
+// arguments.  lg = leg[b], read by the caller ahead of its last barrier: the goal to fly to is goals[b][lg].  s_old (thread k <
+// n_spl: spline k): p[state0 + k] of the PREVIOUS update, where the guess starts; now [n_spl]: where the vehicle is (may be
+// p + o_state0 itself: thread k reads now[k] before it writes).  Thread k writes the L coefficients of spline k by numpy's linspace
+// statement, every product and sum rounded on its own.  No barrier inside: the caller parts it from what reads x, lam and p next.
+__device__ __noinline__ void mission_next_leg_agent(const MissionArgs& ms, int b, int lg, double* pb, double* xb, double* lamb, double s_old,
+                                                    const double* now, int step_index, int tid, int nthr) {
+#pragma clang fp contract(off)
+  const int n = ms.n_spl, L = ms.L, c_lo = ms.coeff_off, c_hi = ms.coeff_off + n * L;
+  for (int i = tid; i < ms.n_var; i += nthr)
+    if (i < c_lo || i >= c_hi) xb[i] = ms.x_reset[i];
+  for (int i = tid; i < ms.n_con; i += nthr) lamb[i] = 0.0;
+  if (tid < n) {
+    const int k = tid;
+    const double g = ms.goals[((size_t)b * ms.G + lg) * n + k], here = now[k];
+    const double delta = g - s_old;
+    const double step = delta / (double)(L - 1);
+    double* c = xb + c_lo + k * L;
+    for (int i = 0; i < L - 1; ++i) {
+      const double m = (double)i * step;
+      c[i] = m + s_old;
+    }
+    c[L - 1] = g;
+    pb[ms.o_poseT + k] = g;
+    pb[ms.o_state0 + k] = here;
+    pb[ms.o_input0 + k] = 0.0;
+    if (k == 0) {
+      pb[ms.p_t] = 0.0;
+      ms.clock[b] = 0;
+      ms.arrivals[(size_t)b * (ms.G + 1) + lg] = step_index;
+      ms.leg[b] = lg + 1;
+    }
+  }
+}
+
+// the plant's stop rule on the travelled state (the statements of plant_predict_agent's test)
+__device__ __forceinline__ bool mission_plant_arrived(const PlantArgs& pl, int b, const double* pb) {
+#pragma clang fp contract(off)
+  if (pl.n_upd[b] < 1) return false;
+  double e2 = 0.0, u2 = 0.0;
+  for (int k = 0; k < pl.n_spl; ++k) {
+    const double e = pl.state[(size_t)b * pl.n_spl + k] - pb[pl.p_poseT + k], u = pl.input_last[(size_t)b * pl.n_spl + k];
+    const double ee = e * e, uu = u * u;
+    e2 = e2 + ee; u2 = u2 + uu;
+  }
+  return sqrt(e2) <= pl.stop_tol && sqrt(u2) <= pl.stop_tol;
+}
+
+// stand-alone launch (omgx_batch_mission_advance): the arrival test and the switch without a solve; four agents share a workgroup,
+// one wave each.  plant (or nullptr): the rule is the plant's and the leg starts from the travelled state.
+__global__ void __launch_bounds__(256)
+mission_advance_kernel(double* __restrict__ p, double* __restrict__ x, double* __restrict__ lam, int n_par, int B,
+                       const MissionArgs* __restrict__ msp, StopArgs sa, const PlantBlock* __restrict__ plant, int step_index) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= B) return;
+  const MissionArgs& ms = *msp;
+  double* pb = p + (size_t)b * n_par;
+  if (sa.under_way[b] == 0) return;
+  const bool hit = plant ? mission_plant_arrived(plant->pl, b, pb) : omgx::stop_criterium(pb, sa.o_state, sa.o_input, sa.o_pose, sa.n_dim, sa.tol);
+  if (!hit) return;
+  const int lg = ms.leg[b];
+  if (lg < 0 || lg > ms.G) return;
+  const double s_old = lane < ms.n_spl ? pb[ms.o_state0 + lane] : 0.0;
+  // (one wave: every lane has its loads of the flag, the leg and the state behind it before lane 0 stores any of them)
+  __builtin_amdgcn_wave_barrier();
+  if (lg < ms.G && lg < ms.n_goals[b]) {
+    mission_next_leg_agent(ms, b, lg, pb, x + (size_t)b * ms.n_var, lam + (size_t)b * ms.n_con, s_old,
+                           plant ? plant->pl.state + (size_t)b * ms.n_spl : pb + ms.o_state0, step_index, lane, 64);
+  } else if (lane == 0) {
+    sa.under_way[b] = 0;
+    ms.arrivals[(size_t)b * (ms.G + 1) + lg] = step_index;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Rollout: K receding-horizon steps of every agent in ONE launch (omgx_batch_rollout).  Agents of a point-to-point batch
 // are independent, so nothing in the protocol asks for a barrier between the steps of different agents: a persistent
 // workgroup takes an agent and runs its whole loop -- ideal prediction from the current plan, obstacles advanced, the
@@ -1467,13 +1556,18 @@ struct RolloutArgs {
   StopArgs stop; int stop_on;           // omgx_batch_set_stop: an agent's loop ends at the step its state meets the criterion
   const PlantBlock* plant;              // omgx_batch_set_plant: read by the PLANT instance only
   const ObstacleScriptArgs* script;     // omgx_batch_set_obstacle_script: read by the SCRIPT instances only
+  const MissionArgs* mission;           // omgx_batch_set_mission: read by the MISSION instances only ...
+  int n_table;                          // ... as is the length of `steps`, there a table indexed by the agent's own leg clock
 };
 
 // PLANT (omgx_batch_set_plant): step (1) is the plant's predict + stop test on the travelled state, and after the solve the plant's
 // simulate takes the place of the log append; every other statement is the same one.
 // SCRIPT (omgx_batch_set_obstacle_script): step (2) is obstacles_advance_agent between the absolute times of the step; every other
 // statement is the same one.
-template <int MODE, bool WAVE_ONLY, bool GEN, bool PLANT = false, bool SCRIPT = false>
+// MISSION (omgx_batch_set_mission): the step record is steps[clock[b]], the agent's own leg clock; where the stop rule holds and the
+// agent has a goal left, mission_next_leg_agent runs instead of the end of the loop and that step's solve is the cold one; every other
+// statement is the same one.
+template <int MODE, bool WAVE_ONLY, bool GEN, bool PLANT = false, bool SCRIPT = false, bool MISSION = false>
 __global__ void __launch_bounds__(512)
 ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, double* __restrict__ p, double* __restrict__ x,
                    const double* __restrict__ lb, const double* __restrict__ ub, int bounds_shared, double* __restrict__ lam,
@@ -1502,11 +1596,45 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
     const double* lbb = lb + (bounds_shared ? 0 : (size_t)b * d.n_con);
     const double* ubb = ub + (bounds_shared ? 0 : (size_t)b * d.n_con);
     for (int k = 0; k < K; ++k) {
-      const RolloutStep st = rop->steps[k];
+      int ck = k;
+      [[maybe_unused]] bool leg_start = false;      // (MISSION: this step starts the agent's next leg)
+      [[maybe_unused]] double s_old = 0.0;          // (MISSION: p[state0] of the previous update, read ahead of the prediction)
+      if constexpr (MISSION) {
+        const MissionArgs& ms = *rop->mission;
+        ck = ms.clock[b];
+        if (ck < 0 || ck >= rop->n_table) break;      // (a clock outside the table the caller filled: the loop ends, nothing is read)
+        if ((int)threadIdx.x < ms.n_spl) s_old = pb[ms.o_state0 + threadIdx.x];
+      }
+      const RolloutStep st = rop->steps[ck];
       // (1) ideal prediction (predict_kernel): the plan and its time derivatives at tau, the new t
       if constexpr (PLANT) {
         // the plant's: state0 from the state the vehicle had one update ago, the stop rule on the travelled state -- an agent that
         // has arrived ends its loop here, ahead of the glue of the step: plan, multipliers and status stay as they are
+        if constexpr (MISSION) {
+          // (the flag ahead of the test tells a loop that ends now from one that had ended: only the former may start a leg)
+          const MissionArgs& ms = *rop->mission;
+          const int was = rop->plant->pl.under_way ? rop->plant->pl.under_way[b] : 0;
+          if (!plant_predict_agent(rop->plant->pl, b, xb + rop->plant->pl.coeff_off, pb, st.tau, st.t_rel, w.kkt)) {
+            const int lg = ms.leg[b];
+            leg_start = was != 0 && lg >= 0 && lg < ms.G && lg < ms.n_goals[b];
+            __syncthreads();      // (every thread has read the leg; thread 0 has cleared the flag)
+            if (leg_start) {
+              // the next leg starts from the travelled state; p is as the previous update left it: p[state0] is the stale one
+              mission_next_leg_agent(ms, b, lg, pb, xb, lamb, s_old, rop->plant->pl.state + (size_t)b * ms.n_spl, ms.step0 + k, threadIdx.x, blockDim.x);
+              if (threadIdx.x == 0) rop->plant->pl.under_way[b] = 1;
+            } else {
+              if (threadIdx.x == 0) {
+                if (was != 0 && lg >= 0 && lg <= ms.G) ms.arrivals[(size_t)b * (ms.G + 1) + lg] = ms.step0 + k;
+                iters[b] = 0;
+                for (int k2 = k; k2 < K; ++k2) {
+                  if (rop->iters_log) rop->iters_log[(size_t)k2 * n_agents + b] = 0;
+                  if (rop->status_log) rop->status_log[(size_t)k2 * n_agents + b] = status[b];
+                }
+              }
+              break;
+            }
+          }
+        } else
         if (!plant_predict_agent(rop->plant->pl, b, xb + rop->plant->pl.coeff_off, pb, st.tau, st.t_rel, w.kkt)) {      // (the KKT store is idle between two solves: scratch)
           if (threadIdx.x == 0) {
             iters[b] = 0;
@@ -1553,7 +1681,7 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
       }
       __syncthreads();
       // (3) knot crossing: plan <- T plan, multipliers by index (the KKT store is idle between two solves: scratch)
-      if (st.crossed) {
+      if (st.crossed && !leg_start) {      // (a leg that starts here has a fresh plan and no multipliers)
         shift_row(xb, rop->sh_ent, rop->n_ent, rop->sh_T, w.kkt);
         for (int i = threadIdx.x; i < d.n_con; i += blockDim.x) w.kkt[i] = lamb[i];
         __syncthreads();
@@ -1566,8 +1694,23 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
       if (rop->stop_on) {
         const StopArgs sa = rop->stop;
         bool go = sa.under_way[b] != 0;
+        [[maybe_unused]] const bool was = go;
         if (go && omgx::stop_criterium(pb, sa.o_state, sa.o_input, sa.o_pose, sa.n_dim, sa.tol)) go = false;
         __syncthreads();
+        if constexpr (MISSION && !PLANT) {
+          if (was && !go) {      // (arrived now: the same branch in every thread)
+            const MissionArgs& ms = *rop->mission;
+            const int lg = ms.leg[b];
+            leg_start = lg >= 0 && lg < ms.G && lg < ms.n_goals[b];
+            __syncthreads();      // (every thread has read the leg)
+            if (leg_start) {
+              // the state the prediction of this step wrote is where the vehicle is now; the arrival test is not repeated on the new goal
+              mission_next_leg_agent(ms, b, lg, pb, xb, lamb, s_old, pb + ms.o_state0, ms.step0 + k, threadIdx.x, blockDim.x);
+              __syncthreads();
+              go = true;
+            } else if (lg >= 0 && lg <= ms.G && threadIdx.x == 0) ms.arrivals[(size_t)b * (ms.G + 1) + lg] = ms.step0 + k;
+          }
+        }
         if (!go) {
           if (threadIdx.x == 0) {
             sa.under_way[b] = 0; iters[b] = 0;
@@ -1580,8 +1723,16 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
         }
       }
       // (4) warm-started solve, results back to the agent's rows
-      const omgx::Result r = omgx::ipm_solve(c, d, T, st.crossed ? rop->o_cross : o, w, pb, xb, lbb, ubb, o.warm_start ? lamb : nullptr,
-                                             o.warm_start ? status[b] : 0, kkt_doubles, o.warm_start ? dw_state[b] : 0.0);
+      omgx::Result r;
+      if constexpr (MISSION) {
+        // (a leg's first solve is the cold one: its own option set, no multipliers, no status, no carried inertia correction)
+        omgx::Opts os = st.crossed ? rop->o_cross : o;
+        if (leg_start) os = rop->mission->o_cold;
+        const bool warm = o.warm_start && !leg_start;
+        r = omgx::ipm_solve(c, d, T, os, w, pb, xb, lbb, ubb, warm ? lamb : nullptr, warm ? status[b] : 0, kkt_doubles, warm ? dw_state[b] : 0.0);
+      } else
+      r = omgx::ipm_solve(c, d, T, st.crossed ? rop->o_cross : o, w, pb, xb, lbb, ubb, o.warm_start ? lamb : nullptr,
+                          o.warm_start ? status[b] : 0, kkt_doubles, o.warm_start ? dw_state[b] : 0.0);
       __builtin_amdgcn_s_setprio(0);
       __syncthreads();
       for (int i = threadIdx.x; i < d.n_var; i += blockDim.x) xb[i] = w.x[i];
@@ -1598,6 +1749,7 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
         }
         if (rop->iters_log) rop->iters_log[(size_t)k * n_agents + b] = r.iters;
         if (rop->status_log) rop->status_log[(size_t)k * n_agents + b] = r.status;
+        if constexpr (MISSION) { if (!leg_start) rop->mission->clock[b] = ck + 1; }      // (the switch has set a new leg's clock to 0)
       }
       if (stp) {      // `Vehicle.store` of this step (omgx_batch_set_store), as in the solve kernel's epilogue
         const StoreArgs st2 = *stp;
@@ -1760,8 +1912,17 @@ __global__ void admm_comm_kernel(omgx_admm_layout lay, const int32_t* __restrict
 typedef void (*ipm_rollout_t)(omgx::Dims, omgx::Tables, omgx::Opts, int, double*, double*, const double*, const double*, int, double*,
                               int32_t*, int32_t*, int, double*, size_t, double*, int*, const RolloutArgs*, int, const int32_t*, const StoreArgs*);
 // (the classes of the wave path without quartic terms / cos / sin atoms: the receding-horizon classes that fit LDS)
-static ipm_rollout_t rollout_kernel_for(int mode, int wave_ok, int general, int plant = 0, int script = 0) {
+static ipm_rollout_t rollout_kernel_for(int mode, int wave_ok, int general, int plant = 0, int script = 0, int mission = 0) {
   if (!wave_ok || general) return nullptr;
+  if (mission) {      // (the instances with a mission: the same three modes, with and without the plant; none with a script)
+    if (script) return nullptr;
+    switch (mode) {
+      case omgx::WS_LDS: return plant ? ipm_rollout_kernel<omgx::WS_LDS, true, false, true, false, true> : ipm_rollout_kernel<omgx::WS_LDS, true, false, false, false, true>;
+      case omgx::WS_JAC_ONLY: return plant ? ipm_rollout_kernel<omgx::WS_JAC_ONLY, true, false, true, false, true> : ipm_rollout_kernel<omgx::WS_JAC_ONLY, true, false, false, false, true>;
+      case omgx::WS_JAC_HV: return plant ? ipm_rollout_kernel<omgx::WS_JAC_HV, true, false, true, false, true> : ipm_rollout_kernel<omgx::WS_JAC_HV, true, false, false, false, true>;
+      default: return nullptr;
+    }
+  }
   if (script) {      // (the instances with an obstacle script: the same three modes, with and without the plant)
     switch (mode) {
       case omgx::WS_LDS: return plant ? ipm_rollout_kernel<omgx::WS_LDS, true, false, true, true> : ipm_rollout_kernel<omgx::WS_LDS, true, false, false, true>;

@@ -234,6 +234,14 @@ class CObstacleScript(C.Structure):
                 ('n_ev', C.c_int32), ('n_obst', C.c_int32)]
 
 
+class CMissionSpec(C.Structure):
+    """include/omgx.h omgx_mission_spec"""
+    _fields_ = [('goals', C.c_void_p), ('n_goals', C.c_void_p), ('leg', C.c_void_p), ('clock', C.c_void_p), ('arrivals', C.c_void_p),
+                ('x_reset', C.c_void_p), ('cold', C.c_void_p),
+                ('G', C.c_int32), ('o_state0', C.c_int32), ('o_input0', C.c_int32), ('o_poseT', C.c_int32), ('p_t', C.c_int32),
+                ('coeff_off', C.c_int32), ('n_spl', C.c_int32), ('L', C.c_int32), ('n_steps', C.c_int32), ('step_index', C.c_int32)]
+
+
 PREDICT_IDEAL, PREDICT_RK4 = 0, 1
 ONLY_FAILED = 8
 
@@ -373,6 +381,8 @@ PROTOTYPES = {
     'omgx_batch_plant_quadrotor_predict': (C.c_int, [_H, _P, _P, _D, _D, C.POINTER(CQuadPlantSpec), _P, _P, _I]),
     'omgx_batch_obstacles_advance': (C.c_int, [_H, _P, C.POINTER(CObstacleScript), _D, _D]),
     'omgx_batch_set_obstacle_script': (C.c_int, [_H, C.POINTER(CObstacleScript), _P, _I]),
+    'omgx_batch_set_mission': (C.c_int, [_H, C.POINTER(CMissionSpec)]),
+    'omgx_batch_mission_advance': (C.c_int, [_H, _P, _P, _P, _I]),
     'omgx_shift_rows': (C.c_int, [_H, _P, _I, _I, _P, _P, _I, _P, _I]),
     'omgx_admm_center': (C.c_int, [_H, _LAY] + [_P] * 3),
     'omgx_admm_update': (C.c_int, [_H, _LAY] + [_P] * 4 + [_D] + [_P] * 4),
@@ -908,6 +918,43 @@ class BatchSolver(object):
         _check(self.lib, self.lib.omgx_batch_set_obstacle_script(self._h, C.byref(sp), t_abs.ctypes.data, len(t_abs)),
                'omgx_batch_set_obstacle_script')
         self._script = sp
+
+    def set_mission(self, mission=None, n_steps=1, step_index=0, cold_options=None):
+        """Every following `rollout` flies the agents' goal lists (include/omgx.h omgx_batch_set_mission; mission=None: off): each agent
+        takes n_steps steps, stamped from step_index on, and the step list of `rollout` is the table of a leg's own clock.  mission: dict
+        of the device tensors goals [B, G, n_spl] fp64, n_goals / leg / clock [B] and arrivals [B, 1 + G] int32, the host row x_reset
+        [n_var] and the offsets o_state0 / o_input0 / o_poseT / p_t / coeff_off / n_spl / L.  cold_options: what a leg's first solve
+        changes of the handle's options (warm_start = 0 is the library's).  The tensors are kept alive here while it is set."""
+        if mission is None:
+            self._mission = None
+            _check(self.lib, self.lib.omgx_batch_set_mission(self._h, None), 'omgx_batch_set_mission')
+            return
+        m = mission
+        G = int(m['goals'].shape[1]) if hasattr(m['goals'], 'shape') and len(m['goals'].shape) == 3 else 0
+        _need('goals', m['goals'], (self._B, 'G', ('n_spl', m['n_spl'])), 'float64 device')
+        for nm in ('n_goals', 'leg', 'clock'):
+            _need(nm, m[nm], (self._B,), 'int32 device')
+        _need('arrivals', m['arrivals'], (self._B, ('1 + G', 1 + G)), 'int32 device')
+        x_reset = np.ascontiguousarray(m['x_reset'], dtype=np.float64)
+        if x_reset.shape != (self.template.n_var,):
+            raise ValueError('x_reset must be [n_var] = [%d]' % self.template.n_var)
+        cold = COptions(**dict(self.options, **(cold_options or {})))
+        sp = CMissionSpec(m['goals'].data_ptr(), m['n_goals'].data_ptr(), m['leg'].data_ptr(), m['clock'].data_ptr(), m['arrivals'].data_ptr(),
+                          x_reset.ctypes.data, C.addressof(cold), G, int(m['o_state0']), int(m['o_input0']), int(m['o_poseT']), int(m['p_t']),
+                          int(m['coeff_off']), int(m['n_spl']), int(m['L']), int(n_steps), int(step_index))
+        _check(self.lib, self.lib.omgx_batch_set_mission(self._h, C.byref(sp)), 'omgx_batch_set_mission')
+        self._mission = (m, x_reset)
+
+    def mission_advance(self, p, x, lam_g, step_index):
+        """The arrival test and the leg switch of the mission set, without a solve (include/omgx.h omgx_batch_mission_advance): one
+        launch on device tensors p [B, n_par], x [B, n_var], lam_g [B, n_con]."""
+        _need('p', p, (self._B, self.template.n_par), 'float64 device')
+        _need('x', x, (self._B, self.template.n_var), 'float64 device')
+        _need('lam_g', lam_g, (self._B, self.template.n_con), 'float64 device')
+        if not (p.is_cuda and x.is_cuda and lam_g.is_cuda):
+            raise ValueError('p, x and lam_g must be device tensors')
+        _check(self.lib, self.lib.omgx_batch_mission_advance(self._h, p.data_ptr(), x.data_ptr(), lam_g.data_ptr(), int(step_index)),
+               'omgx_batch_mission_advance')
 
     def set_plant(self, plant=None, log=None):
         """Every following `rollout` runs with the plant in the loop (include/omgx.h omgx_batch_set_plant; plant=None: off).  The

@@ -10,7 +10,7 @@ with a primal-dual warm start.
 Layout: `BatchP2P` states that protocol once -- tables and options from the template, `solve_cold`, `step`, `rollout`, the stop rule,
 the log -- and branches on no executor.  Where the [B, *] arrays live and who computes on them sits behind its hooks (`_allocate,
 _predict, _shift, _solve, _cold, _rollout, _norm, _stop_rule, _signals_alloc, _signals_fused, _signals_append_now,
-_signals_summary, _zeros, _plant_alloc, _plant_lag, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
+_signals_summary, _zeros, _plant_alloc, _plant_lag, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance, _mission_alloc, _mission_off, _mission_clock_max, _mission_run, _mission_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
 being the allocator / stream only; no data leaves HBM between steps) and `HostP2P` (`ops=<a host solver object>`: the same
 statements in numpy, how the parity tests and the CPU baseline of bench.py replay the loop; this package never imports the
 oracle).  `BatchP2P(problem, P, ops=...)` hands out the executor `ops` names.  The clock of a step is `splines.step_clock`, the
@@ -25,6 +25,8 @@ with `time_constant` the vehicle applies them through the reference's first-orde
 `Deployer.update(current_time, states, ...)`; include/omgx.h OMGX_HAS_FEEDBACK): a loop has one source of states.
 `BatchP2P.obstacle_script` moves the obstacles by the reference's `simulation={'trajectories': ...}` -- jumps of position, velocity
 or acceleration at given times (include/omgx.h OMGX_HAS_OBSTACLE_SCRIPT; `splines.advance_obstacles_scripted` in numpy).
+`BatchP2P.mission` gives every agent a list of goals: inside `rollout` an agent that arrives starts its next leg -- fresh guess, cold
+solve, a clock of its own -- instead of ending its loop (include/omgx.h OMGX_HAS_MISSION; `mission_next_leg_numpy` in numpy).
 """
 import math
 import os
@@ -167,6 +169,8 @@ class BatchP2P(object):
         self._pl = None                                   # (plant)
         self._fb = None                                   # (feedback)
         self._sc = None                                   # (obstacle_script)
+        self._ms = None                                   # (mission)
+        self._x0 = P['x0']                                # (the batch's first guess: `mission` keeps its agent-independent part)
         self._plan_ready = False                          # (solve_cold has run: x holds a plan)
         # (warm_mu_factor 0.1: a step starts at the barrier parameter the previous solve of the agent ended with, tol / 10,
         # unless the shifted point is far off that central path -- a tenth of its average complementarity then: at tol 1e-3
@@ -221,6 +225,9 @@ class BatchP2P(object):
         None: all): an agent with 0 has no measurement at this update and is predicted from its plan.  enforce: the solve starts
         from `states` as they are, with `inputs` [B, n_spl] (None: zero) as its initial input (`enforce_states` / `enforce_inputs`).
         Device loop: device or pinned host tensors (include/omgx.h omgx_batch_predict_measured); host loop: arrays."""
+        if self._ms is not None:
+            raise RuntimeError('step(): a mission is on -- its agents run on clocks of their own and a solve launch has one option set and '
+                               'one clock: step with rollout(1)')
         if states is None:
             if inputs is not None or fresh is not None or enforce:
                 raise ValueError('step: inputs / fresh / enforce go with states')
@@ -268,6 +275,8 @@ class BatchP2P(object):
         Returns the number of knot crossings."""
         if self._pl is not None and self._pl.get('model') == 'quadrotor':
             raise NotImplementedError("rollout: the Quadrotor's plant runs per step only (`step`): the rollout kernel has no instance for it")
+        if self._ms is not None:
+            return self._mission_rollout(int(n_steps), iters_log, status_log)
         clock, t, t_abs = [], self.time, [self.time]
         for _ in range(int(n_steps)):
             t, tau, t_rel, crossed = step_clock(t, self.update_time, self.knot_time, self.T)
@@ -279,6 +288,99 @@ class BatchP2P(object):
 
     def _rollout(self, tau, t_rel, crossed, iters_log, status_log, t_abs=None):
         raise NotImplementedError('rollout is a device launch')
+
+    # -- missions: a list of goals per agent -------------------------------------------------------------
+    def mission(self, goals, n_goals=None, on=True):
+        """Give every agent a list of goals to fly one after the other inside `rollout`, as the reference's examples do with a second
+        `simulator.run()` after `vehicle.set_terminal_conditions(...)` or a `Deployer` loop over via points (include/omgx.h
+        OMGX_HAS_MISSION has the statements).  goals [B, G, n_dim]: the goals AFTER the one already in p[poseT]; n_goals [B] (0 .. G,
+        default G): how many of them an agent flies.  Needs `stop_at_arrival`: arrival is that rule (with `plant`: the plant's, on the
+        travelled state).  From now on, when the rule holds for an agent at the head of a step of `rollout` and it has a goal left, that
+        step starts the next leg instead of ending the loop: poseT <- the goal, the plan <- the reference's fresh guess (per axis
+        `np.linspace` from the state0 of the PREVIOUS update, one update stale as in the reference, to the goal; every other variable
+        the agent-independent value of the batch's first guess), multipliers <- 0, state0 <- the state the vehicle is in now, input0
+        <- 0, t <- 0, and a cold solve (`max_iter` of `solve_cold`, the base options, no bends); from there the agent runs on its own
+        clock, the leg's.  Only arrival at the last goal clears `under_way[b]`.  `mission_state()` returns `leg` [B] (index of the goal
+        being flown, 0 = the one in p), `clock` [B] (receding-horizon steps of the current leg behind its first solve; starts at the
+        batch's own count) and `arrivals` [B, 1 + G] (the rollout step, counted from this call, at whose head each goal was found
+        reached; -1: not yet).  `rollout(1)` is the per-step form; `step()` is refused (a solve launch has one option set and one
+        clock).  The batch's own `time` stays the absolute clock on the update grid.  Point-mass classes; not with an obstacle script,
+        the Quadrotor's plant or a host pool.  on=False: the stop rule ends loops again."""
+        if not on:
+            self._ms = None
+            return self._mission_off()
+        if self.under_way is None:
+            raise RuntimeError('mission(): call stop_at_arrival() first -- arriving is that rule')
+        if getattr(self, 'pool', None) is not None:
+            raise NotImplementedError('mission: not with a host pool (its workers run the step glue themselves)')
+        if self._sc is not None:
+            raise NotImplementedError('mission: not with an obstacle script (the rollout kernel has no script x mission instance)')
+        if self._pl is not None and self._pl.get('model') == 'quadrotor':
+            raise NotImplementedError("mission: not with the Quadrotor's plant (it runs per step only, a mission inside `rollout`)")
+        o_pose = self._o_pose('mission')
+        if self.n_spl != self.n_dim:
+            raise NotImplementedError('mission(): the fresh guess of a leg is the point-mass classes\' (one spline per axis)')
+        goals = np.ascontiguousarray(goals, dtype=float)
+        if goals.ndim != 3 or goals.shape[0] != self.B or goals.shape[1] < 1 or goals.shape[2] != self.n_dim or not np.isfinite(goals).all():
+            raise ValueError('mission: goals must be finite [B, G, n_dim] = [%d, G >= 1, %d], got %s' % (self.B, self.n_dim, list(goals.shape)))
+        G = goals.shape[1]
+        n_goals = np.full(self.B, G, dtype=np.int32) if n_goals is None else np.asarray(n_goals)
+        if n_goals.shape != (self.B,) or n_goals.dtype.kind not in 'iu' or (n_goals < 0).any() or (n_goals > G).any():
+            raise ValueError('mission: n_goals must be [B] integers in 0 .. %d' % G)
+        x0 = np.asarray(self._x0, dtype=float)
+        blk = np.ones(self.tpl.n_var, dtype=bool)
+        blk[self.o_spl:self.o_spl + self.n_spl * self.L] = False
+        if (x0[:, blk] != x0[0, blk]).any():
+            raise ValueError('mission: the first guess x0 differs between agents outside the spline block; a leg restarts from one row')
+        # the leg clock carries on from the batch's: the number of updates `step_clock` needs from 0 to the batch's time
+        t, n_upd = 0.0, 0
+        while t < self.time - 1e-9:
+            t, n_upd = step_clock(t, self.update_time, self.knot_time, self.T)[0], n_upd + 1
+        if abs(t - self.time) > 1e-9:
+            raise ValueError('mission: the batch time %g is not on the update grid' % self.time)
+        ms = dict(G=G, o_pose=o_pose, x_reset=np.ascontiguousarray(x0[0]).copy(), steps=0)
+        ms.update(self._mission_alloc(goals, n_goals.astype(np.int32), n_upd))
+        self._ms = ms
+
+    def mission_state(self):
+        """dict `leg` [B], `clock` [B], `arrivals` [B, 1 + G] of `mission` (int32; device tensors on the device loop, arrays on the host loop)."""
+        if self._ms is None:
+            raise RuntimeError('mission_state(): call mission() first')
+        return dict((nm, self._ms[nm]) for nm in ('leg', 'clock', 'arrivals'))
+
+    def mission_advance(self):
+        """The arrival test and the leg switch of `mission` WITHOUT the solve, on the batch as it stands (`omgx_batch_mission_advance`):
+        an agent under way for which the rule holds starts its next leg -- the guess runs from p[state0] as it stands, state0 is where
+        the vehicle is (p[state0]; with `plant` the travelled state) -- or, at its last goal, stops.  Counts as one rollout step in
+        `arrivals`.  How the switch is looked at on its own: behind a solve the guess is gone."""
+        if self._ms is None:
+            raise RuntimeError('mission_advance(): call mission() first')
+        self._mission_advance(self._ms['steps'])
+        self._ms['steps'] += 1
+
+    def _mission_table(self, n):
+        """The step records (tau, t_rel, crossed) of a leg's clock 0 .. n - 1: `step_clock` iterated from the leg-local time 0 -- the
+        same table for every agent and every leg, and for the first leg the records of the batch's own clock."""
+        out, t = [], 0.0
+        for _ in range(int(n)):
+            t, tau, t_rel, crossed = step_clock(t, self.update_time, self.knot_time, self.T)
+            out.append((tau, t_rel, crossed))
+        return out
+
+    def _mission_rollout(self, n_steps, iters_log, status_log):
+        if n_steps < 1:
+            raise ValueError('rollout: n_steps must be positive')
+        if self._sc is not None:
+            raise NotImplementedError('rollout: a mission and an obstacle script are both on (the rollout kernel has no script x mission instance)')
+        table = self._mission_table(self._mission_clock_max() + n_steps)
+        t, crossings = self.time, 0
+        for _ in range(n_steps):      # (the batch's own clock: absolute, on the update grid, whatever the legs do)
+            t, _, _, crossed = step_clock(t, self.update_time, self.knot_time, self.T)
+            crossings += int(crossed)
+        self._mission_run(table, n_steps, iters_log, status_log)
+        self._ms['steps'] += n_steps
+        self.time = t
+        return crossings
 
     # -- obstacle scripts ----------------------------------------------------------------------------
     def _advance_obstacles(self, t_prev, t_now):
@@ -310,6 +412,8 @@ class BatchP2P(object):
             return
         if getattr(self, 'pool', None) is not None:
             raise NotImplementedError('obstacle_script: not with a host pool (its workers run the step glue themselves)')
+        if self._ms is not None:
+            raise NotImplementedError('obstacle_script: a mission is on (the rollout kernel has no script x mission instance)')
         obstacles = self.problem.environment.obstacles
         if events is None:
             rows = []
@@ -413,6 +517,8 @@ class BatchP2P(object):
             o_pose = self._o_pose('stop_at_arrival') if on else None
         if on:
             self.stop_tol = float(stop_tol)
+        elif self._ms is not None:
+            self.mission(None, on=False)                    # (a mission is a use of the rule: it goes with it)
         self._stop_rule(o_pose)
 
     # -- the travelled trajectories ----------------------------------------------------------------
@@ -471,6 +577,8 @@ class BatchP2P(object):
     def _plant_quadrotor(self, sample_time, max_updates, disturbance, time_constant, gravity):
         """`plant(model='quadrotor')`: the Quadrotor's own model in the loop (include/omgx.h OMGX_HAS_PLANT_QUADROTOR)."""
         self._quad_model('plant', 'quadrotor')
+        if self._ms is not None:
+            raise NotImplementedError("plant(): model='quadrotor' runs per step only, a mission inside `rollout`")
         if time_constant is not None:
             raise NotImplementedError("plant(): the first-order actuator lag is not simulated with model='quadrotor'")
         if self._plan_ready:
@@ -802,6 +910,35 @@ class DeviceP2P(BatchP2P):
                             p_off=self.p_offs, p_t=self.o_t, obstacles=self.obst, dt=self.update_time, shift_entries=self.shift_entries, shift_T=self.shift_mats,
                             lam_perm=self.perm, cross_options=self.cross_options or None, iters_log=iters_log, status_log=status_log,
                             **self._plan)
+
+    # -- missions: registered with the handle, flown by the rollout kernel's mission instances --------------------------------------
+    def _mission_alloc(self, goals, n_goals, clock0):
+        t = self.torch
+        i32 = dict(dtype=t.int32, device=self.dev)
+        return dict(goals=t.as_tensor(goals, dtype=t.float64).to(self.dev).contiguous(), n_goals=t.as_tensor(n_goals, dtype=t.int32).to(self.dev),
+                    leg=t.zeros(self.B, **i32), clock=t.full((self.B,), clock0, **i32), arrivals=t.full((self.B, 1 + goals.shape[1]), -1, **i32))
+
+    def _mission_set(self, n_steps):
+        ms = self._ms
+        spec = dict((nm, ms[nm]) for nm in ('goals', 'n_goals', 'leg', 'clock', 'arrivals', 'x_reset'))
+        spec.update(o_state0=self.o_state0, o_input0=self.o_input0, o_poseT=ms['o_pose'], p_t=self.o_t, coeff_off=self.o_spl, n_spl=self.n_spl, L=self.L)
+        # (a leg's first solve: what `solve_cold` sets)
+        self.solver.set_mission(spec, n_steps=n_steps, step_index=ms['steps'], cold_options=dict(self._base_extra, max_iter=self.max_iter_cold))
+
+    def _mission_off(self):
+        self.solver.set_mission(None)
+
+    def _mission_clock_max(self):
+        return int(self._ms['clock'].max().item())
+
+    def _mission_run(self, table, n_steps, iters_log, status_log):
+        self._mission_set(n_steps)
+        self._rollout(*([r[k] for r in table] for k in range(3)), iters_log=iters_log, status_log=status_log)
+
+    def _mission_advance(self, step_index):
+        self._plant_rollout()                               # (the plant as registered with the handle: its rule, its travelled state)
+        self._mission_set(1)
+        self.solver.mission_advance(self.p, self.x, self.lam, step_index)
 
     def _norm(self, a):
         return a.norm(dim=1)
@@ -1230,6 +1367,104 @@ class HostP2P(BatchP2P):
     def _script_advance(self, t_prev, t_now):
         advance_obstacles_scripted(self.p, self.obst, self._sc, t_prev, t_now, dt=self.update_time)
 
+    # -- missions: the rollout kernel's MISSION instances and `omgx_batch_mission_advance` in numpy ----------------------------------
+    def _mission_alloc(self, goals, n_goals, clock0):
+        return dict(goals=goals.copy(), n_goals=n_goals.copy(), leg=np.zeros(self.B, dtype=np.int32), clock=np.full(self.B, clock0, dtype=np.int32),
+                    arrivals=np.full((self.B, 1 + goals.shape[1]), -1, dtype=np.int32))
+
+    def _mission_off(self):
+        pass
+
+    def _mission_clock_max(self):
+        return int(self._ms['clock'].max())
+
+    def _mission_switch(self, rows, s_old, state_now, step_index):
+        ms = self._ms
+        mission_next_leg_numpy(rows, ms['goals'], ms['leg'], ms['clock'], ms['arrivals'], self.p, self.x, self.lam, s_old, state_now, step_index,
+                               ms['x_reset'], self.o_spl, self.L, self.o_state0, self.o_input0, ms['o_pose'], self.o_t)
+
+    def _mission_arrived(self):
+        """Who meets the stop rule now (the plant's rule asks for a simulated update, as `_plant_predict` does)."""
+        return self.arrived(self.stop_tol) & ((self._pl['n_upd'] >= 1) if self._pl is not None else True)
+
+    def _mission_advance(self, step_index):
+        ms = self._ms
+        hit = self.under_way & self._mission_arrived()
+        start = hit & (ms['leg'] < ms['n_goals'])
+        for b in np.flatnonzero(hit & ~start):
+            ms['arrivals'][b, ms['leg'][b]] = step_index
+        self.under_way &= ~(hit & ~start)
+        now = self._pl['state'] if self._pl is not None else self.p[:, self.o_state0:self.o_state0 + self.n_dim].copy()
+        self._mission_switch(np.flatnonzero(start), self.p[:, self.o_state0:self.o_state0 + self.n_dim].copy(), now, step_index)
+
+    def _solve_rows(self, idx, warm, extra=None):
+        """The agents `idx` solved as a batch of their own (independent problems: the same results), warm or -- a leg start -- cold."""
+        kw = dict(self.opts, warm_start=int(warm), max_iter=self.max_iter_step if warm else self.max_iter_cold, **(extra or {}))
+        dw = self.dw[idx].copy() if warm else np.zeros(len(idx))
+        r = self.port.solve(self.tpl, self.p[idx], self.x[idx], lam_g0=self.lam[idx] if warm else None, status0=self.status[idx] if warm else None,
+                            n_threads=self.n_threads, dw_state=dw, **kw)
+        self.x[idx], self.lam[idx], self.status[idx], self.iters[idx], self.dw[idx] = r['x'], r['lam_g'], r['status'], r['iters'], dw
+
+    def _mission_run(self, table, n_steps, iters_log, status_log):
+        for k in range(n_steps):
+            self._mission_step(table, self._ms['steps'] + k)
+            if iters_log is not None:
+                iters_log[k] = self.iters
+            if status_log is not None:
+                status_log[k] = self.status
+
+    def _mission_step(self, table, step_index):
+        """One step of every agent as the rollout kernel's MISSION instance runs it: the agents grouped by their leg clocks, the glue
+        statements of `step` applied per group with that group's record, the switch at the stop test, then the solves -- leg starts
+        cold, the others warm (the crossing ones with `cross_options`) -- each group an index sub-batch."""
+        ms, pl = self._ms, self._pl
+        n, o_s = self.n_dim, self.o_state0
+        under0 = self.under_way.copy()
+        self.iters = np.zeros(self.B, dtype=np.int32)
+        snap = (self.p.copy(), self.x.copy(), self.lam.copy())
+        out = [a.copy() for a in snap]
+        s_old = snap[0][:, o_s:o_s + n].copy()                # (p[state0] of the previous update: read ahead of the prediction)
+        final, start, crossing = (np.zeros(self.B, dtype=bool) for _ in range(3))
+        for c in np.unique(ms['clock'][under0]):
+            grp = under0 & (ms['clock'] == c)
+            tau, t_rel, crossed = table[c]
+            self.p, self.x, self.lam = (a.copy() for a in snap)
+            self.under_way = grp.copy()
+            if pl is None:
+                self._predict(tau, t_rel)
+            else:
+                self._plant_predict(tau, t_rel)               # (ends the loops of the group's arrived agents ahead of the glue)
+            hit = grp & ~self.under_way
+            advance_obstacles(self.p, self.obst, self.update_time)
+            if crossed:
+                self._shift()
+            if pl is None:
+                hit = grp & self.arrived(self.stop_tol)
+            go_on = hit & (ms['leg'] < ms['n_goals'])
+            # an agent that stops for good keeps what the kernel leaves it: with the plant its rows as they were, else the glue's
+            take = grp & ~(hit & ~go_on) if pl is not None else grp
+            for dst, src in zip(out, (self.p, self.x, self.lam)):
+                dst[take] = src[take]
+            final |= hit & ~go_on
+            start |= go_on
+            crossing |= grp & ~hit & bool(crossed)
+        self.p, self.x, self.lam = out
+        for b in np.flatnonzero(final):
+            ms['arrivals'][b, ms['leg'][b]] = step_index
+        now = pl['state'] if pl is not None else self.p[:, o_s:o_s + n].copy()
+        self._mission_switch(np.flatnonzero(start), s_old, now, step_index)
+        self.under_way = under0 & ~final
+        warm = self.under_way & ~start
+        for idx, is_warm, extra in ((np.flatnonzero(start), False, None), (np.flatnonzero(warm & ~crossing), True, None),
+                                    (np.flatnonzero(warm & crossing), True, self.cross_options)):
+            if len(idx):
+                self._solve_rows(idx, is_warm, extra)
+        ms['clock'][warm] += 1
+        if pl is not None:
+            self._plant_simulate()                            # (the vehicles of the agents solved travel the update; it writes the log)
+        elif self._log_in_solve:
+            self._signals_append_host(self.under_way)
+
     def _feedback_predict(self, tau, t_rel, states, inputs, fresh, enforce):
         """`omgx_batch_predict_measured` in numpy: an agent without a fresh measurement as `_predict`, one with as `_plant_predict`
         with the measured state in the place of `state_prev` (the same statements: the same bits), or the given values (enforce)."""
@@ -1253,6 +1488,30 @@ class HostP2P(BatchP2P):
 
     def _signals_summary(self, target):
         return signals_summary_numpy(self._sig['log'], self._sig['count'], target, self._sig['sample_time'])
+
+
+def mission_next_leg_numpy(rows, goals, leg, clock, arrivals, p, x, lam, s_old, state_now, step_index, x_reset, o_spl, L, o_state0, o_input0,
+                           o_poseT, o_t):
+    """`mission_next_leg_agent` (csrc/omgx_kernels.h) in numpy for the agents `rows`: the leg switch of `BatchP2P.mission`, the same
+    statements in the same order (include/omgx.h OMGX_HAS_MISSION).  s_old [B, n_dim]: p[state0] of the previous update (where the
+    guess starts), state_now [B, n_dim]: where the vehicle is.  The coefficients are numpy's own linspace statement --
+    start + i * ((stop - start) / (L - 1)), the last one the goal itself."""
+    n = goals.shape[2]
+    for b in rows:
+        g, s = goals[b, leg[b]], np.array(s_old[b], dtype=float)
+        p[b, o_poseT:o_poseT + n] = g
+        x[b] = x_reset
+        step = (g - s) / (L - 1)
+        c = s[:, None] + np.arange(L)[None, :] * step[:, None]
+        c[:, L - 1] = g
+        x[b, o_spl:o_spl + n * L] = c.reshape(-1)
+        lam[b] = 0.0
+        p[b, o_state0:o_state0 + n] = state_now[b]
+        p[b, o_input0:o_input0 + n] = 0.0
+        p[b, o_t] = 0.0
+        clock[b] = 0
+        arrivals[b, leg[b]] = step_index
+        leg[b] += 1
 
 
 def quad_inputs_numpy(dd, ddd, g):
