@@ -271,7 +271,9 @@ int  omgx_batch_last_instance(const omgx_batch* b);
  * HBM slab (leaf panels by columns); 2 = + Jacobian values; 3 = + the per-row arrays (the O(n_var)
  * vectors, the matrix descriptors and a copy of the root block stay in LDS); 4 = compact KKT store and row arrays in
  * LDS, Jacobian values and row values in the slab; 5 = as 4 with the row values in LDS (4 and 5: templates on the wave
- * path, two agents per CU when the rest fits half a CU).  Every mode runs min(n_agents, n_slabs) persistent workgroups
+ * path only).  A template on the wave path gets the first of 0, 5, 4 whose LDS part fits half a CU -- two agents per CU then,
+ * workgroups of 256 threads: also in mode 0, which every small class gets -- and otherwise the first of 0, 5, 4 that fits a
+ * whole CU, one agent per CU with 512 threads (tests/workspace_cells.py has a class per cell).  Every mode runs min(n_agents, n_slabs) persistent workgroups
  * that take their agents from an atomic counter. */
 int  omgx_batch_workspace(const omgx_batch* b, int32_t* mode, int64_t* lds_bytes,
                           int64_t* hbm_bytes_per_slab, int32_t* n_slabs);

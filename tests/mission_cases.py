@@ -21,12 +21,13 @@ def mission_goals(m):
     return goals, (np.arange(m.B) % 4).astype(np.int32)
 
 
-def mission_batch(n, ops, options, stop_tol=STOP_TOL, warmup=WARMUP, mission=True, plant=None, **kw):
+def mission_batch(n, ops, options, stop_tol=STOP_TOL, warmup=WARMUP, mission=True, plant=None, build=None, **kw):
     """(batch, P): n agents of the config-2 workload, stop rule on, cold solve, `warmup` plain updates, then the mission.  plant: the
-    keyword arguments of `BatchP2P.plant`, called ahead of the cold solve."""
+    keyword arguments of `BatchP2P.plant`, called ahead of the cold solve.  build(n) -> (problem, P): another class than config 2
+    (tests/test_gpu_workspace_cells.py)."""
     from omgtools import workloads
     from omgtools.batch import BatchP2P
-    problem, P = workloads.holonomic_p2p(n)
+    problem, P = (build or workloads.holonomic_p2p)(n)
     m = BatchP2P(problem, P, ops=ops, options=options, **kw)
     if plant is not None:
         m.plant(**plant)

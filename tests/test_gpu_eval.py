@@ -21,12 +21,11 @@ def _build(name, n):
         be.create_nlp = saved
 
 
-@pytest.mark.parametrize('scenario', ['holonomic_p2p', 'quadrotor_p2p', 'holonomic3d_p2p'])
-def test_device_derivatives_match_the_oracle(scenario):
+def oracle_parity(problem, P, B, scenario, check=None):
+    """`omgx_batch_eval` at seeded random points of the class (problem, P) against the oracle's numpy restatement, to 1e-10; returns
+    what the finite-difference part of the test below goes on with (also called by tests/test_gpu_workspace_cells.py)."""
     from omgtools.backend import BatchSolver
     from oracle.nlp_numpy import NumpyNLP
-    B = 3
-    problem, P = _build(scenario, B)
     tpl = problem.father.template
     nlp = NumpyNLP(tpl)
     rng = np.random.default_rng(5)
@@ -37,6 +36,8 @@ def test_device_derivatives_match_the_oracle(scenario):
     lam = rng.normal(size=(B, tpl.n_con))
     solver = BatchSolver(tpl, B)
     try:
+        if check is not None:
+            check(solver)                                        # (the caller's look at the handle ahead of the launch)
         got = solver.eval(p, x, lam)
     finally:
         solver.close()
@@ -51,6 +52,15 @@ def test_device_derivatives_match_the_oracle(scenario):
         assert np.abs(got['jac'][b] - J).max() < 1e-10 * sj, (scenario, b, np.abs(got['jac'][b] - J).max())
         assert np.abs(got['hess'][b] - H).max() < 1e-10 * sh, (scenario, b, np.abs(got['hess'][b] - H).max())
         assert np.array_equal(got['hess'][b], got['hess'][b].T)
+    return tpl, rng, x, p, lam, got
+
+
+@pytest.mark.parametrize('scenario', ['holonomic_p2p', 'quadrotor_p2p', 'holonomic3d_p2p'])
+def test_device_derivatives_match_the_oracle(scenario):
+    from omgtools.backend import BatchSolver
+    B = 3
+    problem, P = _build(scenario, B)
+    tpl, rng, x, p, lam, got = oracle_parity(problem, P, B, scenario)
     # finite differences of the device's own g: the Jacobian is the derivative of what the kernel evaluates
     b, h = 0, 1e-6
     cols = rng.choice(tpl.n_var, size=min(B - 1, 2), replace=False)

@@ -28,23 +28,27 @@ def _close(mpc):
     mpc.close() if hasattr(mpc, 'parts') else mpc.solver.close()
 
 
-def _loop(B, n_streams, rule):
-    """Cold solve (no restart guesses: they are a feature of the full instance) + N_STEPS steps; the five arrays after every launch and
-    the instance every launch ran."""
+def _loop(B, n_streams, rule, build=None, n_steps=N_STEPS, check=None, **kw):
+    """Cold solve (no restart guesses: they are a feature of the full instance) + n_steps steps; the five arrays after every launch and
+    the instance every launch ran.  build(B) -> (problem, P): another class than config 2 (tests/test_gpu_workspace_cells.py); kw: of
+    the loop (`update_time`); check(solver): called with every handle ahead of its first launch."""
     import torch
     from omgtools import workloads
     from omgtools.batch import BatchP2P, StreamedP2P
-    problem, P = workloads.holonomic_p2p(B)
+    problem, P = (build or workloads.holonomic_p2p)(B)
     dev = torch.device('cuda', 0)
     opts = dict(tol=1e-3, max_iter=300)
-    mpc = BatchP2P(problem, P, ops='hip', device=dev, options=opts) if n_streams == 1 else \
-        StreamedP2P(problem, P, n_streams=n_streams, device=dev, options=opts)
+    mpc = BatchP2P(problem, P, ops='hip', device=dev, options=opts, **kw) if n_streams == 1 else \
+        StreamedP2P(problem, P, n_streams=n_streams, device=dev, options=opts, **kw)
     try:
+        if check is not None:
+            for m in _parts(mpc):
+                check(m.solver)
         if rule:
             mpc.stop_at_arrival(stop_tol=-1.0)
         log, inst, crossed = [], [], 0
         mpc.solve_cold(bends=())
-        for k in range(N_STEPS + 1):
+        for k in range(n_steps + 1):
             if k:
                 crossed += int(bool(mpc.step()))
             log.append(dict((key, mpc.host(key).copy()) for key in KEYS))

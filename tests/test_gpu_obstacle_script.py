@@ -21,26 +21,28 @@ def _drift(problem, P):
         P['p'][:, oa[0]:oa[1]] = rng.uniform(-0.01, 0.01, size=(len(P['p']), oa[1] - oa[0]))
 
 
-def _events(n, seed=3, t_max=1.2):
+def _events(n, seed=3, t_max=1.2, n_obst=3, t_cross=0.95):
     """Six random events per agent over the 12 updates (on and off the update grid, all three kinds, all three obstacles), one of
-    them moved into the knot-crossing update 0.9 -> 1.0."""
+    them moved into the knot-crossing update 0.9 -> 1.0.  (t_max, n_obst, t_cross: of another class than config 2.)"""
     from omgtools.batch import random_obstacle_script
-    ev = random_obstacle_script(n, 3, 2, 6, t_max, 0.03, seed=seed)
-    ev['time'][:, 3] = 0.95
+    ev = random_obstacle_script(n, n_obst, 2, 6, t_max, 0.03, seed=seed)
+    ev['time'][:, 3] = t_cross
     return ev
 
 
-def _mk(n, events=None, drift=False, cold=True, plant=False, cls=None, **kw):
+def _mk(n, events=None, drift=False, cold=True, plant=False, cls=None, build=None, max_updates=16, **kw):
+    """build(n) -> (problem, P): another class than config 2 (tests/test_gpu_workspace_cells.py)."""
     import torch
     from omgtools import workloads
     from omgtools.batch import BatchP2P, input_disturbance
-    problem, P = workloads.holonomic_p2p(n)
+    problem, P = (build or workloads.holonomic_p2p)(n)
     if drift:
         _drift(problem, P)
     m = (cls or BatchP2P)(problem, P, device=torch.device('cuda', 0), options=OPTS, **kw)
     if plant:
-        m.plant(sample_time=0.01, max_updates=16, disturbance=input_disturbance(n, 2, 16, 10, 1001, fc=0.1, stdev=0.02, seed=7))
-        m.record_signals(sample_time=0.01, max_updates=16)
+        m.plant(sample_time=0.01, max_updates=max_updates,
+                disturbance=input_disturbance(n, 2, max_updates, 10, 1001, fc=0.1, stdev=0.02, seed=7))
+        m.record_signals(sample_time=0.01, max_updates=max_updates)
     if events is not None:
         m.obstacle_script(events)
     if cold:

@@ -21,11 +21,12 @@ def _dist(n, max_updates, stdev=0.02, seed=7):
     return input_disturbance(n, 2, max_updates, 10, 1001, fc=0.1, stdev=stdev, seed=seed)
 
 
-def _mk(n, max_updates=16, dist='noise', mutate=None, stop=None, record=True, cold=True, plant=True, cls=None, **kw):
+def _mk(n, max_updates=16, dist='noise', mutate=None, stop=None, record=True, cold=True, plant=True, cls=None, build=None, **kw):
+    """build(n) -> (problem, P): another class than config 2 (tests/test_gpu_workspace_cells.py)."""
     import torch
     from omgtools import workloads
     from omgtools.batch import BatchP2P
-    problem, P = workloads.holonomic_p2p(n)
+    problem, P = (build or workloads.holonomic_p2p)(n)
     if mutate is not None:
         mutate(problem, P)
     m = (cls or BatchP2P)(problem, P, device=torch.device('cuda', 0), options=OPTS, **kw)
@@ -172,12 +173,12 @@ def test_feedback_identity_on_the_device():
 STOP_TOL, NEAR, MAX_STEPS = 1e-3, (0, 5, 10, 15), 60
 
 
-def _near_targets(problem, P):
+def _near_targets(problem, P, agents=NEAR):
     """poseT of four agents moved to 0.3 m from their start: they arrive within the run."""
     tpl = problem.father.template
     label = problem.vehicles[0].label
     s0, pT = (tpl.entry_range(label, nm, 'par')[0] for nm in ('state0', 'poseT'))
-    for b in NEAR:
+    for b in agents:
         d = P['p'][b, pT:pT + 2] - P['p'][b, s0:s0 + 2]
         P['p'][b, pT:pT + 2] = P['p'][b, s0:s0 + 2] + 0.3 * d / np.linalg.norm(d)
         L = len(problem.vehicles[0].basis)

@@ -8,16 +8,18 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _pair(n, mutate=None, **kw):
+def _pair(n, mutate=None, build=None, update_time=0.1, **kw):
+    """Two handles of the same batch behind their cold solves.  build(n) -> (problem, P): another class than config 2
+    (tests/test_gpu_workspace_cells.py)."""
     import torch
     from omgtools import workloads
     from omgtools.batch import BatchP2P
     out = []
     for _ in range(2):
-        problem, P = workloads.holonomic_p2p(n, **kw)
+        problem, P = (build or workloads.holonomic_p2p)(n, **kw)
         if mutate is not None:
             mutate(problem, P)
-        mpc = BatchP2P(problem, P, ops='hip', device=torch.device('cuda', 0), options=dict(tol=1e-3, max_iter=300))
+        mpc = BatchP2P(problem, P, ops='hip', device=torch.device('cuda', 0), options=dict(tol=1e-3, max_iter=300), update_time=update_time)
         mpc.solve_cold(bends=())
         out.append(mpc)
     return out
