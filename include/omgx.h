@@ -802,6 +802,72 @@ typedef struct omgx_mission_spec {
 int  omgx_batch_set_mission(omgx_batch* b, const omgx_mission_spec* sp);
 int  omgx_batch_mission_advance(omgx_batch* b, double* p, double* x, double* lam_g, int32_t step_index);
 
+/* (OMGX_HAS_FREE_T) Free end time: the step glue of `Point2point(..., freeT=True)` (`problems/point2point.py:269-369`).  The motion
+ * time T is a variable of the agent's own, x[o_T]: prediction, warm-start shift and the first stop clause read it per agent, so this
+ * glue is device code, not a host-side table as omgx_batch_shift.  The class's t is 0 throughout; there is no knot clock.
+ *
+ * The shift.  The reference's `shift_spline(coeffs, s, basis)` (`basics/spline_extra.py:88-99`) projects the piece of a spline on
+ * [s, 1] onto the basis with equidistant knots on that interval.  For a basis whose own knots are equidistant the new basis is the
+ * affine image of the old one, so per basis   c' = proj . y,   y_j = spline(s + (1 - s) fit_j)   with two constant tables: fit [n_fit]
+ * (points of [0, 1]) and proj [rows x n_fit] row-major (rows = n_knots - degree - 1 coefficients) -- e.g. a least-squares fit at
+ * Chebyshev points, or the reference's own collocation (`basics/spline.py:283-306`: its arg-max points mapped back, the inverse of
+ * its collocation matrix).  The caller owns that choice.
+ *
+ * omgx_batch_set_free_t uploads once, on the handle's stream: the plan (the rule above omgx_store_spec, without inv_T), o_T, the
+ * outputs of the prediction (n_out, p_off, p_t as omgx_batch_predict_ex), update_time (read by omgx_batch_free_t_append), the entry
+ * table n_ent x {offset, rows, cols, basis} -- a block of x, cols columns of rows coefficients each, column k at offset + k * rows,
+ * as omgx_batch_shift lays them out -- and per basis degree, knots, n_fit, fit, proj.  All pointers are host pointers, read during
+ * the call.  sp == NULL switches it off and frees the tables.  Limits, refused beyond with OMGX_E_INVALID before anything is
+ * launched or uploaded (omgx_last_error() names the entry and the field): 1 <= n_ent <= OMGX_FREE_T_MAX_ENT, 1 <= n_basis <=
+ * OMGX_FREE_T_MAX_BASIS, per basis 1 <= degree <= 5, 2 * degree + 2 <= n_knots <= 40, rows <= OMGX_FREE_T_MAX_ROWS, 1 <= n_fit <=
+ * OMGX_FREE_T_MAX_FIT; an entry's rows are those of its basis, cols >= 1, the block inside x; 0 <= o_T < n_var; update_time > 0.
+ *
+ * omgx_batch_free_t_advance: one launch on the handle's stream, one wave per agent; x, p, under_way are device pointers, under_way
+ * may be NULL (every agent).  Per agent with under_way[b] != 0, with T = x[o_T]:
+ *   1. not (T >= update_time) -- a NaN too --:  under_way[b] <- 0 (where given), nothing else is touched
+ *      (`FreeTPoint2point.stop_criterium`'s first clause, `point2point.py:348-352`);
+ *   2. prediction on the OLD plan and the OLD T:  p[p_off[o] + k] <- spline_k^(o)(update_time / T) / T^o  (o < n_out, p_off[o] >= 0;
+ *      the scale by o successive divisions),  p[p_t] <- 0 (p_t >= 0);
+ *   3. `init_step` (`point2point.py:354-368`):  T < 2 update_time:  dt = T - update_time, rem = T;  else  dt = update_time, rem = T -
+ *      update_time;  s = dt / rem;  every column of every entry  c' = proj . y,  y_j = the old column's spline at s + (1 - s) fit_j,
+ *      the products summed over j in ascending order, each product and each sum rounded on its own;  x[o_T] <- rem.
+ * The shift is in place: a column's old coefficients and its samples are staged in LDS before any of its coefficients is written,
+ * and the prediction is done before the shift.  s = 1 (T = 2 update_time exactly) is well defined: every sample is the terminal
+ * value.  lam_g, status and the agents with flag 0 are not touched.  The update_time of the call is the one read here.  The call
+ * does NOT carry a pending omgx_batch_order_by_iters (omgx_batch_predict_ex does): the solve that follows launches the ordering.
+ *
+ * omgx_batch_free_t_append: the travelled log for a per-agent horizon -- omgx_batch_signals_append's statement and routine with
+ * t_rel = 0, inv_T = 1 / T (T = x[o_T]) and n_b samples in place of n_samp:  n_b = sp->n_samp if T >= update_time (the free-T
+ * spec's);  n_b = floor(T / sample_time + 5e-7) if sample_time <= T < update_time (`Problem.simulate`'s shortened span and its
+ * int(round(., 6)));  T < sample_time, or no number: nothing is appended, column 0 included (`FreeTPoint2point.simulate` does nothing
+ * then).  So column c0 + i - 1 holds d^o/dt^o spline_k at u = i * (sample_time * inv_T), scaled by inv_T^o, and sample 0 (u = 0)
+ * goes ahead of the first append.  sp->inv_T and sp->p_t are ignored; the plan of sp is the one given to omgx_batch_set_free_t.
+ * Overflow and count rules are unchanged, omgx_batch_signals_reduce works on the result as it is: its motion time is then the
+ * reference's free-T objective, the elapsed time.  One launch on the handle's stream; x, under_way device pointers. */
+#define OMGX_HAS_FREE_T 1
+#define OMGX_FREE_T_MAX_ENT   32
+#define OMGX_FREE_T_MAX_BASIS 4
+#define OMGX_FREE_T_MAX_ROWS  64
+#define OMGX_FREE_T_MAX_FIT   256
+typedef struct omgx_free_t_basis {
+  int32_t degree, n_knots, n_fit;
+  const double* knots;      /* [n_knots] host */
+  const double* fit;        /* [n_fit] host */
+  const double* proj;       /* [n_knots - degree - 1][n_fit] host, row-major */
+} omgx_free_t_basis;
+typedef struct omgx_free_t_spec {
+  const double* knots;      /* [n_knots] host: the plan (the vehicle's splines) */
+  int32_t coeff_off, n_spl, degree, n_knots;
+  int32_t o_T;              /* index of T in x */
+  int32_t n_out; const int32_t* p_off; int32_t p_t;      /* as omgx_batch_predict_ex ([n_out] host; -1: skip) */
+  double  update_time;
+  int32_t n_ent; const int32_t* entries;                 /* [n_ent][4] host = {offset, rows, cols, basis} */
+  int32_t n_basis; const omgx_free_t_basis* basis;       /* [n_basis] host */
+} omgx_free_t_spec;
+int  omgx_batch_set_free_t(omgx_batch* b, const omgx_free_t_spec* sp);
+int  omgx_batch_free_t_advance(omgx_batch* b, double* x, double* p, double update_time, int32_t* under_way);
+int  omgx_batch_free_t_append(omgx_batch* b, const double* x, const int32_t* under_way, const omgx_signals_spec* sp);
+
 /* Same shift on any device-resident row-major array (stride doubles per row, n_rows rows):
  * used for the ADMM consensus state on a knot crossing (`problems/admm.py:477-491`).
  * The handle keeps the table sets it has seen on the device (16, found again by content): a loop that shifts with the

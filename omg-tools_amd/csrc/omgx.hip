@@ -138,7 +138,11 @@ struct omgx_batch {
   MissionArgs* d_mission = nullptr;         // ... its copy in device memory ...
   double* d_x_reset = nullptr;              // ... and the handle's copy of the reset row [n_var]
   bool mission_on = false;
-  StopArgs* d_stop = nullptr;      // omgx_batch_set_stop: device copy of the arguments
+  FreeTArgs free_t_host = {};               // omgx_batch_set_free_t: the free-end-time glue as its kernels read it ...
+  FreeTArgs* d_free_t = nullptr;            // ... its copy in device memory ...
+  DevBuf free_t_tab;                        // ... and the fit / proj tables of its bases behind it (freed when it is switched off)
+  bool free_t_on = false;
+  StopArgs* d_stop = nullptr;     // omgx_batch_set_stop: device copy of the arguments
   StopArgs stop_host = {};          // (and the host copy: omgx_batch_rollout hands it to its kernel inside RolloutArgs)
   bool stop_on = false;
   int last_instance = 0;            // solve-kernel instance of the last omgx_batch_solve launch: 0 full, 1 lean (omgx_batch_last_instance)
@@ -1869,6 +1873,113 @@ int omgx_batch_mission_advance(omgx_batch* b, double* p, double* x, double* lam_
   HIPCHK(hipSetDevice(b->device));
   hipLaunchKernelGGL(mission_advance_kernel, dim3((b->n_agents + 3) / 4), dim3(256), 0, b->stream, p, x, lam_g, b->dims.n_par, b->n_agents,
                      (const MissionArgs*)b->d_mission, b->stop_host, (const PlantBlock*)(b->plant_on ? b->d_plant : nullptr), step_index);
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
+int omgx_batch_set_free_t(omgx_batch* b, const omgx_free_t_spec* sp) {
+  if (!sp) {
+    if (!b) return bad("null handle");
+    b->free_t_on = false;
+    HIPCHK(hipSetDevice(b->device));
+    b->free_t_tab.reset();      // (waits for the launches that still read the tables)
+    return OMGX_OK;
+  }
+  // without a handle: the plan, the limits, the tables
+  if (!sp->p_off || !sp->entries || !sp->basis) return bad("set_free_t: null p_off / entries / basis");
+  TRY(check_plan("set_free_t", Plan{sp->coeff_off, sp->n_spl, sp->degree, sp->n_knots, 0.0, sp->knots}, 1, kAnySpl, false));
+  if (sp->n_out < 1 || sp->n_out > 4 || sp->n_out > sp->degree + 1) return bad("set_free_t: n_out = %d outside 1 .. min(4, degree + 1)", sp->n_out);
+  if (!(sp->update_time > 0.0)) return bad("set_free_t: update_time = %g must be positive", sp->update_time);
+  if (sp->o_T < 0) return bad("set_free_t: o_T = %d is negative", sp->o_T);
+  if (sp->n_ent < 1 || sp->n_ent > OMGX_FREE_T_MAX_ENT) return bad("set_free_t: n_ent = %d outside 1 .. %d", sp->n_ent, OMGX_FREE_T_MAX_ENT);
+  if (sp->n_basis < 1 || sp->n_basis > OMGX_FREE_T_MAX_BASIS) return bad("set_free_t: n_basis = %d outside 1 .. %d", sp->n_basis, OMGX_FREE_T_MAX_BASIS);
+  size_t tab_doubles = 0;
+  for (int i = 0; i < sp->n_basis; ++i) {
+    const omgx_free_t_basis& bs = sp->basis[i];
+    if (!bs.knots || !bs.fit || !bs.proj) return bad("set_free_t: basis[%d]: null knots / fit / proj", i);
+    if (bs.degree < 1 || bs.degree > 5) return bad("set_free_t: basis[%d]: degree = %d outside 1 .. 5", i, bs.degree);
+    if (bs.n_knots < 2 * bs.degree + 2 || bs.n_knots > 40) return bad("set_free_t: basis[%d]: n_knots = %d outside %d .. 40", i, bs.n_knots, 2 * bs.degree + 2);
+    if (bs.n_knots - bs.degree - 1 > OMGX_FREE_T_MAX_ROWS) return bad("set_free_t: basis[%d]: rows = %d outside 1 .. %d", i, bs.n_knots - bs.degree - 1, OMGX_FREE_T_MAX_ROWS);
+    if (bs.n_fit < 1 || bs.n_fit > OMGX_FREE_T_MAX_FIT) return bad("set_free_t: basis[%d]: n_fit = %d outside 1 .. %d", i, bs.n_fit, OMGX_FREE_T_MAX_FIT);
+    tab_doubles += (size_t)bs.n_fit * (size_t)(1 + bs.n_knots - bs.degree - 1);
+  }
+  for (int e = 0; e < sp->n_ent; ++e) {
+    const int32_t* en = sp->entries + 4 * e;
+    if (en[1] < 1 || en[1] > OMGX_FREE_T_MAX_ROWS) return bad("set_free_t: entries[%d]: rows = %d outside 1 .. %d", e, en[1], OMGX_FREE_T_MAX_ROWS);
+    if (en[3] < 0 || en[3] >= sp->n_basis) return bad("set_free_t: entries[%d]: basis = %d outside 0 .. %d", e, en[3], sp->n_basis - 1);
+    const omgx_free_t_basis& bs = sp->basis[en[3]];
+    if (en[1] != bs.n_knots - bs.degree - 1) return bad("set_free_t: entries[%d]: rows = %d, its basis has %d coefficients", e, en[1], bs.n_knots - bs.degree - 1);
+    if (en[2] < 1) return bad("set_free_t: entries[%d]: cols = %d must be positive", e, en[2]);
+    if (en[0] < 0) return bad("set_free_t: entries[%d]: offset = %d is negative", e, en[0]);
+  }
+  if (!b) return bad("null handle");
+  const omgx::Dims& d = b->dims;
+  FreeTArgs a = {};
+  const Plan pl{sp->coeff_off, sp->n_spl, sp->degree, sp->n_knots, 0.0, sp->knots};
+  TRY(check_predict_in_xp(b, "set_free_t", pl, sp->n_out, sp->p_off, sp->p_t, a.p_off));
+  if (sp->o_T >= d.n_var) return bad("set_free_t: o_T = %d outside x (n_var = %d)", sp->o_T, d.n_var);
+  for (int e = 0; e < sp->n_ent; ++e) {
+    const int32_t* en = sp->entries + 4 * e;
+    if (en[0] + (long long)en[1] * en[2] > d.n_var) return bad("set_free_t: entries[%d]: offset = %d, %d x %d coefficients outside x (n_var = %d)", e, en[0], en[1], en[2], d.n_var);
+    for (int q = 0; q < 4; ++q) a.ent[e][q] = en[q];
+  }
+  b->free_t_on = false;      // (a failed registration leaves it OFF)
+  HIPCHK(hipSetDevice(b->device));
+  HIPCHK(b->free_t_tab.alloc(sizeof(double) * tab_doubles));      // (frees the previous tables first: waits for the launches that read them)
+  std::vector<double> tab;
+  tab.reserve(tab_doubles);
+  a.coeff_off = pl.coeff_off; a.n_spl = pl.n_spl; a.degree = pl.degree; a.n_knots = pl.n_knots;
+  fill_knots(a.knots, pl.knots, pl.n_knots);
+  a.n_out = sp->n_out; a.p_t = sp->p_t; a.o_T = sp->o_T; a.n_ent = sp->n_ent; a.n_basis = sp->n_basis; a.update_time = sp->update_time;
+  for (int i = 0; i < sp->n_basis; ++i) {
+    const omgx_free_t_basis& bs = sp->basis[i];
+    FreeTBasis& o = a.basis[i];
+    o.degree = bs.degree; o.n_knots = bs.n_knots; o.n_fit = bs.n_fit; o.rows = bs.n_knots - bs.degree - 1;
+    fill_knots(o.knots, bs.knots, bs.n_knots);
+    o.fit = (const double*)b->free_t_tab.p + tab.size();
+    tab.insert(tab.end(), bs.fit, bs.fit + bs.n_fit);
+    o.proj = (const double*)b->free_t_tab.p + tab.size();
+    tab.insert(tab.end(), bs.proj, bs.proj + (size_t)o.rows * bs.n_fit);
+  }
+  // (a fresh allocation nothing reads yet; the copy is done when the call returns, so the host vector may go)
+  HIPCHK(hipMemcpy(b->free_t_tab.p, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+  b->free_t_host = a;
+  TRY(push_args(b, &b->d_free_t, b->free_t_host));
+  b->free_t_on = true;
+  return OMGX_OK;
+}
+
+int omgx_batch_free_t_advance(omgx_batch* b, double* x, double* p, double update_time, int32_t* under_way) {
+  if (!x || !p) return bad("free_t_advance: null x / p");
+  if (!(update_time > 0.0)) return bad("free_t_advance: update_time = %g must be positive", update_time);
+  if (!b) return bad("null handle");
+  if (!b->free_t_on || !b->d_free_t) return bad("free_t_advance: no free-end-time glue is set (omgx_batch_set_free_t)");
+  HIPCHK(hipSetDevice(b->device));
+  hipLaunchKernelGGL(free_t_advance_kernel, dim3(b->n_agents), dim3(64), 0, b->stream, x, b->dims.n_var, p, b->dims.n_par,
+                     (const FreeTArgs*)b->d_free_t, update_time, under_way);
+  HIPCHK(hipGetLastError());
+  return OMGX_OK;
+}
+
+int omgx_batch_free_t_append(omgx_batch* b, const double* x, const int32_t* under_way, const omgx_signals_spec* sp) {
+  if (!sp) return bad("null argument");
+  omgx_signals_spec s = *sp;
+  s.inv_T = 1.0; s.p_t = 0;      // (ignored by this entry: every agent has its own horizon, and t is 0)
+  SignalArgs sg;
+  TRY(check_signals_spec(&s));
+  if (!b) return bad("null handle");
+  if (!b->free_t_on) return bad("free_t_append: no free-end-time glue is set (omgx_batch_set_free_t)");
+  TRY(check_plan_in_x(b, "free_t_append", plan_of(s)));
+  if (!same_plan(s, b->free_t_host)) return bad("free_t_append: coeff_off / n_spl / degree / n_knots are not those given to omgx_batch_set_free_t");
+  if (!x) return bad("null argument");
+  put_plan(sg, plan_of(s));
+  sg.log = s.log; sg.count = s.count; sg.overflow = s.overflow;
+  sg.n_der = s.n_der; sg.n_samp = s.n_samp; sg.cap = s.cap; sg.p_t = 0; sg.sample_time = s.sample_time;
+  HIPCHK(hipSetDevice(b->device));
+  const size_t lds = sample_scratch_doubles(sg.n_spl, sg.degree, sg.n_knots, sg.n_der) * sizeof(double);
+  if (lds > 64 * 1024) { g_err = "signals: the per-agent scratch exceeds 64 KiB of LDS"; return OMGX_E_TOOLARGE; }
+  hipLaunchKernelGGL(free_t_append_kernel, dim3(b->n_agents), dim3(256), lds, b->stream, x, b->dims.n_var, under_way, sg, b->free_t_host.o_T,
+                     b->free_t_host.update_time);
   HIPCHK(hipGetLastError());
   return OMGX_OK;
 }

@@ -1533,6 +1533,115 @@ mission_advance_kernel(double* __restrict__ p, double* __restrict__ x, double* _
 }
 
 // ---------------------------------------------------------------------------
+// Free end time (omgx_batch_set_free_t; include/omgx.h OMGX_HAS_FREE_T states the semantics): the step glue of a batch whose motion
+// time T is a variable of every agent's own, x[o_T] -- the first stop clause, the prediction and the warm-start shift all read it, so
+// none of them can be a host-side table.  The shift of a column is  c' = proj . y,  y_j = the old spline at s + (1 - s) fit_j, with
+// the two constant tables of its basis; FreeTArgs lives in device memory (the handle's copy), fit / proj behind it.
+// ---------------------------------------------------------------------------
+struct FreeTBasis {
+  int degree, n_knots, n_fit, rows;
+  const double* fit;        // [n_fit]
+  const double* proj;       // [rows][n_fit]
+  KnotArg knots;
+};
+struct FreeTArgs {
+  KnotArg knots;                                    // the plan, as PredictArgs holds it
+  int coeff_off, n_spl, degree, n_knots, n_out, p_off[4], p_t;
+  int o_T, n_ent, n_basis;
+  double update_time;                               // (read by the append)
+  int ent[OMGX_FREE_T_MAX_ENT][4];                  // {offset, rows, cols, basis}
+  FreeTBasis basis[OMGX_FREE_T_MAX_BASIS];
+};
+
+// One wave per agent.  Lanes over (derivative order, spline) for the prediction; per column of an entry lanes over the old
+// coefficients (into LDS), then over the fit points (samples into LDS), then over the new coefficients, each a sum over the
+// samples in ascending order.  Nothing of a column is written before its samples are staged, nothing of x before the prediction
+// has read the old plan, and x[o_T] last.
+__global__ void __launch_bounds__(64)
+free_t_advance_kernel(double* __restrict__ x, int n_var, double* __restrict__ p, int n_par, const FreeTArgs* __restrict__ ftp,
+                      double update_time, int32_t* __restrict__ under_way) {
+#pragma clang fp contract(off)
+  __shared__ double kn[40];
+  __shared__ double c_old[OMGX_FREE_T_MAX_ROWS];
+  __shared__ double y[OMGX_FREE_T_MAX_FIT];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (under_way && under_way[b] == 0) return;
+  const FreeTArgs& ft = *ftp;
+  double* xb = x + (size_t)b * n_var;
+  double* pb = p + (size_t)b * n_par;
+  const double T = xb[ft.o_T];
+  // (one wave: every lane has its loads of the flag and of T behind it before lane 0 stores either)
+  __builtin_amdgcn_wave_barrier();
+  if (!(T >= update_time)) {
+    if (under_way && lane == 0) under_way[b] = 0;
+    return;
+  }
+  // prediction on the old plan and the old T
+  for (int i = lane; i < ft.n_knots; i += 64) kn[i] = ft.knots.k[i];
+  __syncthreads();
+  const double tau = update_time / T;
+  const int L = ft.n_knots - ft.degree - 1;
+  const int jt = span_of(kn, ft.degree, ft.n_knots, tau);
+  for (int e = lane; e < ft.n_out * ft.n_spl; e += 64) {
+    const int o = e / ft.n_spl, k = e - o * ft.n_spl;
+    if (ft.p_off[o] < 0) continue;
+    double v = spline_der_at(xb + ft.coeff_off + k * L, kn, ft.degree, jt, tau, o);
+    for (int q = 0; q < o; ++q) v = v / T;
+    pb[ft.p_off[o] + k] = v;
+  }
+  if (lane == 0 && ft.p_t >= 0) pb[ft.p_t] = 0.0;
+  // init_step: the plan re-expressed on what is left of it
+  double dt = update_time, rem = T - update_time;
+  if (T < 2.0 * update_time) { dt = T - update_time; rem = T; }
+  const double s = dt / rem, w = 1.0 - s;
+  for (int e = 0; e < ft.n_ent; ++e) {
+    const int off = ft.ent[e][0], rows = ft.ent[e][1], cols = ft.ent[e][2];
+    const FreeTBasis& bs = ft.basis[ft.ent[e][3]];
+    const int degree = bs.degree, n_knots = bs.n_knots, n_fit = bs.n_fit;
+    __syncthreads();      // (the samples of the previous entry, and the prediction, have read kn)
+    for (int i = lane; i < n_knots; i += 64) kn[i] = bs.knots.k[i];
+    for (int k = 0; k < cols; ++k) {
+      double* c = xb + off + k * rows;
+      __syncthreads();    // (the previous column's sums have read y; its samples c_old)
+      for (int i = lane; i < rows; i += 64) c_old[i] = c[i];
+      __syncthreads();
+      for (int j = lane; j < n_fit; j += 64) {
+        const double u = s + w * bs.fit[j];
+        y[j] = deboor_at(c_old, kn, degree, span_of(kn, degree, n_knots, u), u);
+      }
+      __syncthreads();
+      for (int r = lane; r < rows; r += 64) {
+        const double* pr = bs.proj + (size_t)r * n_fit;
+        double acc = 0.0;
+        for (int j = 0; j < n_fit; ++j) acc = acc + pr[j] * y[j];
+        c[r] = acc;
+      }
+    }
+  }
+  __syncthreads();
+  if (lane == 0) xb[ft.o_T] = rem;
+}
+
+// The travelled log for a per-agent horizon (omgx_batch_free_t_append): signals_append_agent with the agent's own inv_T = 1 / T,
+// t_rel = 0 and its own number of samples -- all of an update's, or what is left of the plan (`Problem.simulate`'s shortened span),
+// or none.  One workgroup per agent; T is the same in every thread, so every branch is the workgroup's.
+__global__ void __launch_bounds__(256)
+free_t_append_kernel(const double* __restrict__ x, int n_var, const int32_t* __restrict__ under_way, SignalArgs sg, int o_T, double update_time) {
+  extern __shared__ __align__(16) double lds[];
+  const int b = blockIdx.x;
+  if (under_way && under_way[b] == 0) return;
+  const double T = x[(size_t)b * n_var + o_T];
+  if (!(T >= sg.sample_time)) return;      // (a NaN too)
+  if (!(T >= update_time)) {
+    const int n_b = (int)floor(T / sg.sample_time + 5e-7);
+    sg.n_samp = n_b < sg.n_samp ? n_b : sg.n_samp;
+  }
+  if (sg.n_samp < 1) return;
+  sg.inv_T = 1.0 / T;
+  signals_append_agent(sg, b, x + (size_t)b * n_var + sg.coeff_off, 0.0, lds);
+}
+
+// ---------------------------------------------------------------------------
 // Rollout: K receding-horizon steps of every agent in ONE launch (omgx_batch_rollout).  Agents of a point-to-point batch
 // are independent, so nothing in the protocol asks for a barrier between the steps of different agents: a persistent
 // workgroup takes an agent and runs its whole loop -- ideal prediction from the current plan, obstacles advanced, the

@@ -242,6 +242,20 @@ class CMissionSpec(C.Structure):
                 ('coeff_off', C.c_int32), ('n_spl', C.c_int32), ('L', C.c_int32), ('n_steps', C.c_int32), ('step_index', C.c_int32)]
 
 
+class CFreeTBasis(C.Structure):
+    """include/omgx.h omgx_free_t_basis"""
+    _fields_ = [('degree', C.c_int32), ('n_knots', C.c_int32), ('n_fit', C.c_int32), ('knots', C.c_void_p), ('fit', C.c_void_p),
+                ('proj', C.c_void_p)]
+
+
+class CFreeTSpec(C.Structure):
+    """include/omgx.h omgx_free_t_spec"""
+    _fields_ = [('knots', C.c_void_p), ('coeff_off', C.c_int32), ('n_spl', C.c_int32), ('degree', C.c_int32), ('n_knots', C.c_int32),
+                ('o_T', C.c_int32), ('n_out', C.c_int32), ('p_off', C.c_void_p), ('p_t', C.c_int32), ('update_time', C.c_double),
+                ('n_ent', C.c_int32), ('entries', C.c_void_p), ('n_basis', C.c_int32), ('basis', C.c_void_p)]
+
+
+FREE_T_MAX_ENT, FREE_T_MAX_BASIS, FREE_T_MAX_ROWS, FREE_T_MAX_FIT = 32, 4, 64, 256      # (include/omgx.h OMGX_FREE_T_MAX_*)
 PREDICT_IDEAL, PREDICT_RK4 = 0, 1
 ONLY_FAILED = 8
 
@@ -383,6 +397,9 @@ PROTOTYPES = {
     'omgx_batch_set_obstacle_script': (C.c_int, [_H, C.POINTER(CObstacleScript), _P, _I]),
     'omgx_batch_set_mission': (C.c_int, [_H, C.POINTER(CMissionSpec)]),
     'omgx_batch_mission_advance': (C.c_int, [_H, _P, _P, _P, _I]),
+    'omgx_batch_set_free_t': (C.c_int, [_H, C.POINTER(CFreeTSpec)]),
+    'omgx_batch_free_t_advance': (C.c_int, [_H, _P, _P, _D, _P]),
+    'omgx_batch_free_t_append': (C.c_int, [_H, _P, _P, _SIG]),
     'omgx_shift_rows': (C.c_int, [_H, _P, _I, _I, _P, _P, _I, _P, _I]),
     'omgx_admm_center': (C.c_int, [_H, _LAY] + [_P] * 3),
     'omgx_admm_update': (C.c_int, [_H, _LAY] + [_P] * 4 + [_D] + [_P] * 4),
@@ -955,6 +972,49 @@ class BatchSolver(object):
             raise ValueError('p, x and lam_g must be device tensors')
         _check(self.lib, self.lib.omgx_batch_mission_advance(self._h, p.data_ptr(), x.data_ptr(), lam_g.data_ptr(), int(step_index)),
                'omgx_batch_mission_advance')
+
+    def set_free_t(self, spec=None):
+        """Register the free-end-time step glue with the handle (include/omgx.h omgx_batch_set_free_t; spec=None: off, the tables are
+        freed).  spec: dict with the plan (`coeff_off, n_spl, degree, knots`), `o_T`, `p_off`, `p_t`, `update_time`, `entries`
+        [n_ent, 4] = {offset, rows, cols, basis} and `bases`, a list of dicts `degree, knots, fit [n_fit], proj [rows, n_fit]`.
+        Host arrays, read during the call."""
+        if spec is None:
+            _check(self.lib, self.lib.omgx_batch_set_free_t(self._h, None), 'omgx_batch_set_free_t')
+            return
+        keep = [_host_knots(spec['knots']), np.ascontiguousarray(spec['p_off'], dtype=np.int32),
+                np.ascontiguousarray(spec['entries'], dtype=np.int32).reshape(-1, 4)]
+        bases = (CFreeTBasis * max(1, len(spec['bases'])))()
+        for i, bs in enumerate(spec['bases']):
+            kn, fit = _host_knots(bs['knots']), np.ascontiguousarray(bs['fit'], dtype=np.float64).reshape(-1)
+            proj = np.ascontiguousarray(bs['proj'], dtype=np.float64)
+            if proj.shape != (len(kn) - int(bs['degree']) - 1, len(fit)):
+                raise ValueError('set_free_t: bases[%d]: proj must be [n_knots - degree - 1, n_fit] = %s, got %s'
+                                 % (i, [len(kn) - int(bs['degree']) - 1, len(fit)], list(proj.shape)))
+            keep += [kn, fit, proj]
+            bases[i] = CFreeTBasis(int(bs['degree']), len(kn), len(fit), kn.ctypes.data, fit.ctypes.data, proj.ctypes.data)
+        sp = CFreeTSpec(keep[0].ctypes.data, int(spec['coeff_off']), int(spec['n_spl']), int(spec['degree']), len(keep[0]), int(spec['o_T']),
+                        len(keep[1]), keep[1].ctypes.data, int(spec['p_t']), float(spec['update_time']), len(keep[2]), keep[2].ctypes.data,
+                        len(spec['bases']), C.addressof(bases))
+        _check(self.lib, self.lib.omgx_batch_set_free_t(self._h, C.byref(sp)), 'omgx_batch_set_free_t')
+
+    def free_t_advance(self, x, p, update_time, under_way=None):
+        """The head of a free-end-time step, one launch on device tensors x [B, n_var], p [B, n_par] (include/omgx.h
+        omgx_batch_free_t_advance): per agent under way the stop clause T < update_time (clears `under_way`), the prediction on the
+        old plan and the old T, the plan re-expressed on what is left of it, T reduced."""
+        _need('x', x, (self._B, self.template.n_var), 'float64 device')
+        _need('p', p, (self._B, self.template.n_par), 'float64 device')
+        _need('under_way', under_way, (self._B,), 'int32 device', optional=True)
+        _check(self.lib, self.lib.omgx_batch_free_t_advance(self._h, x.data_ptr(), p.data_ptr(), float(update_time),
+                                                             under_way.data_ptr() if under_way is not None else None),
+               'omgx_batch_free_t_advance')
+
+    def free_t_append(self, x, log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, sample_time, under_way=None):
+        """One append of the travelled log with every agent's own horizon x[:, o_T] (include/omgx.h omgx_batch_free_t_append)."""
+        _need('x', x, (self._B, self.template.n_var), 'float64 device')
+        _need('under_way', under_way, (self._B,), 'int32 device', optional=True)
+        sp = self._signals_spec(log, count, overflow, coeff_off, n_spl, degree, knots, n_samp, 0, sample_time, 1.0)
+        _check(self.lib, self.lib.omgx_batch_free_t_append(self._h, x.data_ptr(), under_way.data_ptr() if under_way is not None else None,
+                                                            C.byref(sp)), 'omgx_batch_free_t_append')
 
     def set_plant(self, plant=None, log=None):
         """Every following `rollout` runs with the plant in the loop (include/omgx.h omgx_batch_set_plant; plant=None: off).  The

@@ -10,7 +10,7 @@ with a primal-dual warm start.
 Layout: `BatchP2P` states that protocol once -- tables and options from the template, `solve_cold`, `step`, `rollout`, the stop rule,
 the log -- and branches on no executor.  Where the [B, *] arrays live and who computes on them sits behind its hooks (`_allocate,
 _predict, _shift, _solve, _cold, _rollout, _norm, _stop_rule, _signals_alloc, _signals_fused, _signals_append_now,
-_signals_summary, _zeros, _plant_alloc, _plant_lag, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance, _mission_alloc, _mission_off, _mission_clock_max, _mission_run, _mission_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
+_signals_summary, _free_t_set, _free_t_advance, _zeros, _plant_alloc, _plant_lag, _plant_predict, _plant_simulate, _plant_rollout, _feedback_predict, _script_alloc, _script_advance, _mission_alloc, _mission_off, _mission_clock_max, _mission_run, _mission_advance`), written once per executor: `DeviceP2P` (`ops='hip'`, the only product path: launches of the library on torch tensors, torch
 being the allocator / stream only; no data leaves HBM between steps) and `HostP2P` (`ops=<a host solver object>`: the same
 statements in numpy, how the parity tests and the CPU baseline of bench.py replay the loop; this package never imports the
 oracle).  `BatchP2P(problem, P, ops=...)` hands out the executor `ops` names.  The clock of a step is `splines.step_clock`, the
@@ -27,6 +27,13 @@ with `time_constant` the vehicle applies them through the reference's first-orde
 or acceleration at given times (include/omgx.h OMGX_HAS_OBSTACLE_SCRIPT; `splines.advance_obstacles_scripted` in numpy).
 `BatchP2P.mission` gives every agent a list of goals: inside `rollout` an agent that arrives starts its next leg -- fresh guess, cold
 solve, a clock of its own -- instead of ending its loop (include/omgx.h OMGX_HAS_MISSION; `mission_next_leg_numpy` in numpy).
+
+A free-end-time problem (`Point2point(..., freeT=True)`: `FreeTPoint2point`, one Holonomic or Holonomic3D vehicle) runs another
+protocol, stated once in `BatchP2P._step_free_t`: T is a variable of every agent, there is no knot clock, and a step is advance (the stop
+clause T < update_time, the prediction on the old plan and the old T, the plan re-expressed on what is left of it, T reduced -- one
+launch, include/omgx.h OMGX_HAS_FREE_T; `free_t_advance_numpy` in numpy), obstacle motion, warm-started solve, and with `record_signals`
+the append on every agent's own horizon (`free_t_append_numpy`).  `horizon()` returns the current T per agent; `rollout`, `plant`,
+`feedback` and `mission` are refused on such a batch.
 """
 import math
 import os
@@ -103,6 +110,117 @@ def dual_shift_perm(father, extrapolate=True):
     return perm
 
 
+# -- free end time: the step glue of `Point2point(..., freeT=True)` (include/omgx.h OMGX_HAS_FREE_T has the statements) ----------------
+FREE_T_REFUSAL = ('%s: not with a free-end-time problem -- the rollout kernel and the plant entries carry one inv_T, '
+                  'every agent of this batch has a horizon of its own')
+
+
+def free_t_basis_tables(basis):
+    """(fit [n_fit], proj [len(basis), n_fit]) of a basis with equidistant knots: the reference's `shift_spline(coeffs, s, basis)`
+    (`basics/spline_extra.py:88-99`, here `splines.shift_spline_T`) projects the piece on [s, 1] onto the basis with equidistant
+    knots on that interval -- the affine image of `basis` itself, so  c' = proj . y,  y_j = spline(s + (1 - s) fit_j)  for every s.
+    Any other basis: NotImplementedError."""
+    k, d = np.asarray(basis.knots, dtype=float), basis.degree
+    inner = k[d:len(k) - d]
+    steps = np.diff(inner)
+    if (np.any(k[:d + 1] != k[0]) or np.any(k[len(k) - d - 1:] != k[-1]) or k[0] != 0.0 or k[-1] != 1.0 or len(steps) < 1
+            or np.any(steps <= 0.0) or np.abs(steps - steps.mean()).max() > 1e-9 * steps.mean()):
+        raise NotImplementedError('free end time: the shift of a basis whose knots are not equidistant on [0, 1] is not a constant table')
+    fit = basis.fit_points()
+    return fit, np.linalg.pinv(basis.eval_basis(fit))
+
+
+def spline_der_numpy(c, knots, degree, u, dord=0):
+    """dord-th derivative (spline-domain units) at the points u [n] of the splines with coefficients c [..., L]: [..., n].  The
+    device routines' statements (`spline_der_at`, `span_of`): the span k_j < u <= k_{j+1}, clamped into the basis, so a point a
+    rounding error outside [0, 1] is on the polynomial of the nearest span."""
+    c, kk, u = np.asarray(c, dtype=float), np.asarray(knots, dtype=float), np.atleast_1d(np.asarray(u, dtype=float))
+    dg, nk = int(degree), len(knots)
+    j = np.full(u.shape, dg, dtype=np.int64)
+    for q in range(dg + 1, nk - dg - 1):
+        j = np.where(kk[q] < u, q, j)
+    v = [c[..., j - dg + r] for r in range(dg + 1)]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        for o in range(1, dord + 1):
+            for r in range(dg, o - 1, -1):
+                i = j - dg + r
+                den = kk[i + dg - o + 1] - kk[i]
+                v[r] = np.where(den != 0.0, (dg - o + 1) * (v[r] - v[r - 1]) / den, 0.0)
+        g = dg - dord
+        for lev in range(1, g + 1):
+            for r in range(dg, dord + lev - 1, -1):
+                i = j - dg + r
+                den = kk[i + g - lev + 1] - kk[i]
+                a = np.where(den != 0.0, (u - kk[i]) / den, 0.0)
+                v[r] = (1.0 - a) * v[r - 1] + a * v[r]
+    return v[dg]
+
+
+def free_t_advance_numpy(x, p, under_way, update_time, ft):
+    """`omgx_batch_free_t_advance` in numpy, in place on x [B, n_var], p [B, n_par] and under_way [B] (or None: every agent).  ft: the
+    tables of `BatchP2P` for a free-end-time problem -- `o_T`, the plan `coeff_off, n_spl, degree, knots`, `p_off`, `p_t`, `entries`
+    [(offset, rows, cols, basis)], `bases` [dict(degree, knots, fit, proj)].  The resample-and-project form, so s = 1 is defined."""
+    ut, o_T = float(update_time), ft['o_T']
+    n_spl, L = ft['n_spl'], len(ft['knots']) - ft['degree'] - 1
+    for b in range(x.shape[0]):
+        if under_way is not None and not under_way[b]:
+            continue
+        T = float(x[b, o_T])
+        if not T >= ut:
+            if under_way is not None:
+                under_way[b] = 0
+            continue
+        c = x[b, ft['coeff_off']:ft['coeff_off'] + n_spl * L].reshape(n_spl, L)
+        for o, off in enumerate(ft['p_off']):
+            if off < 0:
+                continue
+            v = spline_der_numpy(c, ft['knots'], ft['degree'], [ut / T], o)[:, 0]
+            for _ in range(o):
+                v = v / T
+            p[b, off:off + n_spl] = v
+        if ft['p_t'] >= 0:
+            p[b, ft['p_t']] = 0.0
+        dt, rem = (T - ut, T) if T < 2.0 * ut else (ut, T - ut)
+        s = dt / rem
+        for off, rows, cols, ib in ft['entries']:
+            bs = ft['bases'][ib]
+            y = spline_der_numpy(x[b, off:off + rows * cols].reshape(cols, rows), bs['knots'], bs['degree'], s + (1.0 - s) * bs['fit'])
+            acc = np.zeros((cols, rows))
+            for j in range(len(bs['fit'])):             # (ascending, every product and sum rounded on its own)
+                acc = acc + bs['proj'][None, :, j] * y[:, j, None]
+            x[b, off:off + rows * cols] = acc.reshape(-1)
+        x[b, o_T] = rem
+
+
+def free_t_append_numpy(x, under_way, log, count, overflow, ft, n_samp, sample_time):
+    """`omgx_batch_free_t_append` in numpy, in place on log [B, n_der, n_spl, cap], count [B], overflow [B] (or None)."""
+    ut, st, o_T = float(ft['update_time']), float(sample_time), ft['o_T']
+    n_der, n_spl, cap = log.shape[1], ft['n_spl'], log.shape[3]
+    L = len(ft['knots']) - ft['degree'] - 1
+    for b in range(x.shape[0]):
+        if under_way is not None and not under_way[b]:
+            continue
+        T = float(x[b, o_T])
+        if not T >= st:
+            continue
+        n_b = int(n_samp) if T >= ut else min(int(n_samp), int(math.floor(T / st + 5e-7)))
+        if n_b < 1:
+            continue
+        inv_T = 1.0 / T
+        cnt = int(count[b])
+        first = 0 if cnt == 0 else 1
+        n_col = n_b + 1 - first
+        if cnt < 0 or cnt + n_col > cap:
+            if overflow is not None:
+                overflow[b] = 1
+            continue
+        u = np.arange(first, n_b + 1) * (st * inv_T)
+        c = x[b, ft['coeff_off']:ft['coeff_off'] + n_spl * L].reshape(n_spl, L)
+        for o in range(n_der):
+            log[b, o, :, cnt:cnt + n_col] = spline_der_numpy(c, ft['knots'], ft['degree'], u, o) * inv_T ** o
+        count[b] = cnt + n_col
+
+
 class BatchP2P(object):
     """The protocol; the module docstring has the layout."""
 
@@ -132,8 +250,12 @@ class BatchP2P(object):
         veh = problem.vehicles[0]
         self.veh, self.basis = veh, veh.basis
         self.L, self.n_dim, self.n_spl = len(veh.basis), veh.n_dim, veh.n_spl
-        self.T = float(problem.options['horizon_time'])
-        self.knot_time = float(problem.knot_time)
+        # free end time (`Point2point(..., freeT=True)`): T is a variable of every agent, there is no knot clock
+        self._ft = None
+        if (problem.label, 'T') in tpl.var_layout:
+            self._free_t_tables(problem, cross_options)
+        self.T = None if self._ft is not None else float(problem.options['horizon_time'])
+        self.knot_time = None if self._ft is not None else float(problem.knot_time)
         self.update_time = float(update_time)
         self.B = P['p'].shape[0]
         self.o_spl = tpl.entry_range(veh.label, 'splines_seg0', 'var')[0]
@@ -154,14 +276,14 @@ class BatchP2P(object):
         # (a problem loaded from a bundle, `omgtools.workloads`, brings the multiplier map of a knot crossing with it)
         self.perm = father.dual_perm if hasattr(father, 'dual_perm') else dual_shift_perm(father)
         ents, mats, off = [], [], 0
-        for label, name, spl in father.shifted_entries(every_spline=shift_every_spline):
+        for label, name, spl in (father.shifted_entries(every_spline=shift_every_spline) if self._ft is None else ()):
             lo, rows, cols = tpl.var_layout[(label, name)]
             Tm = shiftoverknot_T(spl['basis'])
             ents.append([lo, rows, cols, off])
             mats.append(Tm.reshape(-1))
             off += Tm.size
-        self.shift_entries = np.array(ents, dtype=np.int32)
-        self.shift_mats = np.concatenate(mats)
+        self.shift_entries = np.array(ents, dtype=np.int32).reshape(-1, 4)
+        self.shift_mats = np.concatenate(mats) if mats else np.zeros(0)
         self._shift_dense = [(e, m.reshape(e[1], e[1])) for e, m in zip(ents, mats)]
         self.time = 0.0
         self.under_way, self.stop_tol = None, 1e-3        # (stop_at_arrival)
@@ -183,6 +305,43 @@ class BatchP2P(object):
         self.max_iter_step = int(max_iter_step) if max_iter_step else self.max_iter_cold
         self.straggler_first = bool(straggler_first)
         self._allocate(P, ops, device)
+        if self._ft is not None:
+            self._ft.update(coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree, knots=np.asarray(self.basis.knots, dtype=float),
+                            p_off=list(self.p_offs), p_t=self.o_t, update_time=self.update_time)
+            self._free_t_set()
+
+    def _free_t_tables(self, problem, cross_options):
+        """The tables of a free-end-time batch (`self._ft`): where T sits in x, and per entry of `father.shifted_entries()` -- the
+        entries `FreeTPoint2point.init_step` re-expresses -- its block of x and the (fit, proj) tables of its basis."""
+        father, tpl = problem.father, problem.father.template
+        if hasattr(father, 'dual_perm') or not hasattr(problem, 'init_step'):
+            raise NotImplementedError('BatchP2P: a free-end-time problem loaded from a bundle carries no bases for its shift; build it through the front end')
+        if cross_options:
+            raise ValueError('BatchP2P: cross_options belong to a knot crossing; a free-end-time problem has no knot clock')
+        lay, label = tpl.par_layout, problem.vehicles[0].label
+        if any((label, nm) not in lay for nm in ('state0', 'input0', 'poseT')):
+            raise NotImplementedError('BatchP2P: free end time is carried for the point-mass classes (state0 / input0 / poseT: Holonomic, Holonomic3D)')
+        from .backend import FREE_T_MAX_BASIS, FREE_T_MAX_ENT, FREE_T_MAX_FIT, FREE_T_MAX_ROWS
+        bases, index, entries = [], {}, []
+        for lbl, name, spl in father.shifted_entries():
+            basis = spl['basis']
+            if basis not in index:
+                fit, proj = free_t_basis_tables(basis)
+                index[basis] = len(bases)
+                bases.append(dict(degree=basis.degree, knots=np.asarray(basis.knots, dtype=float), fit=fit, proj=np.ascontiguousarray(proj)))
+            lo, rows, cols = tpl.var_layout[(lbl, name)]
+            entries.append((int(lo), int(rows), int(cols), index[basis]))
+        if (len(entries) > FREE_T_MAX_ENT or len(bases) > FREE_T_MAX_BASIS or any(len(bs['fit']) > FREE_T_MAX_FIT for bs in bases)
+                or any(e[1] > FREE_T_MAX_ROWS for e in entries)):
+            raise NotImplementedError('BatchP2P: the free-end-time shift tables exceed the limits of omgx_batch_set_free_t (include/omgx.h)')
+        self._ft = dict(o_T=tpl.entry_range(problem.label, 'T', 'var')[0], entries=entries, bases=bases)
+
+    def horizon(self):
+        """[B]: the current motion time T of every agent of a free-end-time batch (a copy of x[:, o_T])."""
+        if self._ft is None:
+            raise RuntimeError('horizon(): the horizon of a fixed-T batch is `self.T`')
+        o = self._ft['o_T']
+        return self.x[:, o].clone() if hasattr(self.x, 'clone') else self.x[:, o].copy()
 
     # -- solves ------------------------------------------------------------------------
     def solve_cold(self, bends=(1.0, -1.0, 2.5, -2.5), fused=True):
@@ -196,12 +355,13 @@ class BatchP2P(object):
         # the log (record_signals) takes the cold plan ONCE, after the last restart pass: the log inside the solve stays off during
         # the cold solve (an agent that a restart solves again must not be logged twice) and one stand-alone append follows
         log = self._sig is not None and self._pl is None      # (with the plant in the loop the fused log is off anyway: its simulate writes the log)
-        if log:
+        fused_log = log and self._ft is None                  # (free end time: the append is a launch of its own behind every solve)
+        if fused_log:
             self._signals_fused(False)
         try:
             n_restarts = self._cold(bends, fused)
         finally:
-            if log:
+            if fused_log:
                 self._signals_fused(True)
         if log:
             self._signals_append_now()
@@ -228,6 +388,10 @@ class BatchP2P(object):
         if self._ms is not None:
             raise RuntimeError('step(): a mission is on -- its agents run on clocks of their own and a solve launch has one option set and '
                                'one clock: step with rollout(1)')
+        if self._ft is not None:
+            if states is not None or inputs is not None or fresh is not None or enforce:
+                raise NotImplementedError(FREE_T_REFUSAL % 'step(states=...)')
+            return self._step_free_t(events, before_solve)
         if states is None:
             if inputs is not None or fresh is not None or enforce:
                 raise ValueError('step: inputs / fresh / enforce go with states')
@@ -265,6 +429,23 @@ class BatchP2P(object):
             self._plant_simulate()                          # (4) the vehicle travels the update
         return crossed
 
+    def _step_free_t(self, events, before_solve):
+        """`step` of a free-end-time batch (`FreeTPoint2point`: `stop_criterium`, `init_step`, `Vehicle.predict`, solve, `simulate`):
+        (1) advance -- per agent under way the stop clause T < update_time, the prediction on the old plan and the old T, the plan
+        re-expressed on what is left of it, T reduced (include/omgx.h omgx_batch_free_t_advance); (2) obstacle motion, t = 0 in this
+        class; (3) warm-started solve, with the arrival test of `stop_at_arrival` inside it; (4) with `record_signals` the append on
+        every agent's own horizon.  `time` advances by `update_time`; nothing crosses a knot."""
+        t_now = self.time + self.update_time
+        self._free_t_advance()
+        self._advance_obstacles(self.time, t_now)
+        self.time = t_now
+        if before_solve is not None:
+            before_solve(self)
+        self._solve(True, events)
+        if self._sig is not None:
+            self._signals_append_now()
+        return False
+
     def rollout(self, n_steps, iters_log=None, status_log=None):
         """`n_steps` receding-horizon steps of every agent in ONE launch (`omgx_batch_rollout`): per agent the statements of `step` --
         prediction, obstacles, knot-crossing shift, warm-started solve -- in the same order with the same numbers, without the barrier
@@ -273,6 +454,8 @@ class BatchP2P(object):
         travelled state, input disturbance, stop test on the travelled state: a disturbance study of a whole fleet in one launch.  A
         deployment that feeds states measured outside back steps with `step` (`feedback`, `step(states=...)`): a rollout takes none.
         Returns the number of knot crossings."""
+        if self._ft is not None:
+            raise NotImplementedError(FREE_T_REFUSAL % 'rollout')
         if self._pl is not None and self._pl.get('model') == 'quadrotor':
             raise NotImplementedError("rollout: the Quadrotor's plant runs per step only (`step`): the rollout kernel has no instance for it")
         if self._ms is not None:
@@ -309,6 +492,8 @@ class BatchP2P(object):
         if not on:
             self._ms = None
             return self._mission_off()
+        if self._ft is not None:
+            raise NotImplementedError(FREE_T_REFUSAL % 'mission')
         if self.under_way is None:
             raise RuntimeError('mission(): call stop_at_arrival() first -- arriving is that rule')
         if getattr(self, 'pool', None) is not None:
@@ -556,7 +741,8 @@ class BatchP2P(object):
         self._sig = sig
         if self._pl is not None:
             return                                          # (the plant's simulate writes the log: the fused spline log stays off)
-        self._signals_fused(True)
+        if self._ft is None:                                # (free end time: the append is a launch of its own behind every solve, `step`)
+            self._signals_fused(True)
         if self._plan_ready:
             self._signals_append_now()
 
@@ -655,6 +841,8 @@ class BatchP2P(object):
                 if self._sig is not None:
                     self._signals_fused(True)
             return
+        if self._ft is not None:
+            raise NotImplementedError(FREE_T_REFUSAL % 'plant')
         if model is not None:
             self._quad_model('plant', model)
             return self._plant_quadrotor(sample_time, max_updates, disturbance, time_constant, gravity)
@@ -728,6 +916,8 @@ class BatchP2P(object):
         if not on:
             self._fb = None
             return
+        if self._ft is not None:
+            raise NotImplementedError(FREE_T_REFUSAL % 'feedback')
         lay, label = self.tpl.par_layout, self.veh.label
         cls_name = type(self.veh).__name__ if hasattr(self.veh, 'ode') else label
         if model is not None:
@@ -799,7 +989,8 @@ class DeviceP2P(BatchP2P):
         self.solver = BatchSolver(self.tpl, self.B, device=self.dev.index or 0, options=self.opts)
         self.solver.set_stream(torch.cuda.current_stream().cuda_stream)
         # the plan as every glue entry of the library takes it (include/omgx.h, above omgx_store_spec): built once
-        self._plan = dict(coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree, knots=self.basis.knots, inv_T=1.0 / self.T)
+        self._plan = dict(coeff_off=self.o_spl, n_spl=self.n_spl, degree=self.basis.degree, knots=self.basis.knots,
+                          inv_T=1.0 / self.T if self.T else 1.0)      # (free end time: every agent's own, read from x)
         self.p = torch.as_tensor(np.ascontiguousarray(P['p']), **f64)
         self.x = torch.as_tensor(np.ascontiguousarray(P['x0']), **f64)
         self.x_new = torch.empty_like(self.x)
@@ -967,9 +1158,20 @@ class DeviceP2P(BatchP2P):
         g = self._sig
         self.solver.set_signals(g['log'], g['count'], g['overflow'], **self._signals_args())
 
+    def _free_t_set(self):
+        """The free-end-time tables, registered with the handle once (include/omgx.h omgx_batch_set_free_t)."""
+        self.solver.set_free_t(self._ft)
+
+    def _free_t_advance(self):
+        self.solver.free_t_advance(self.x, self.p, self.update_time, under_way=self.under_way)
+
     def _signals_append_now(self):
         """One append of the current plan (x at the time p[:, t]) outside a solve: the stand-alone kernel."""
         g = self._sig
+        if self._ft is not None:                            # (every agent on its own horizon: omgx_batch_free_t_append)
+            a = self._signals_args()
+            return self.solver.free_t_append(self.x, g['log'], g['count'], g['overflow'], under_way=self.under_way,
+                                             **dict((k, a[k]) for k in ('coeff_off', 'n_spl', 'degree', 'knots', 'n_samp', 'sample_time')))
         self.solver.signals_append(self.x, self.p, g['log'], g['count'], g['overflow'], under_way=self.under_way, **self._signals_args())
 
     def _zeros(self, shape):
@@ -1078,6 +1280,8 @@ class HostP2P(BatchP2P):
             return BatchP2P.step(self, events, before_solve, states, inputs, fresh, enforce)
         if states is not None or inputs is not None or fresh is not None or enforce:
             raise NotImplementedError('step(states=...): not with a host pool (its workers run the step glue themselves)')
+        if self._ft is not None:
+            raise NotImplementedError('step: a free-end-time batch does not run on a host pool (its workers carry the fixed-T step glue)')
         t_now, tau, t_rel, crossed = step_clock(self.time, self.update_time, self.knot_time, self.T)
         self.time = t_now
         self._solve(True, step_desc=self._pool_step(tau, t_rel, crossed), extra=self.cross_options if crossed else None)
@@ -1167,7 +1371,16 @@ class HostP2P(BatchP2P):
         """The append at the end of `_solve`, on or off."""
         self._log_in_solve = bool(on)
 
+    def _free_t_set(self):
+        self._log_in_solve = False               # (the append is a step of its own behind every solve: `_step_free_t`)
+
+    def _free_t_advance(self):
+        free_t_advance_numpy(self.x, self.p, self.under_way, self.update_time, self._ft)
+
     def _signals_append_now(self):
+        if self._ft is not None:
+            g = self._sig
+            return free_t_append_numpy(self.x, self.under_way, g['log'], g['count'], g['overflow'], self._ft, g['n_samp'], g['sample_time'])
         self._signals_append_host(self.under_way)
 
     def _signals_append_host(self, under_way):
@@ -1734,6 +1947,12 @@ class StreamedP2P(object):
             if key != 'time':
                 out[key] = self.torch.cat([q[key] for q in parts])
         return out
+
+    def horizon(self):
+        """`BatchP2P.horizon` of the whole batch."""
+        out = self._each(lambda m: m.horizon())
+        self.join()
+        return self.torch.cat(out)
 
     def summary(self):
         out = self._each(lambda m: m.summary())

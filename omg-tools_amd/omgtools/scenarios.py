@@ -42,6 +42,42 @@ def holonomic_p2p(n_agents, knot_intervals=11, n_obs=3, seed=20240807 + 2,
                                           len(vehicle.basis), n_agents, seed, horizon_time, gap=gap)
 
 
+def holonomic_free_t_p2p(n_agents, knot_intervals=10, seed=20240807 + 7):
+    """Batch of independent free-end-time Holonomic problems (`Point2point(..., freeT=True)`, the reference's time-optimal mode):
+    start near [-1.5, -1.5], goal near [2, 2], both jittered per agent by U(+-0.2), a standing circle (0.4 at [0.2, -0.4]) and a
+    circle (0.3 from [1.0, 1.2]) that moves at [-0.1, 0.05]; the motion time T is a variable, 10 s in the first guess; the vehicle's
+    splines start on the straight line (the statement of `workloads.fill_holonomic_p2p`), the hyperplanes at zero."""
+    vehicle = Holonomic()
+    vehicle.define_knots(knot_intervals=knot_intervals)
+    vehicle.set_initial_conditions([-1.5, -1.5])
+    vehicle.set_terminal_conditions([2., 2.])
+    environment = Environment(room={'shape': Square(5.)})
+    environment.add_obstacle(Obstacle({'position': [0.2, -0.4]}, shape=Circle(0.4)))
+    environment.add_obstacle(Obstacle({'position': [1.0, 1.2], 'velocity': [-0.1, 0.05]}, shape=Circle(0.3)))
+    problem = Point2point(vehicle, environment, options={'verbose': 0}, freeT=True)
+    problem.init()
+    tpl = problem.father.template
+    obstacles = _obstacle_facts(environment)
+    P = {'p': np.zeros((n_agents, tpl.n_par)), 'x0': np.zeros((n_agents, tpl.n_var))}
+    rng = np.random.default_rng(seed)
+    lo, hi = tpl.entry_range(vehicle.label, 'splines_seg0', 'var')
+    o_T = tpl.entry_range(problem.label, 'T', 'var')[0]
+    L = len(vehicle.basis)
+    for b in range(n_agents):
+        start = np.array([-1.5, -1.5]) + rng.uniform(-0.2, 0.2, size=2)
+        goal = np.array([2., 2.]) + rng.uniform(-0.2, 0.2, size=2)
+        wl._set(tpl, P['p'], b, vehicle.label, 'state0', start)
+        wl._set(tpl, P['p'], b, vehicle.label, 'poseT', goal)
+        for o in obstacles:
+            wl._set(tpl, P['p'], b, o['label'], 'x', o['position'])
+            wl._set(tpl, P['p'], b, o['label'], 'v', o['velocity'])
+            wl._set(tpl, P['p'], b, o['label'], 'checkpoints', np.asarray(o['checkpoints']).reshape(-1))
+            wl._set(tpl, P['p'], b, o['label'], 'rad', o['rad'])
+        P['x0'][b, lo:hi] = np.c_[np.linspace(start[0], goal[0], L), np.linspace(start[1], goal[1], L)].reshape(-1, order='F')
+        P['x0'][b, o_T] = 10.
+    return problem, P
+
+
 def quadrotor_p2p(n_agents, knot_intervals=13, n_obs=5, seed=20240807 + 3, horizon_time=5.,
                   options=None):
     """Config 3: batch of independent 2-D Quadrotor point-to-point problems (flat outputs y, z of
