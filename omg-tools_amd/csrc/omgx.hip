@@ -1,5 +1,7 @@
-// omgx.hip -- libomgx.so: the omgx_batch handle and the C ABI (include/omgx.h).  Host code only: the gfx950 kernels, their
-// argument structs and the selectors of their template instances are in omgx_kernels.h.
+// omgx.hip -- the host unit of libomgx.so: the omgx_batch handle and the C ABI (include/omgx.h), and the glue kernels it launches
+// by name (omgx_kernels.h).  It instantiates no ipm_solve / ipm_prepare / ipm_eval / ipm_rollout kernel: those are compiled in the
+// instance units (omgx_inst_*.hip) and reach this file only as the pointers the selectors of omgx_device.h return, so an edit
+// here recompiles this unit and none of theirs.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <cmath>
@@ -47,16 +49,36 @@ constexpr int kLdsHalf = kLdsLimit / 2 - 512;      // two workgroups per CU (the
 
 }  // namespace
 
-// The kernel instances of a handle's template class, resolved once per handle (omgx_batch_create) through the selectors of omgx_kernels.h:
-// the one place where a workspace mode maps to a template instance.  refine / lean / rollout / rollout_plant are null where the class has no
-// such instance (the general instance, classes off the wave path, the spill modes).
+// The solve kernel of a class: the general instance carries everything; otherwise the refinement and the lean launches have
+// instances of their own on the wave path (modes 0 / 4 / 5), and a class without the one asked for gets its full instance.
+static ipm_kernel_t ipm_kernel_for(int mode, int wave_ok, int general, int refine = 0, int lean = 0) {
+  if (general || mode == omgx::WS_ROOT_HBM) return solve_general_kernel(mode, wave_ok);
+  ipm_kernel_t k = nullptr;
+  if (wave_ok && refine) k = solve_refine_kernel(mode);
+  else if (wave_ok && lean) k = solve_lean_kernel(mode);
+  if (!k && (wave_ok || mode != omgx::WS_LDS)) k = solve_wave_kernel(mode);      // (mode 0 holds classes off the wave path too)
+  return k ? k : solve_blocked_kernel(mode);
+}
+// (the classes of the wave path without quartic terms / cos / sin atoms: the receding-horizon classes that fit LDS)
+static ipm_rollout_t rollout_kernel_for(int mode, int wave_ok, int general, int plant = 0, int script = 0, int mission = 0) {
+  if (!wave_ok || general) return nullptr;
+  switch (mode) {
+    case omgx::WS_LDS: return rollout_kernel_of<omgx::WS_LDS>(plant, script, mission);
+    case omgx::WS_JAC_ONLY: return rollout_kernel_of<omgx::WS_JAC_ONLY>(plant, script, mission);
+    case omgx::WS_JAC_HV: return rollout_kernel_of<omgx::WS_JAC_HV>(plant, script, mission);
+    default: return nullptr;
+  }
+}
+
+// The kernel instances of a handle's template class, resolved once per handle (omgx_batch_create) through the selectors above and
+// those of the instance units (omgx_device.h).  refine / lean / rollout[][] are null where the class has no such instance (the
+// general instance, classes off the wave path, the spill modes).
+enum { RO_PLAIN = 0, RO_SCRIPT = 1, RO_MISSION = 2, RO_FEATURES = 3 };      // (omgx_batch_set_obstacle_script, omgx_batch_set_mission: never both)
 struct Instances {
   ipm_kernel_t full = nullptr, refine = nullptr, lean = nullptr;
   ipm_eval_kernel_t eval = nullptr;
-  ipm_rollout_t rollout = nullptr, rollout_plant = nullptr;      // (rollout_plant: the instance with the plant in the loop, omgx_batch_set_plant)
-  ipm_rollout_t rollout_script = nullptr, rollout_plant_script = nullptr;      // (the two with an obstacle script, omgx_batch_set_obstacle_script)
-  ipm_rollout_t rollout_mission = nullptr, rollout_plant_mission = nullptr;      // (the two with a mission, omgx_batch_set_mission)
-  decltype(&ipm_prepare_kernel<true>) prepare = nullptr;
+  ipm_rollout_t rollout[2][RO_FEATURES] = {};      // [plant in the loop (omgx_batch_set_plant)][feature]
+  ipm_prepare_kernel_t prepare = nullptr;
 };
 static Instances instances_for(int mode, int wave_ok, int general) {
   Instances in;
@@ -65,13 +87,9 @@ static Instances instances_for(int mode, int wave_ok, int general) {
   if (refine != in.full) in.refine = refine;      // (a class without the instance gets the full one back)
   if (lean != in.full) in.lean = lean;
   in.eval = ipm_eval_kernel_for(mode, wave_ok, general);
-  in.rollout = rollout_kernel_for(mode, wave_ok, general);
-  in.rollout_plant = rollout_kernel_for(mode, wave_ok, general, 1);
-  in.rollout_script = rollout_kernel_for(mode, wave_ok, general, 0, 1);
-  in.rollout_plant_script = rollout_kernel_for(mode, wave_ok, general, 1, 1);
-  in.rollout_mission = rollout_kernel_for(mode, wave_ok, general, 0, 0, 1);
-  in.rollout_plant_mission = rollout_kernel_for(mode, wave_ok, general, 1, 0, 1);
-  in.prepare = general ? ipm_prepare_kernel<true> : ipm_prepare_kernel<false>;
+  for (int plant = 0; plant < 2; ++plant)
+    for (int f = 0; f < RO_FEATURES; ++f) in.rollout[plant][f] = rollout_kernel_for(mode, wave_ok, general, plant, f == RO_SCRIPT, f == RO_MISSION);
+  in.prepare = ipm_prepare_kernel_for(general);
   return in;
 }
 
@@ -728,14 +746,11 @@ int create_batch(omgx_batch* b, const omgx_template* tpl) {
   static int lds_reserved[4 * omgx::WS_MODES] = {0};
   int& reserved = lds_reserved[4 * b->ws_mode + (d.wave_ok ? 1 : 0) + (d.general ? 2 : 0)];
   if ((int)b->lds_bytes > reserved) reserved = (int)b->lds_bytes;
-  const void* const launched[9] = {(const void*)b->inst.full, (const void*)b->inst.refine, (const void*)b->inst.lean, (const void*)b->inst.rollout,
-                                   (const void*)b->inst.rollout_plant, (const void*)b->inst.rollout_script, (const void*)b->inst.rollout_plant_script,
-                                   (const void*)b->inst.rollout_mission, (const void*)b->inst.rollout_plant_mission};
-  for (const void* k : launched)
-    if (k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, reserved) != hipSuccess) {
-      g_err = (k != (const void*)b->inst.full && k != (const void*)b->inst.refine && k != (const void*)b->inst.lean) ? "cannot reserve dynamic LDS for ipm_rollout_kernel" : "cannot reserve dynamic LDS for ipm_solve_kernel";
-      return OMGX_E_HIP;
-    }
+  for (const ipm_kernel_t k : {b->inst.full, b->inst.refine, b->inst.lean})
+    if (k && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, reserved) != hipSuccess) { g_err = "cannot reserve dynamic LDS for ipm_solve_kernel"; return OMGX_E_HIP; }
+  for (const auto& row : b->inst.rollout)
+    for (const ipm_rollout_t k : row)
+      if (k && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, reserved) != hipSuccess) { g_err = "cannot reserve dynamic LDS for ipm_rollout_kernel"; return OMGX_E_HIP; }
   {
     // Persistent workgroups, as many as fit the chip at once (one or two per CU), that take their agents from an atomic
     // counter -- in every mode: solves differ by a factor of several in their iteration counts.  The workgroups of the
@@ -1511,9 +1526,9 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
     return bad("rollout: bad specification (n_steps, tau / t_rel / crossed, at most 8 obstacles, shift tables with their multiplier map)");
   if (!b) return bad("null handle");
   const omgx::Dims& d = b->dims;
-  if (!b->inst.rollout || b->n_range > 0 || !b->d_next)
+  if (!b->inst.rollout[0][RO_PLAIN] || b->n_range > 0 || !b->d_next)
     return bad("rollout: not available for this template class (spill modes, general instance, two-sided rows): step with omgx_batch_solve");
-  if (b->plant_on && (!b->inst.rollout_plant || !b->d_plant))
+  if (b->plant_on && (!b->inst.rollout[1][RO_PLAIN] || !b->d_plant))
     return bad("rollout: a plant is set (omgx_batch_set_plant) but this template class has no plant instance of the rollout kernel: step with "
                "omgx_batch_plant_predict / omgx_batch_solve / omgx_batch_plant_simulate");
   if (b->plant_on && (!same_plan(*sp, b->plant_host.pl) || sp->p_t != b->plant_host.pl.p_t))
@@ -1522,7 +1537,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
     return bad("rollout: the plant's sample_time = %g is not the one the lag was set with (omgx_batch_set_plant_lag: %g)", b->plant_host.pl.sample_time, b->lag_sample_time);
   if (b->script_on) {
     const ObstacleScriptArgs& sc = b->script_host;
-    if (!(b->plant_on ? b->inst.rollout_plant_script : b->inst.rollout_script) || !b->d_script)
+    if (!b->inst.rollout[b->plant_on ? 1 : 0][RO_SCRIPT] || !b->d_script)
       return bad("rollout: an obstacle script is set (omgx_batch_set_obstacle_script) but this template class has no script instance of the "
                  "rollout kernel: step with omgx_batch_obstacles_advance / omgx_batch_solve");
     if (sc.n_t < sp->n_steps + 1)
@@ -1537,7 +1552,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   if (b->mission_on) {
     const MissionArgs& ms = b->mission_host;
     if (b->script_on) return bad("rollout: a mission and an obstacle script are both set: the rollout kernel has no instance for the two");
-    if (!(b->plant_on ? b->inst.rollout_plant_mission : b->inst.rollout_mission) || !b->d_mission)
+    if (!b->inst.rollout[b->plant_on ? 1 : 0][RO_MISSION] || !b->d_mission)
       return bad("rollout: a mission is set (omgx_batch_set_mission) but this template class has no mission instance of the rollout kernel");
     if (!b->stop_on) return bad("rollout: a mission is set but the stop rule is off (omgx_batch_set_stop): arriving is that rule");
     if (ms.K > sp->n_steps) return bad("rollout: the mission runs %d steps per agent but the step table holds %d", ms.K, sp->n_steps);
@@ -1603,8 +1618,7 @@ int omgx_batch_rollout(omgx_batch* b, const omgx_rollout_spec* sp, double* p, do
   a.plant = b->plant_on ? b->d_plant : nullptr;
   a.script = b->script_on ? b->d_script : nullptr;
   a.mission = b->mission_on ? b->d_mission : nullptr;
-  const ipm_rollout_t kern = b->mission_on ? (b->plant_on ? b->inst.rollout_plant_mission : b->inst.rollout_mission) : b->script_on ? (b->plant_on ? b->inst.rollout_plant_script : b->inst.rollout_script)
-                                          : (b->plant_on ? b->inst.rollout_plant : b->inst.rollout);
+  const ipm_rollout_t kern = b->inst.rollout[b->plant_on ? 1 : 0][b->mission_on ? RO_MISSION : b->script_on ? RO_SCRIPT : RO_PLAIN];
   // Two small copies per call (one call is n_steps steps of the whole batch), ORDERED ON THE HANDLE'S STREAM: the persistent
   // kernel of a previous rollout reads these tables for its whole run, and on a non-blocking caller stream a null-stream
   // hipMemcpy would overwrite them under it (pageable sources: staged before the calls return, executed in stream order).

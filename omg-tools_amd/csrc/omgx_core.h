@@ -1,7 +1,7 @@
 // omgx_core.h -- per-agent interior-point solve, written once for two targets:
 //
 //   * hipcc --offload-arch=gfx950: one 256-thread workgroup per agent, all
-//     state in LDS (omgx_kernels.hip: ipm_solve_kernel);
+//     state in LDS (omgx_solve_kernels.h: ipm_solve_kernel);
 //   * g++ -DOMGX_HOST_PORT: the same statements executed by one host thread
 //     (oracle/port/omgx_port.cpp) -- used ONLY as the timed CPU baseline and as
 //     a debugging aid; the product library never contains or calls it.

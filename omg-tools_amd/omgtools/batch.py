@@ -1705,7 +1705,7 @@ class HostP2P(BatchP2P):
 
 def mission_next_leg_numpy(rows, goals, leg, clock, arrivals, p, x, lam, s_old, state_now, step_index, x_reset, o_spl, L, o_state0, o_input0,
                            o_poseT, o_t):
-    """`mission_next_leg_agent` (csrc/omgx_kernels.h) in numpy for the agents `rows`: the leg switch of `BatchP2P.mission`, the same
+    """`mission_next_leg_agent` (csrc/omgx_device.h) in numpy for the agents `rows`: the leg switch of `BatchP2P.mission`, the same
     statements in the same order (include/omgx.h OMGX_HAS_MISSION).  s_old [B, n_dim]: p[state0] of the previous update (where the
     guess starts), state_now [B, n_dim]: where the vehicle is.  The coefficients are numpy's own linspace statement --
     start + i * ((stop - start) / (L - 1)), the last one the goal itself."""
@@ -1729,7 +1729,7 @@ def mission_next_leg_numpy(rows, goals, leg, clock, arrivals, p, x, lam, s_old, 
 
 def quad_inputs_numpy(dd, ddd, g):
     """The Quadrotor's inputs (u1, u2) [2, ...] from the plan's second and third time derivatives dd, ddd [2, ...]: the statements of
-    `quad_inputs` (csrc/omgx_kernels.h), which are `vehicles/quadrotor.py:136-139`."""
+    `quad_inputs` (csrc/omgx_device.h), which are `vehicles/quadrotor.py:136-139`."""
     n2 = (dd[1] + g) * (dd[1] + g) + dd[0] * dd[0]
     return np.array([np.sqrt(n2), (ddd[0] * (dd[1] + g) - dd[0] * ddd[1]) / n2])
 
@@ -1741,7 +1741,7 @@ def quad_ode_numpy(s, u1, u2, g):
 
 def quad_rk4_numpy(s0, a, h, g):
     """State samples 0 .. n [5, n + 1] of the Quadrotor from s0 [5] under the linearly interpolated input samples a [2, n + 1]: classical
-    Runge-Kutta per sample interval, the statements of `quad_rk4_step` (csrc/omgx_kernels.h) in the same order."""
+    Runge-Kutta per sample interval, the statements of `quad_rk4_step` (csrc/omgx_device.h) in the same order."""
     n = a.shape[1] - 1
     out = np.empty((5, n + 1))
     s = np.array(s0, dtype=float)

@@ -18,7 +18,7 @@ Derived atoms (division of parameter polynomials, B-spline basis functions
 evaluated at a parameter-dependent point — the numeric twin of `evalspline`
 with a symbolic argument, `basics/spline_extra.py:28-55`) are recorded as a
 small straight-line program that the device evaluates per agent
-(csrc/omgx_kernels.hip, `eval_atoms`).
+(csrc/omgx_core.h, `eval_params`).
 """
 import numpy as np
 

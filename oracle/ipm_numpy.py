@@ -1,7 +1,7 @@
 """ORACLE (test infrastructure, never shipped or measured as product).
 
 Dense numpy statement of the primal-dual interior-point iteration that the HIP
-kernel (omg-tools_amd/csrc/omgx_kernels.hip, `ipm_solve_kernel`) runs per agent.
+kernel (omg-tools_amd/csrc/omgx_solve_kernels.h, `ipm_solve_kernel`) runs per agent.
 It replaces -- it does not restate -- IPOPT, which is the third-party solver
 the reference calls at `problems/problem.py:113` through CasADi
 (`basics/optilayer.py:60`; casadi>=3.1.1.post3, `setup.py:29`, not vendored and

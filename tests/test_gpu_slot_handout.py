@@ -1,4 +1,4 @@
-"""The slot queue of the persistent kernels (`next_slot` of ipm_solve_kernel / ipm_rollout_kernel, omg-tools_amd/csrc/omgx_kernels.h).
+"""The slot queue of the persistent kernels (`next_slot` of ipm_solve_kernel / ipm_rollout_kernel, omg-tools_amd/csrc/omgx_device.h `queue_leave`).
 
 A handle with more agents than resident workgroups hands its launch slots out through an atomic counter that the workgroup leaving
 last resets for the next launch; a handle whose grid covers its batch gets no counter at all.  Which workgroup solves an agent

@@ -4,7 +4,7 @@ tests/test_gpu_workspace_cells.py).
 A template class on the wave path gets its workspace mode when the handle is created (`plan_for_mode`, omgx.hip): 0 (everything in
 LDS), 5 or 4 (the compact store with Jacobian values in a slab: include/omgx.h), tried in this order, first for two agents per CU --
 workgroups of 256 threads, the LDS part within `kLdsHalf` = 160 KiB / 2 - 512 B -- then for one agent per CU, 512 threads.  Every
-(mode, per CU) cell has kernel instances of its own (`ipm_kernel_for`, `rollout_kernel_for`, omgx_kernels.h): full / lean / refine
+(mode, per CU) cell has kernel instances of its own (the selectors of omgx_device.h, the units omgx_inst_*.hip): full / lean / refine
 solve, six rollout instances, eval.  The headline fleet (`workloads.holonomic_p2p`, k11 / 3 obstacles) sits in ONE cell, mode 5 with
 two per CU; the classes below are what a user gets with other knot counts and obstacle numbers.
 
