@@ -496,6 +496,7 @@ enum { PH_JAC = 0, PH_RESID, PH_ASSEMBLE, PH_FACTOR, PH_SOLVE, PH_STEP, PH_LINES
        PH_F_PARK, PH_F_SWEEP, PH_F_SCALE, PH_A_TCOL, PH_A_HESS, PH_P_LOAD, PH_P_DIV, PH_P_BSPL, PH_P_SLOTS,
        PH_WG_HEAD, PH_WG_TAIL,      // outside PH_TOTAL: kernel entry (or the workgroup's previous solve) to the start of a solve; its last solve to its exit
        PH_F_SCHUR_MFMA, PH_F_SCHUR_SUB,      // PH_F_SCHUR split by wave 0's clock: forming the tiles of S_l on the matrix pipe; subtracting them from the root (with its barriers)
+       PH_K_PRELOAD,      // wave 1's clock: loading the operands of its leaf's substitutions while wave 0 has the root (kkt_root_solve_wave)
        PH_COUNT };
 #if defined(OMGX_PROFILE) && !defined(OMGX_HOST_PORT)
 #define OMGX_TIC() long long tic_ = (c.sync(), clock64())
@@ -1653,8 +1654,156 @@ OMGX_FN void kkt_schur_wave(const C& c, const Dims& d, const Kkt& K, Work& w, [[
   }
 }
 
+// One bit from any wave to every wave: a slot of the reduction scratch per wave and the barrier the caller needs anyway, instead
+// of a reduction of doubles (c.rmax: a DPP ladder in every wave, two barriers).  `flag`: any lane of the wave may raise it.  A
+// caller that goes on to write c.red without another barrier in between has to put one there (the readers of this exchange).
 template <class C>
-OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w) {
+OMGX_FN int wave_flags_any(const C& c, int flag) {
+  const int mine = __builtin_amdgcn_ballot_w64(flag != 0) != 0 ? 1 : 0;
+  if (c.lane() == 0) c.red[c.wave()] = mine ? 1.0 : 0.0;
+  c.sync();
+  int any = 0;
+  for (int i = 0; i < c.nwaves(); ++i) any |= c.red[i] != 0.0 ? 1 : 0;
+  return __builtin_amdgcn_readfirstlane(any);
+}
+
+// A banded leaf's share of the solve, in two parts.  load(): what does not depend on the root -- the carried right-hand side
+// L^{-1} r_l, the inverse pivot, and column `lane` of L' scaled by it (wave_bwd_load: 36 or 40 registers of doubles) -- and may
+// therefore run as soon as the leaf factors are final; finish(): the gather of the root solution from `sol`, the chain over the
+// coupling rows, the backward chain, the store.  The statements and their order are those the solve always had, whoever calls
+// the two parts when: the same bits.
+// (The coupling rows Wt[a * ld] stay in the store.  Held in registers as well -- 2 x 30 more -- the lean headline instance
+// spills 71 vector registers, 288 B of scratch for 64; held instead of the L' column they keep 48 B and measure 1.9 % below
+// this form on the bench, which is 0.7 % below the kernel as it was before this routine: profiles/solve_handoff_ab.txt.)
+struct LeafSolveOps {
+  double lt[OMGX_WAVE_COLS], acc0, dl;
+  WPanel P;
+  int nc, dv, cpl;
+  bool small;
+  template <class C>
+  OMGX_FN void load(const C& c, const Work& w, const BMat& M, int koff) {
+    const int lane = c.lane();
+    P = wpanel_uniform(wpanel_leaf(M));
+    nc = P.nreg + 1 - P.n;                               // (wave-uniform values: scalar loop bounds)
+    dv = __builtin_amdgcn_readfirstlane(M.dinv); cpl = M.cpl;
+    const int j = lane < P.n ? lane : 0;
+    acc0 = w.kkt[P.wbase + j + nc * P.ld];               // L^{-1} r_l
+    dl = w.dinv[dv + j];
+    // (the leaf instance that factorised it, kkt_factor_wave: 36 positions instead of 40 where the leaf has no more)
+    small = wave_leaf_small(P.n, P.bw);
+    if (small) wave_bwd_load<OMGX_LEAF_COLS_SMALL, true>(koff, P, dl, lt);
+    else wave_bwd_load<OMGX_WAVE_COLS, true>(koff, P, dl, lt);
+  }
+  template <class C>
+  OMGX_FN void finish(const C& c, const Dims& d, const Kkt& K, const Work& w, double* xg, double* sol) const {
+    const int lane = c.lane();
+    if (lane < nc) xg[lane] = sol[d.root_off + leaf_cpl_at(d, K, w, cpl, lane)];
+    wave_fence();
+    const double* Wt = w.kkt + P.wbase + (lane < P.n ? lane : 0);
+    double acc = acc0;
+#pragma unroll 4
+    for (int a = 0; a < nc; ++a) acc = fma(-Wt[a * P.ld], xg[a], acc);
+    const double x = small ? wave_bwd_chain<OMGX_LEAF_COLS_SMALL>(P.n, lt, acc * dl) : wave_bwd_chain<OMGX_WAVE_COLS>(P.n, lt, acc * dl);
+    if (lane < P.n) sol[dv + lane] = x;
+    wave_fence();
+  }
+};
+
+// The root block and everything behind it: wave 0 factorises the root (its Schur complements are in) and, the inertia being
+// right, substitutes it backwards at once -- the right-hand side rode through wave_ldl --; meanwhile every other wave loads
+// the operands of its first banded leaf (LeafSolveOps::load).  One barrier publishes the root solution and the inertia flag
+// (a slot of the reduction scratch) together.  Wrong inertia: 2 is returned, nothing was stored by wave_ldl and `sol` is
+// untouched -- it still holds the phase-I column the next assembly of this iteration reads.  Right inertia: no assembly of
+// this iteration can follow any more (ipm_iterate leaves its factorisation loop on 0), the leaf waves gather, run their two
+// chains and store: `sol` holds the Newton step on return, 0.
+// Who substitutes which leaf: leaf l goes to wave (l + 1) % nw -- wave 0 has the root and comes last --, and under the tile
+// rule (Dims::schur_tiles) the diagonal leaf, which has nothing to preload, to wave 0.  Only the substitution rotates: the
+// factorisation keeps l % nw.  A wave's later leaves (more leaves than waves) and wave 0's go through the same statements
+// behind the barrier.  Every wave passes the same barriers: one, a second one on either way out.
+template <class C>
+OMGX_FN int kkt_root_solve_wave(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
+  const BMat* Ms = (const BMat*)w.col;
+  const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
+  const int koff = (int)(w.kkt - omgx_lds);            // the out-of-line wave routines address the LDS by offset
+  OMGX_TIC();
+  [[maybe_unused]] long long tr_ = 0;                  // (thread 0's clock behind the root factorisation)
+  const int diag = (d.schur_tiles > 0 && d.schur_tiles < d.n_leaf) ? d.schur_tiles : -1;      // (tile rule: the last leaf)
+  const int n_rr = diag >= 0 ? diag : d.n_leaf;        // leaves dealt round-robin
+  const int l_done = 1 << 20;
+  double* xg = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1) + wave * 64;      // gathered root solution of this wave's leaf
+  int l = wave ? wave - 1 : nw - 1;
+  LeafSolveOps Q;
+  const bool pre = wave != 0 && l < n_rr && __builtin_amdgcn_readfirstlane(Ms[l < n_rr ? l : 0].bw) >= 0;
+  if (wave == 0) {
+    const WPanel P = wpanel_root(Ms[d.n_leaf], d.n_root);
+#ifdef OMGX_PROFILE
+    const long long tr0_ = clock64();
+#endif
+    // (The root on the four waves of the workgroup -- root_ldl_4w, omgx_wave.h: the same bits, 30.2 k -> 22.1 k cycles alone on a CU --
+    // was measured twice and not adopted.  Round 6, for every iteration, one launch per step: f_root drops by 3.4 k only while the
+    // agent that shares the CU loses what the three parked waves left it, 342 k -> 349 k cycles per solve
+    // (profiles/r06_micro_root_ldl.txt).  With this routine, out of line and for iterations >= 1 only -- the solves a launch of the
+    // per-step path waits for --, the leaf waves preloading behind it: +0.7 % on the default bench line against a spread of 3.6 % of
+    // the parent's own runs, lean scratch 64 -> 80 B: taken out again (profiles/solve_handoff_ab.txt section 9).)
+    const int badr = wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, false, 1>(koff, P);
+#ifdef OMGX_PROFILE
+    tr_ = clock64();
+    if (c.tid() == 0) c.prof[PH_F_SWEEP] += tr_ - tr0_;      // raw root time
+#endif
+    if (!badr) {
+      wave_fence();
+      const double dl = wave_dinv<false>(w.kkt, P);
+      const double y = w.kkt[wcarried<false>(P, P.n) + (lane < P.n ? lane : 0)];           // L^{-1} r: the carried vector row
+      const double x = wave_bwd<OMGX_WAVE_COLS, false>(koff, P, dl, y * dl);
+      if (lane < P.n) sol[d.root_off + lane] = x;
+    }
+    if (lane == 0) c.red[0] = badr ? 1.0 : 0.0;
+  } else if (pre) {
+#ifdef OMGX_PROFILE
+    const long long tp0_ = clock64();
+#endif
+    Q.load(c, w, Ms[l], koff);
+#ifdef OMGX_PROFILE
+    if (c.tid() == 64) c.prof[PH_K_PRELOAD] += clock64() - tp0_;      // the preload as wave 1 sees it
+#endif
+  }
+  c.sync();
+  const int badr = __builtin_amdgcn_readfirstlane(c.red[0] != 0.0 ? 1 : 0);
+#ifdef OMGX_PROFILE
+  // f_root: up to the end of wave 0's factorisation; k_root: its substitution and the barrier
+  { const long long now_ = clock64(); if (c.tid() == 0) { c.prof[PH_F_ROOT] += tr_ - tic_; c.prof[PH_K_ROOT] += now_ - tr_; } tic_ = now_; }
+#endif
+  if (badr) { c.sync(); return 2; }                  // 2: the leaves are fine, the root has the wrong inertia  (the barrier: c.red is free again)
+  bool have = pre;                                   // (the operands of leaf l are in Q)
+  for (;;) {                                         // the preloaded leaf, a wave's later leaves, and wave 0's
+    if (wave == 0 && diag >= 0 && l >= n_rr && l < l_done) l = diag;
+    if (!(l < d.n_leaf && (l < n_rr || wave == 0))) break;
+    if (__builtin_amdgcn_readfirstlane(Ms[l].bw) >= 0) {
+      if (!have) Q.load(c, w, Ms[l], koff);
+      have = false;
+      Q.finish(c, d, K, w, xg, sol);
+    } else {
+      // sparse diagonal leaf: x_j = (r_j - sum_s v_s x_r[p_s] - v_t x_t) / d_j
+      const DiagLeaf L = diag_leaf(Ms[l]);
+      const int j = lane < L.n ? lane : 0;
+      const double* A = w.kkt + L.base + j;
+      double acc = A[(2 + L.S) * L.n] - A[(1 + L.S) * L.n] * sol[d.root_off + d.n_root - 1];
+      for (int s = 0; s < L.S; ++s) {
+        const int ps = diag_leaf_pos(d, K, w, L, s, j);
+        acc = fma(-A[(1 + s) * L.n], sol[d.root_off + (ps < 0 ? 0 : ps)] * (ps < 0 ? 0.0 : 1.0), acc);
+      }
+      if (lane < L.n) sol[L.dinv + lane] = acc * w.dinv[L.dinv + j];
+    }
+    l = l == diag ? l_done : l + nw;
+  }
+  c.sync();
+  OMGX_TOC(PH_K_BWD);                                  // what is left behind the root: gather, two chains, store
+  return 0;
+}
+
+// Leaves, Schur complements, root -- and, the inertia being right, the Newton step in `sol` (kkt_root_solve_wave).
+template <class C>
+OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
   const BMat* Ms = (const BMat*)w.col;
   const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
   const int koff = (int)(w.kkt - omgx_lds);            // the out-of-line wave routines address the LDS by offset
@@ -1684,7 +1833,7 @@ OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w) {
 #ifdef OMGX_PROFILE
   if (c.tid() == 0) { c.prof[PH_F_SCALE] += clock64() - tw0_; c.prof[PH_F_PARK] += 1; }      // raw leaf time of wave 0, number of factorisations
 #endif
-  if (c.rmax(badl ? 1.0 : 0.0) > 0.0) return 1;       // (two barriers: the panels and inverse pivots are visible)
+  if (wave_flags_any(c, badl)) { c.sync(); return 1; }       // (its barrier: the panels and inverse pivots are visible)
   OMGX_TOC(PH_F_LEAF);
   [[maybe_unused]] long long ts0_ = 0, tm_ = 0;      // (wave 0's own clock: start of the Schur phase, cycles up to the end of its MFMA loops)
 #ifdef OMGX_PROFILE
@@ -1696,93 +1845,7 @@ OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w) {
   // (the split of f_schur by wave 0's clock: up to the end of its MFMA loops, and the rest -- subtraction and barriers)
   if (c.tid() == 0) { c.prof[PH_F_SCHUR_MFMA] += tm_; c.prof[PH_F_SCHUR_SUB] += tic_ - ts0_ - tm_; }
 #endif
-  // (Round 6 measured the root on the four waves of the workgroup -- root_ldl_4w, omgx_wave.h: the same bits, 30.2 k -> 22.1 k cycles alone
-  // on a CU -- and did not adopt it: inside the solve kernel f_root drops by 3.4 k only while the phases of the agent that shares the CU
-  // lose what the three parked waves used to leave it, 342 k -> 349 k cycles per solve: profiles/r06_micro_root_ldl.txt)
-  int badr = 0;
-  if (wave == 0) {
-    const WPanel P = wpanel_root(Ms[d.n_leaf], d.n_root);
-#ifdef OMGX_PROFILE
-    const long long tr0_ = clock64();
-#endif
-    badr = wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, false, 1>(koff, P);
-#ifdef OMGX_PROFILE
-    if (c.tid() == 0) c.prof[PH_F_SWEEP] += clock64() - tr0_;      // raw root time
-#endif
-  }
-  const int bad = c.rmax(badr ? 1.0 : 0.0) > 0.0 ? 2 : 0;       // 2: the leaves are fine, the root has the wrong inertia
-  OMGX_TOC(PH_F_ROOT);
-  return bad;
-}
-
-// Root block alone once more (its diagonal was changed in place): wave_ldl stores nothing when a pivot has the
-// wrong sign, so after a failed attempt the store still holds the root as the Schur complements left it and
-// the leaf factors stay valid.
-template <class C>
-OMGX_FN int kkt_refactor_root_wave(const C& c, const Dims& d, const Kkt& K, Work& w) {
-  const BMat* Ms = (const BMat*)w.col;
-  const int koff = (int)(w.kkt - omgx_lds);
-  OMGX_TIC();
-  int badr = 0;
-  if (c.wave() == 0) badr = wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, false, 1>(koff, wpanel_root(Ms[d.n_leaf], d.n_root));
-  const int bad = c.rmax(badr ? 1.0 : 0.0) > 0.0 ? 2 : 0;
-  OMGX_TOC(PH_F_ROOT);
-  return bad;
-}
-
-// the solve that goes with kkt_factor_wave: root backward substitution by wave 0, then every leaf wave
-// corrects its right-hand side by the root solution and substitutes backwards -- no workgroup barrier
-// inside a leaf, no atomics
-template <class C>
-OMGX_FN void kkt_solve_wave(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
-  const BMat* Ms = (const BMat*)w.col;
-  const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
-  const int koff = (int)(w.kkt - omgx_lds);
-  OMGX_TIC();
-  if (wave == 0) {
-    const WPanel P = wpanel_root(Ms[d.n_leaf], d.n_root);
-    const double dl = wave_dinv<false>(w.kkt, P);
-    const double y = w.kkt[wcarried<false>(P, P.n) + (lane < P.n ? lane : 0)];           // L^{-1} r: the carried vector row
-    const double x = wave_bwd<OMGX_WAVE_COLS, false>(koff, P, dl, y * dl);
-    if (lane < P.n) sol[d.root_off + lane] = x;
-  }
-  c.sync();
-  OMGX_TOC(PH_K_ROOT);
-  double* xg = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1) + wave * 64;      // gathered root solution of this wave's leaf
-  for (int l = wave; l < d.n_leaf; l += nw) {
-    const BMat M = Ms[l];
-    if (__builtin_amdgcn_readfirstlane(M.bw) < 0) {
-      // sparse diagonal leaf: x_j = (r_j - sum_s v_s x_r[p_s] - v_t x_t) / d_j
-      const DiagLeaf L = diag_leaf(M);
-      const int j = lane < L.n ? lane : 0;
-      const double* A = w.kkt + L.base + j;
-      double acc = A[(2 + L.S) * L.n] - A[(1 + L.S) * L.n] * sol[d.root_off + d.n_root - 1];
-      for (int s = 0; s < L.S; ++s) {
-        const int ps = diag_leaf_pos(d, K, w, L, s, j);
-        acc = fma(-A[(1 + s) * L.n], sol[d.root_off + (ps < 0 ? 0 : ps)] * (ps < 0 ? 0.0 : 1.0), acc);
-      }
-      if (lane < L.n) sol[L.dinv + lane] = acc * w.dinv[L.dinv + j];
-      continue;
-    }
-    const WPanel P = wpanel_uniform(wpanel_leaf(M));
-    const int n = P.n, nc = P.nreg + 1 - P.n, ld = P.ld;          // (wave-uniform values: scalar loop bounds)
-    if (lane < nc) xg[lane] = sol[d.root_off + leaf_cpl_at(d, K, w, M.cpl, lane)];
-    wave_fence();
-    const int j = lane < n ? lane : 0;
-    const double* Wt = w.kkt + P.wbase + j;
-    double acc = Wt[nc * ld];                          // L^{-1} r_l
-#pragma unroll 4
-    for (int a = 0; a < nc; ++a) acc = fma(-Wt[a * ld], xg[a], acc);
-    const int dv = __builtin_amdgcn_readfirstlane(M.dinv);
-    const double dl = w.dinv[dv + j];
-    // (the leaf instance that factorised it, kkt_factor_wave: 36 positions instead of 40 where the leaf has no more)
-    const double x = wave_leaf_small(n, P.bw) ? wave_bwd<OMGX_LEAF_COLS_SMALL, true>(koff, P, dl, acc * dl)
-                                              : wave_bwd<OMGX_WAVE_COLS, true>(koff, P, dl, acc * dl);
-    if (lane < n) sol[dv + lane] = x;
-    wave_fence();
-  }
-  c.sync();
-  OMGX_TOC(PH_K_BWD);
+  return kkt_root_solve_wave(c, d, K, w, sol);
 }
 
 // One more solve with the factors kkt_factor_wave left in the store (the factorisation carries the right-hand side of the
@@ -1790,7 +1853,7 @@ OMGX_FN void kkt_solve_wave(const C& c, const Dims& d, const Kkt& K, Work& w, do
 // where kkt_rhs writes it (last carried row of every leaf, row nr of the root).  Leaf waves substitute forwards in
 // registers (wave_fwd_r) and form their share W Delta^{-1} y of the root's right-hand side; wave 0 subtracts the shares in
 // leaf order (fixed order of the sums), substitutes the root forwards and backwards; the leaves finish as in
-// kkt_solve_wave.  out [N]: the solution in position order (the equality multipliers of this solve are dropped).
+// kkt_root_solve_wave.  out [N]: the solution in position order (the equality multipliers of this solve are dropped).
 template <class C>
 OMGX_FN void kkt_solve2_wave(const C& c, const Dims& d, const Kkt& K, Work& w, double* out, bool with_y = false) {
   const BMat* Ms = (const BMat*)w.col;
@@ -1897,7 +1960,7 @@ OMGX_FN void kkt_solve2_wave(const C& c, const Dims& d, const Kkt& K, Work& w, d
 template <class C>
 OMGX_FN int kkt_factor(const C& c, const Dims& d, const Kkt& K, Work& w) {
 #ifndef OMGX_HOST_PORT
-  if constexpr (C::wave_only) return kkt_factor_wave(c, d, K, w);      // (compact store, omgx_plan.h)
+  if constexpr (C::wave_only) return kkt_factor_wave(c, d, K, w, w.sol);      // (compact store, omgx_plan.h; 0: the Newton step is in w.sol)
 #endif
   if constexpr (C::wave_only) return 1; else {
   int bad = 0;
@@ -2037,7 +2100,7 @@ template <class C>
 OMGX_FN int kkt_refactor_root(const C& c, const Dims& d, const Kkt& K, Work& w) {
 #ifndef OMGX_HOST_PORT
   if constexpr (!C::wave_only) return 1;      // (never reached: the blocked instances run with Dims::wave_ok = 0)
-  else return kkt_refactor_root_wave(c, d, K, w);
+  else return kkt_root_solve_wave(c, d, K, w, w.sol);      // (the leaf factors stay valid and final: the leaf waves preload here too)
 #else
   int bad = 0;
   BMat* Ms = (BMat*)w.col;
@@ -2122,7 +2185,7 @@ OMGX_FN void trsv_fwd4(const C& c, const double* A, Addr L, int n, double* y, co
 template <class C>
 OMGX_FN void kkt_solve(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
 #ifndef OMGX_HOST_PORT
-  if constexpr (C::wave_only) { kkt_solve_wave(c, d, K, w, sol); return; }
+  if constexpr (C::wave_only) return;      // (the factorisation that returned 0 ended in the substitutions: kkt_root_solve_wave)
 #endif
   if constexpr (!C::wave_only) {
   double* yr = sol + d.root_off;

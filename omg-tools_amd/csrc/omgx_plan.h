@@ -335,7 +335,7 @@ struct HostPlan {
       for (int l = 0; l < d.n_leaf; ++l) leaf_rows += (leaf_off[l + 1] - leaf_off[l]) + (cpl_ptr[l + 1] - cpl_ptr[l]) + 1;
       const int pr = leaf_rows > d.nr + 1 ? leaf_rows : d.nr + 1;
       d.col_doubles = (OMGX_BMAT_DOUBLES + OMGX_STAGE_LD) * (OMGX_MAX_LEAF + 1) + OMGX_PAN_LD * pr;
-      const int wave_scratch = OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1) + 8 * 64;      // kkt_solve_wave: 64 doubles per wave
+      const int wave_scratch = OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1) + 8 * 64;      // kkt_root_solve_wave: 64 doubles per wave
       if (d.col_doubles < wave_scratch) d.col_doubles = wave_scratch;
       if (compact) d.col_doubles = wave_scratch;      // (the wave path needs no panel buffers: descriptors + the gathered root solutions)
       int small = 0;

@@ -352,13 +352,15 @@ __device__ __forceinline__ double wave_dinv(const double* A, const WPanel P) {
 // x <- L^{-T} z for the factor stored in the panel (U = L D in LDS, left by wave_ldl): lane j reads
 // column j (u_ij, i > j), scales it by its own inverse pivot and the wave substitutes backwards with one
 // broadcast per row.  z: component `lane` (lanes >= n ignored); returns x_lane.
-template <int NC, bool BANDED>
-__device__ __forceinline__ double wave_bwd(int off, const WPanel Pin, double dinvl, double z) {
+// The two halves are routines of their own: the operands (column `lane` of L', scaled) depend on the factor alone, so a wave
+// may hold them in registers before z exists (kkt_root_solve_wave, omgx_core.h: a leaf wave loads them while wave 0 has the
+// root).  P: wave-uniform (wpanel_uniform).  lt: NA >= NC registers, the first NC are written / read.
+template <int NC, bool BANDED, int NA>
+__device__ __forceinline__ void wave_bwd_load(int off, const WPanel& P, double dinvl, double (&lt)[NA]) {
+  static_assert(NA >= NC, "room for NC operands");
   const double* A = omgx_lds + off;
-  const WPanel P = wpanel_uniform(Pin);
   const int lane = threadIdx.x & 63;
   const int n = P.n;
-  double lt[NC];
   const int c = lane < n ? lane : 0;
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
@@ -369,12 +371,23 @@ __device__ __forceinline__ double wave_bwd(int off, const WPanel Pin, double din
     const double v = A[wsym<BANDED>(P, ic) + cc];
     lt[i] = (i < n && lane < i && in) ? v * dinvl : 0.0;
   }
+}
+template <int NC, int NA>
+__device__ __forceinline__ double wave_bwd_chain(int n, const double (&lt)[NA], double z) {
+  const int lane = threadIdx.x & 63;
   double x = lane < n ? z : 0.0;
 #pragma unroll
   for (int i = NC - 1; i >= 1; --i) {
     if (i < n) x = fma(-lt[i], readlane_d(x, i), x);
   }
   return x;
+}
+template <int NC, bool BANDED>
+__device__ __forceinline__ double wave_bwd(int off, const WPanel Pin, double dinvl, double z) {
+  const WPanel P = wpanel_uniform(Pin);
+  double lt[NC];
+  wave_bwd_load<NC, BANDED>(off, P, dinvl, lt);
+  return wave_bwd_chain<NC>(P.n, lt, z);
 }
 
 // Substitutions for a right-hand side that did NOT ride through the factorisation (second-order correction of a trial

@@ -20,7 +20,11 @@ PHASES = ['jac', 'resid', 'assemble', 'factor', 'solve', 'step', 'linesearch', '
           # descriptors --, and the workgroup's last solve to its exit (queue counter, fences)
           'wg_head', 'wg_tail',
           # 'f_schur' split by wave 0's clock: forming the tiles of the Schur complements on the matrix pipe; subtracting them from the root, with its barriers
-          'f_schur_mfma', 'f_schur_sub']
+          'f_schur_mfma', 'f_schur_sub',
+          # wave 1's clock: loading the operands of its leaf's substitutions while wave 0 has the root.  (Since the factorisation ends in
+          # the substitutions, 'factor' holds 'k_root' -- wave 0's root substitution up to the barrier behind it -- and 'k_bwd' -- what
+          # the leaf waves do behind that barrier --, and 'solve' is what is left: refinement terms.)
+          'k_preload']
 
 
 def mpc_mode(problem, P, B, steps=20, warmup=3, rounds=False):
