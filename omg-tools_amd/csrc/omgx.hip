@@ -12,7 +12,7 @@
 #include <string>
 #include <vector>
 #include "../../include/omgx.h"
-#include "omgx_core.h"
+#include "omgx_types.h"
 #include "omgx_plan.h"
 #include "omgx_kernels.h"
 #include "omgx_table_cache.h"

@@ -1,6 +1,6 @@
 // omgx_core.h -- per-agent interior-point solve, written once for two targets:
 //
-//   * hipcc --offload-arch=gfx950: one 256-thread workgroup per agent, all
+//   * hipcc --offload-arch=gfx950: one 512-thread workgroup per agent, all
 //     state in LDS (omgx_solve_kernels.h: ipm_solve_kernel);
 //   * g++ -DOMGX_HOST_PORT: the same statements executed by one host thread
 //     (oracle/port/omgx_port.cpp) -- used ONLY as the timed CPU baseline and as
@@ -18,336 +18,24 @@
 // block-arrow LDL' (leaves = hyperplane blocks, root = trajectory block + t +
 // equality multipliers), fraction-to-boundary, Armijo on the barrier function,
 // monotone barrier update.
+//
+// Two parts stand in files of their own: omgx_types.h, what host and device share as data -- all the host code of the library
+// (omgx.hip, omgx_plan.h, omgx_device.h) includes of the solve --, and omgx_kkt_wave.h, the linear solve of the wave path
+// (device only).  The rest follows here in sections: execution context; parameter stage and row passes; blocked LDL';
+// descriptors; the linear solve (substitutions, right-hand side, then the blocked device path with the device entry points
+// and the host twin with its own); Hessian; setup, iteration, verification entry.
 #pragma once
-#include <stdint.h>
-#include <math.h>
-
+#include "omgx_types.h"
 #ifdef OMGX_HOST_PORT
-#define OMGX_FN inline
-#define OMGX_HD inline
-#define OMGX_HDF inline
-#else
-#define OMGX_FN __device__ __forceinline__
-#define OMGX_HD __host__ __device__ inline
-#define OMGX_HDF __host__ __device__ __forceinline__      // OMGX_FN that the plan (host code of the library) may call too
+#include <vector>      // the host twin's state (linear solve)
 #endif
 
-#ifdef OMGX_HOST_PORT
-#include <vector>
-static thread_local std::vector<double> omgx_rbak;      // root block before its factorisation (host twin of the wave path)
-#endif
 #ifdef OMGX_COUNT_FACT
 #include <atomic>
 static std::atomic<long> omgx_dbg_nfact(0);
 static std::atomic<long> omgx_dbg_cnt[12];      // 0 leaf failures, 1 root failures, 2 dw=0 attempts that failed, 3 decrease attempts that failed, 4 iterations
 #endif
 namespace omgx {
-
-enum { ROW_FREE = 0, ROW_UPPER = 1, ROW_LOWER = 2, ROW_EQ = 3, ROW_BAD = 4 };
-enum { OP_DIV = 0, OP_BSPL = 1, OP_COS = 2, OP_SIN = 3 };
-
-struct Dims {
-  int n_var, n_par, n_con, n_atoms, n_slots, n_terms, n_prog;
-  int N;        // n_var + 1 (phase-I variable t is variable index n_var)
-  int n_leaf, n_root, n_eq, nnz_j, root_off;
-  int nr;       // n_root + n_eq: order of the root block
-  int n_pairs;  // Jacobian entry pairs contributing to J' Sigma J
-  int n_eqe;    // Jacobian entries of the equality rows
-  int max_leaf, max_cpl;
-  int col_doubles;   // scratch for the blocked LDL' (staging + panel buffers)
-  int col_small_noroot;   // col_small without the LDS copy of the root block (mode 6)
-  int col_small;     // the same for the spill modes (left-looking leaf sweep only: inverse pivots + parked diagonal blocks per leaf): kept in LDS there
-  int mono_packed;   // 1: every parameter monomial has <= 4 atoms, Tables::pm_rec / sl_ell hold MonoRec; 2: <= 8 atoms, MonoRec8; 0: CSR tables only
-  int n_long;        // slots with more than OMGX_SLOT_CAP monomials (the first n_long entries of Tables::sl_list)
-  int n_hess;        // number of terms with >= 2 factors
-  int quartic;       // 1: some term has four factors
-  int general;       // 1: quartic terms, cos / sin atoms or basis rows of degree > 5: the kernel instance that carries them
-  int rp_packed;     // 1: rows and positions fit 16 bits each, Tables::je_rp is valid
-  int n_knots;       // total length of the knot vectors of the atoms program (copied to LDS per solve)
-  int atoms_alias;   // 1: atoms and knots live in the space of gbar | sol (they are dead once the slots are evaluated, gbar and sol
-                     //    are first written inside the iteration): n_atoms + n_knots <= 2 N + n_eq
-  int wave_ok;       // 1: every panel of the KKT store fits one wave (register-resident factorisation, omgx_wave.h)
-  int n_jv;          // Jacobian entries whose value depends on x (the others are constant over a solve)
-  int n_jv4, n_ja4;  // owners of the Jacobian item tables (four entries each): x-dependent entries, all entries
-  int ka_len, kh_len, kg_len;   // records per owner bin (longest bin) of the pair / Hessian / Gershgorin passes
-  int n_kafix, n_kgfix;         // targets whose run was cut (fix-up records)
-  int n_khfix;                  // the same for the Hessian items
-  int side_off, dump_off;       // side slots / per-lane dump slots behind the KKT store
-  int n_cs_own;      // owner threads of the column sums J'w (chunks of the columns)
-  int kg_side_dinv;  // 1: the side sums of the Gershgorin pass live in w.dinv, 0: in the side slots behind the KKT store
-  int n_owner;       // owner bins in use (<= OMGX_NBIN, the stride of the record tables): the threads of the workgroup the plan was made for
-  int n_lift, lift_depth;   // auxiliary variables of lifted products / quotients (omgx_template::n_lift) and the length of their longest chain
-  // Schur phase by tile owners (wave path; HostPlan::schur_rule, kkt_factor_wave): schur_tiles = number of banded leaves (they all
-  // couple to the same root positions in the same order), 0 = the round form.  The descriptor image then carries, as int32 behind
-  // its (n_leaf + 1) descriptors: that coupling row at schur_row, the dl_pos slice of the diagonal leaf at schur_dl (offsets in ints
-  // from the start of the image), schur_ints = length of the whole image
-  int schur_tiles, schur_row, schur_dl, schur_ints;
-};
-
-// one parameter monomial coef * prod atoms[a_k] as a single 16-byte record (a_k = -1: unused): one
-// load per monomial instead of the pointer chase pm_ptr -> pm_atom -> atoms of the CSR form
-struct MonoRec { double coef; int16_t a0, a1, a2, a3; };
-// the same with up to eight atoms (Dims::mono_packed == 2: ADMM objectives multiply rho, multipliers and basis values)
-struct MonoRec8 { double coef; int16_t a0, a1, a2, a3, a4, a5, a6, a7; };
-
-// Owner-computes records (omgx_plan.h): every sum of the solve has one owner thread and a fixed order.  A term is
-// coef * slot * x_v0 x_v1 x_v2 x_v3 (OMGX_TERM_VARS = 4 factors, -1: unused; a repeated index is a power).
-// JItem: one contribution coef * slot * x[va] * x[vb] * x[vc] (v = -1: factor 1) to a Jacobian entry: the term without
-// one of its factors.
-// HItem: one contribution of a nonlinear term to a KKT address (or, for the Gershgorin sums, to a position): the term
-// without two of its factors, h = lambda_row * coef * slot * x[vthird] * x[vfourth]; kind 1 = the two factors that
-// were taken out are the same variable (a diagonal entry: both orders of the pair land on it).
-// (slot indices are 16 bit in the 16- and 24-byte records: the plan refuses templates with more than 32767 slots)
-#define OMGX_TV 4
-struct JItem { double coef; int16_t slot, va, vb, vc; };
-// one term of a row for the row-value passes (24 bytes; padding records have coef 0)
-struct RowTerm { double coef; int32_t slot; int16_t v0, v1, v2, v3; };
-struct HItem { double coef; int32_t row, target; int16_t slot, vthird, vfourth, kind; };
-
-struct Tables {   // read-only, shared by all agents (global memory)
-  const int32_t* prog; const double* knots;
-  const int32_t* pp_ptr; const double* pm_coef; const int32_t* pm_ptr; const int32_t* pm_atom;
-  const int32_t* slot_pp;
-  const MonoRec* pm_rec;    // [n_mono] packed form of (pm_coef, pm_ptr, pm_atom); valid if Dims::mono_packed
-  const int32_t* slot_rng;  // [n_slots][2] monomial range of every slot (= pp_ptr[slot_pp[s]], pp_ptr[slot_pp[s] + 1])
-  const int32_t* row_ptr; const double* t_coef; const int32_t* t_slot; const int32_t* t_var;
-  const int32_t* order; const int32_t* leaf_off; const int32_t* blk;
-  const int32_t* eq_rows; const int32_t* eq_index;
-  const int32_t* cpl_ptr; const int32_t* cpl_idx; const int32_t* cpl_map;
-  const int32_t* d_off; const int32_t* b_off;   // panel offsets / leading dimensions inside the KKT store
-  // compact store of the wave path (omgx_plan.h `compact`): per leaf the offset of its carried rows (sparse diagonal
-  // leaf: the number of coupling slots S), the row stride and width of its band, its kind (0 banded panel, 1 sparse
-  // diagonal leaf); dl_pos[4 * leaf_off[l] + s * n_l + j]: root position coupled through slot s of variable j (-1: none)
-  const int32_t* lf_w; const int32_t* lf_ldb; const int32_t* lf_band; const int32_t* lf_kind; const int32_t* dl_pos;
-  const int32_t* bmat_img;  // compact store only: the matrix descriptors of a solve, [n_leaf + 1] BMat as the plan filled them (kkt_describe_fill)
-  // precomputed KKT addresses (HostPlan): Jacobian pairs, t-column, diagonal, Hessian terms
-  const int32_t* eqe3;      // [n_eqe][3] = {Jacobian entry, KKT address, row} of the equality-row entries
-  const int32_t* pair4;     // [n_pairs][4] = {Jacobian entry a, entry b, KKT address, row}: one 16-byte record per pair
-  const int32_t* je_row; const int32_t* diag_addr;
-  const int32_t* je_rp;     // [nnz_j] (row << 16) | position of every Jacobian entry (valid if Dims::rp_packed)
-  const double* reg_w;   // [N] position order: inertia-correction class (+1 nonlinear root variable, -1 nonlinear leaf variable, else the weight itself: OMGX_DW_LINEAR)
-  const int32_t* leaf_bw;   // [n_leaf] half bandwidth of the leaf block in its (reverse Cuthill-McKee) order
-  const int32_t* tq_addr;   // [n_var] KKT address of (t, q)
-  // owner-computes tables
-  const int32_t* row_perm;  // [n_con] rows, longest term list first
-  // ELL tables of the row / column / entry owners: record `step` of owner i at index step * n_owner + i
-  // (coalesced across the lanes), padded with null records; *_glen[i >> 6] = steps the 64 owners of a
-  // group need (rounded up to the batch the loops load at a time)
-  const RowTerm* rt_ell;    // [rt_steps][n_con] terms of row row_perm[i]
-  const int32_t* rt_glen;
-  const int32_t* jp_ell;    // [jp_steps][n_con][2] {Jacobian entry, position} of row row_perm[i] (padding: entry nnz_j = 0.0)
-  const int32_t* jp_glen;
-  const int32_t* cs_ell;    // [cs_steps][n_cs_own][2] {Jacobian entry, row} of column-sum owner o (padding: entry nnz_j = 0.0)
-  const int32_t* cs_glen;
-  const int32_t* cs_own;    // [n_var + 1] owners of the column in slot j: cs_own[j] .. cs_own[j + 1]
-  const int32_t* cs_col;    // [n_var] column (position) of slot j (columns by decreasing length)
-  // Jacobian items, four entries per owner (jac_entries4): the x-dependent entries (every iteration) and all entries (setup)
-  const JItem* jv_ell;      // [jv_steps][4][n_jv4] items of the owner's k-th entry (entries by decreasing item count, four in a row per owner)
-  const int32_t* jv_own;    // [4][n_jv4][2] {entry, row} (-1: the owner has no k-th entry)
-  const int32_t* jv_glen;   // [n_jv4 / 64] items per entry the group walks (1 or even)
-  const JItem* ja_ell;      // [ja_steps][4][n_ja4]
-  const int32_t* ja_own;
-  const int32_t* ja_glen;
-  const int32_t* sl_list;   // [n_slots] slots by decreasing monomial count
-  const MonoRec* sl_ell;    // [sl_steps][n_slots] monomials of slot sl_list[i] (padding: coef 0)
-  const int32_t* sl_glen;
-  // lifted auxiliaries (Dims::n_lift), level by level: lift_rec[k] = {ELL slot of the defining row, the auxiliary variable}; the records of
-  // level L (rows that read auxiliaries of the levels below only) are lift_lev[L] .. lift_lev[L + 1]
-  const int32_t* lift_rec; const int32_t* lift_lev;
-  const int32_t* cs_ptr;    // [n_var + 1] column (position) -> its entries, row order
-  const int32_t* cs_rec;    // [.][2] {Jacobian entry, row}
-  const int32_t* obj_ent;   // [n_var] objective-row entry of the position (-1: none)
-  // ELL layout: record r of owner bin b at index r * OMGX_NBIN + b (coalesced across the lanes), a bin's
-  // records sorted by target; the target is stored only in the last record of its run (-1 in the others
-  // and in the padding): the owner adds every record to a running sum and stores / restarts where it sees one
-  const int32_t* ka_rec;    // [ka_len][OMGX_NBIN][4] pair records {entry a, entry b, KKT address, row}
-  const HItem* kh_rec;      // [kh_len][OMGX_NBIN] Hessian items (target = KKT address)
-  const HItem* kg_rec;      // [kg_len][OMGX_NBIN] Gershgorin items (target = position, N + k = side slot k)
-  const int32_t* kh_fix;    // [n_khfix][3] the same for cut runs of Hessian items (after hess_bin)
-  const int32_t* ka_fix;    // [n_kafix][3] {KKT address, first side slot, number of side slots}: address += the slots, in order
-  const int32_t* kg_fix;    // [n_kgfix][3] the same for the Gershgorin sums (position)
-};
-
-struct Opts {
-  double tol; int max_iter; double mu_init, kappa_push, nu_init, scale_gmax;
-  int warm_start;      // 1: lam0 holds the multipliers of the previous solve (primal-dual warm start)
-  double kappa_warm;   // kappa_push used for warm starts
-  double dw_leaf_ratio_cold;   // cold starts: inertia-correction weight of nonlinear leaf variables (root: its inverse)
-  int prio_iter;               // device: iteration from which a solve runs at raised wave priority (0: never)
-  double warm_mu_factor;       // warm starts: mu_0 = clamp(warm_mu_factor * mean(s z), tol / 10, mu_init)
-  double warm_z_floor;         // warm starts: multipliers lifted to max(OMGX_WARM_ZMIN, min(warm_z_floor * tol, warm_z_cap * tol / slack))
-  double warm_z_cap;           // (0: no cap)
-  int max_soc;                 // > 0: a rejected first trial of the line search is answered by up to max_soc second-order corrections (every template class: kkt_solve2_wave / kkt_solve2)
-  int hess_approx;             // 1: no constraint curvature in the Hessian, damping driven by the accepted step length (general instances; include/omgx.h)  // (version 8) IPOPT's absolute tolerances on the UNSCALED problem beside `tol` (its documented defaults: compl_inf_tol = constr_viol_tol = 1e-4,
-  // which the reference leaves in force when it sets ipopt.tol = 1e-3, `problems/problem.py:57`); 0: not tested (rounds 1-5).  The barrier
-  // parameter ends at min(tol, compl_tol) / 10.
-  double compl_tol, viol_tol;
-  int refine;                  // (version 9) 1: iterative refinement of a regularised Newton step, from the second iteration of a solve on (default 0)
-};
-
-// fixed constants of the iteration (same values in oracle/ipm_numpy.py DEFAULTS)
-#ifndef OMGX_KAPPA_EPS
-#define OMGX_KAPPA_EPS   10.0
-#endif
-#define OMGX_KAPPA_MU    0.2
-#define OMGX_THETA_MU    1.5
-#define OMGX_TAU_MIN     0.99
-#define OMGX_DELTA_C     1e-8    // regularisation of the equality block: delta_c = OMGX_DELTA_C * mu^(1/4) (IPOPT's delta_c_bar mu^kappa_c)
-#define OMGX_ETA         1e-4
-#define OMGX_PHI_NOISE   1e-10   // predicted merit decrease (relative) below which the Armijo test is skipped
-#define OMGX_DW_FIRST    1e-4
-#ifndef OMGX_DW_INC
-#define OMGX_DW_INC      10.0
-#endif
-#ifndef OMGX_DW_DEC
-#define OMGX_DW_DEC      (1.0 / 3.0)
-#endif
-#define OMGX_DW_MAX      1e10
-#define OMGX_DW_ZERO     1e-9
-#define OMGX_DW_HEAVY    10.0
-#ifndef OMGX_KAPPA_EPS_HEAVY
-#define OMGX_KAPPA_EPS_HEAVY 100.0    // (round 4 tried 30: same-box A/B, 4096 agents: config 2 cold 91.4k vs 90.0k solves/s -- noise -- but the Quadrotor class 12.2k vs 15.7k cold, 25.2 vs 21.7 ms per warm step: kept at 100)
-#endif
-#ifndef OMGX_DW_BACKOFF_MAX
-#define OMGX_DW_BACKOFF_MAX 8
-#endif
-#ifndef OMGX_EXPAND_MAX
-#define OMGX_EXPAND_MAX   16.0    // longest multiple of a regularised Newton step the line search offers
-#endif
-#ifndef OMGX_EXPAND_DW
-#define OMGX_EXPAND_DW    1e-2    // ... when the inertia correction is at least this heavy
-#endif
-#ifndef OMGX_EXPAND_FROM
-#define OMGX_EXPAND_FROM  2       // ... after this many iterations in a row that accepted their full step at the first trial
-#endif
-#define OMGX_LS_RETRY    3       // line-search failures in a row that are answered by a heavier inertia correction
-#define OMGX_LS_RETRY_DW 100.0
-#define OMGX_DW_CAP_FLOOR 0.03  // share of dw every nonlinear variable keeps under the Gershgorin cap
-#ifndef OMGX_DW_CLAMP_FROM
-#define OMGX_DW_CLAMP_FROM 1.0  // an inertia correction above this is compared with the Gershgorin guarantee (round 5, see the factorisation loop)
-#endif
-#define OMGX_DW_LINEAR   1e-8   // relative inertia correction of variables that only appear linearly
-#ifndef OMGX_FTB_ACTUAL
-#define OMGX_FTB_ACTUAL  0.5     // share of the linear fraction-to-boundary bound (1 - tau) s the slack of a row must really keep at an accepted trial point
-#endif
-#define OMGX_S_MAX       100.0
-#define OMGX_KAPPA_SIGMA 1e10
-#define OMGX_MAX_BACKTRACK 25
-#define OMGX_NU_MAX      1e8
-#ifndef OMGX_STALL_ITERS
-#define OMGX_STALL_ITERS 20
-#endif
-#define OMGX_WARM_ZMIN   1e-8
-#define OMGX_MAX_LEAF    16
-#define OMGX_BMAT_DOUBLES 5      // sizeof(BMat) / 8
-#define OMGX_PAN_LD 5      // panel buffer row stride: U[4] + pad (odd: conflict-free row-per-lane access)
-#define OMGX_STAGE_LD 20   // per matrix: 4x4 block rows [16] + inverse pivots of the block [4]
-#define OMGX_MIN_LEAF    8       // smaller components are gathered into one leaf
-#define OMGX_NBIN        512     // owner bins of the assembly passes (= threads of the solve workgroup)
-#define OMGX_SLOT_CAP    16      // monomials of a parameter slot one thread sums (setup); the rest of a longer slot: one wave
-#define OMGX_REC_BATCH   8       // records an owner loads at a time (all in flight together)
-#define OMGX_RUN_CAP     16      // longest run of records summed by one owner (longer runs are cut, see omgx_plan.h)
-#define OMGX_RUN_CAP_H   64      // the same for the Hessian items (only templates with lifted auxiliaries have such runs)
-#define OMGX_WAVE_ROWS   64      // register rows of a panel the wave-level routines take (lanes)
-#define OMGX_WAVE_COLS   40      // columns (registers per lane)
-
-// Per-agent work arrays (LDS on the device, heap on the host port).
-struct Work {
-  double *atoms, *slots, *knots;
-  double *x, *xt;                 // [N] variable order, x[n_var] = t
-  double *hv, *ht;                // [n_con] scaled row values (h for inequality, c for equality)
-  double *rho, *vv;               // [n_con] row scale (signed), phase-I weights
-  double *z, *ds;                 // [n_con] multiplier (y for equality rows), slack step
-  // (the slack of an inequality row is not stored: every iterate keeps s = t v - h exactly -- `row_slack`; the bound of a
-  // row is read from the caller's lbg / ubg where the line search needs it)
-  double *jval;                   // [nnz_j] scaled Jacobian entries (objective row unscaled)
-  double *gbar, *sol;             // [N], [N + n_eq]   position order
-  double *kkt;                    // D_l (packed) | B_l | R (packed)
-  double *col;                    // [col_doubles] blocked-LDL' staging + panel buffers
-  double *root;                   // spill modes: LDS copy of the packed root block (+ its right-hand-side row) from the Schur step on (inside col)
-  double *dinv;                   // [N] inverse leaf pivots
-  int8_t *rtype;                  // [n_con]
-  double *red;                    // reduction scratch [64]
-};
-
-// Workspace placement.  Mode 0 keeps every array in LDS (the fast path: cfg 1/2/4).  Problems
-// whose arrays exceed the 160 KiB of one CU spill the largest ones to a per-workgroup slab in
-// HBM (L2/MALL-cached), largest first:
-//   mode 1  kkt                  mode 2  + jval
-//   mode 3  + the six [n_con] row arrays and rtype (only the O(n_var) vectors stay in LDS)
-// Mode 4 is the other direction: templates on the register-resident wave path whose workspace then fits HALF a CU --
-// two workgroups (agents) per CU -- put the Jacobian values and the row values hv into the slab and keep the
-// (compact) KKT store and every array the owner passes gather from in LDS.
-// Mode 5 (round 4) is mode 4 with the row values hv back in LDS, for templates that still fit half a CU then (config 2: 80,280 B):
-// hv is read by a dozen row passes per iteration, each a dependent global load per pass of the workgroup (+2 % solves/s).
-// Mode 6 (round 5) is mode 3 with the root block left in the slab as well: templates whose root block (its variables + ALL
-// equality rows: the classes with lifted auxiliaries carry hundreds, include/omgx.h n_lift) does not fit LDS even alone
-// (Bicycle: order 439 = 773 KB).  Only the O(n_var) vectors, the descriptors and the panel buffers stay on chip.
-enum { WS_LDS = 0, WS_KKT_HBM = 1, WS_JAC_HBM = 2, WS_ROWS_HBM = 3, WS_JAC_ONLY = 4, WS_JAC_HV = 5, WS_ROOT_HBM = 6, WS_MODES = 7 };
-OMGX_HD constexpr bool ws_kkt_hbm(int mode) { return (mode >= WS_KKT_HBM && mode <= WS_ROWS_HBM) || mode == WS_ROOT_HBM; }
-OMGX_HD constexpr bool ws_jac_hbm(int mode) { return mode >= WS_JAC_HBM; }
-OMGX_HD constexpr bool ws_rows_hbm(int mode) { return mode == WS_ROWS_HBM || mode == WS_ROOT_HBM; }
-OMGX_HD constexpr bool ws_hv_hbm(int mode) { return mode == WS_ROWS_HBM || mode == WS_JAC_ONLY || mode == WS_ROOT_HBM; }
-OMGX_HD constexpr bool ws_root_lds(int mode) { return ws_kkt_hbm(mode) && mode != WS_ROOT_HBM; }      // spill modes 1-3: the root block is copied to LDS for its factorisation
-
-OMGX_HD size_t root_doubles(const Dims& d) { return ((size_t)(d.nr + 1) * (d.nr + 2)) / 2; }
-
-OMGX_HD void work_split(const Dims& d, int kkt_doubles, int mode, size_t* lds, size_t* hbm) {
-  size_t nl = 0, ng = 0;
-  nl += d.n_slots + (d.atoms_alias ? 0 : d.n_atoms + d.n_knots);
-  nl += 2 * (size_t)d.N;
-  nl += d.N + (d.N + d.n_eq);
-  nl += d.N;                      // dinv
-  nl += 64;                       // red
-  const size_t rows = 5 * (size_t)d.n_con + (d.n_con + 7) / 8;
-  (ws_rows_hbm(mode) ? ng : nl) += rows;
-  (ws_hv_hbm(mode) ? ng : nl) += d.n_con;             // hv: only ever read by the thread that owns the row
-  (ws_jac_hbm(mode) ? ng : nl) += d.nnz_j + 1;        // + one slot that stays 0.0 (padding records point at it)
-  // (the spill modes keep the matrix descriptors and the small panel scratch of the leaf sweep in LDS: every row of
-  // every block column reads them)
-  if (ws_kkt_hbm(mode)) { ng += (size_t)kkt_doubles; nl += ws_root_lds(mode) ? d.col_small : d.col_small_noroot; } else nl += (size_t)kkt_doubles + d.col_doubles;
-  *lds = nl; *hbm = ng;
-}
-
-OMGX_HD size_t work_doubles(const Dims& d, int kkt_doubles) {
-  size_t nl, ng;
-  work_split(d, kkt_doubles, WS_LDS, &nl, &ng);
-  return nl;
-}
-
-// MODE is a compile-time constant so that every pointer keeps a provable address space
-template <int MODE>
-OMGX_HD void work_carve_split(Work& w, double* lds, double* hbm, const Dims& d, int kkt_doubles) {
-  double* p = lds;
-  double* g = hbm;
-  w.slots = p; p += d.n_slots;
-  if (!d.atoms_alias) { w.atoms = p; p += d.n_atoms; w.knots = p; p += d.n_knots; }
-  w.x = p; p += d.N;             w.xt = p; p += d.N;
-  w.gbar = p; p += d.N;          w.sol = p; p += d.N + d.n_eq;
-  if (d.atoms_alias) { w.atoms = w.gbar; w.knots = w.gbar + d.n_atoms; }
-  w.dinv = p; p += d.N;
-  w.red = p; p += 64;
-  if (ws_rows_hbm(MODE)) {
-    w.ht = g; g += d.n_con;        w.rho = g; g += d.n_con;     w.vv = g; g += d.n_con;
-    w.z = g; g += d.n_con;         w.ds = g; g += d.n_con;
-    w.rtype = (int8_t*)g; g += (d.n_con + 7) / 8;
-  } else {
-    w.ht = p; p += d.n_con;        w.rho = p; p += d.n_con;     w.vv = p; p += d.n_con;
-    w.z = p; p += d.n_con;         w.ds = p; p += d.n_con;
-    w.rtype = (int8_t*)p; p += (d.n_con + 7) / 8;
-  }
-  if (ws_hv_hbm(MODE)) { w.hv = g; g += d.n_con; } else { w.hv = p; p += d.n_con; }
-  if (ws_jac_hbm(MODE)) { w.jval = g; g += d.nnz_j + 1; } else { w.jval = p; p += d.nnz_j + 1; }
-  if (ws_kkt_hbm(MODE)) { w.kkt = g; g += kkt_doubles; w.col = p; p += ws_root_lds(MODE) ? d.col_small : d.col_small_noroot; }
-  else { w.kkt = p; p += kkt_doubles; w.col = p; p += d.col_doubles; }
-  // spill modes: the root block is copied behind the root's panel buffer before the Schur updates -- over the leaf
-  // sweep's scratch, which is dead by then (Dims::col_small covers both)
-  w.root = ws_root_lds(MODE) ? w.col + (OMGX_BMAT_DOUBLES + OMGX_STAGE_LD) * (OMGX_MAX_LEAF + 1) + OMGX_PAN_LD * (d.nr + 1) : nullptr;
-}
-
-OMGX_HD void work_carve(Work& w, double* base, const Dims& d, int kkt_doubles) {
-  work_carve_split<WS_LDS>(w, base, nullptr, d, kkt_doubles);
-}
 
 // ---------------------------------------------------------------------------
 // execution context: thread id, barrier, reductions, LDS atomic add
@@ -372,30 +60,49 @@ struct Ctx {
   void wave_sync() const {}
 };
 #else
-// kWaveOnly: the kernel instance for templates whose panels all fit one wave (Dims::wave_ok): the blocked LDS
+// The compile-time flags of a kernel instance, by name (CF_*), carried by one type: CtxT<F> reads F::hbm, F::wave_only, ...
+// hbm: the KKT store is in the HBM slab (spill modes, ws_kkt_hbm)
+// wave_only: the kernel instance for templates whose panels all fit one wave (Dims::wave_ok): the blocked LDS
 // routines are not compiled into it
-// kGeneral: the instance for templates with Dims::general set (terms with four factors, cos / sin atoms, basis rows of
+// root_lds: Work::root holds the root block from the Schur step on (spill modes, ws_root_lds)
+// general: the instance for templates with Dims::general set (terms with four factors, cos / sin atoms, basis rows of
 // degree > 5): the other instance does not carry that code -- at the 256-register cap of this kernel it cost spills
-// kPrep: the instance of the setup kernel (ipm_prepare_kernel): row arrays and Jacobian values in the agent's record in global
+// prep: the instance of the setup kernel (ipm_prepare_kernel): row arrays and Jacobian values in the agent's record in global
 // memory, no KKT store
-// kRefine: the instance that carries the refinement of regularised steps (Opts::refine): its second solve and its second pass through
+// refine: the instance that carries the refinement of regularised steps (Opts::refine): its second solve and its second pass through
 // the step phase cost the instance without them 2.5 % of its cycles per solve through register pressure alone (345.8 k against 337 k)
-// kLean: the instance for launches that leave the optional features off (picked per launch by omgx_batch_solve): here the absolute
+// lean: the instance for launches that leave the optional features off (picked per launch by omgx_batch_solve): here the absolute
 // tolerances Opts::compl_tol / viol_tol are compile-time zeros -- their tests, the per-row division of the error-measure pass and the
-// nu escalation are not in the code; the solve kernel drops its own optional blocks on the same flag.  Like kRefine, a matter of
+// nu escalation are not in the code; the solve kernel drops its own optional blocks on the same flag.  Like refine, a matter of
 // register pressure: code that is merely present costs the instance that never runs it cycles
-template <bool kHbm, bool kWaveOnly = false, bool kRootLds = false, bool kGeneral = false, bool kPrep = false, bool kRefine = false,
-          bool kLean = false>
+enum : unsigned { CF_HBM = 1, CF_WAVE_ONLY = 2, CF_ROOT_LDS = 4, CF_GENERAL = 8, CF_PREP = 16, CF_REFINE = 32, CF_LEAN = 64 };
+template <unsigned BITS>
+struct CtxFlags {
+  static constexpr bool hbm = (BITS & CF_HBM) != 0, wave_only = (BITS & CF_WAVE_ONLY) != 0, root_lds = (BITS & CF_ROOT_LDS) != 0,
+                        general = (BITS & CF_GENERAL) != 0, prep = (BITS & CF_PREP) != 0, refine = (BITS & CF_REFINE) != 0,
+                        lean = (BITS & CF_LEAN) != 0;
+};
+// The flags of the solve, eval and rollout instances from the kernels' own template parameters: how hbm and root_lds follow from
+// the workspace mode is stated here and nowhere else.  (Aliases of the one flags type, not a type per mode: the modes that agree
+// in every flag -- 0, 4 and 5 -- are one CtxT and share its out-of-line reductions, as they did.)
+template <int MODE, bool WAVE_ONLY, bool GEN, bool REFINE = false, bool LEAN = false>
+using SolveFlags = CtxFlags<(ws_kkt_hbm(MODE) ? CF_HBM : 0u) | (WAVE_ONLY ? CF_WAVE_ONLY : 0u) | (ws_root_lds(MODE) ? CF_ROOT_LDS : 0u) |
+                            (GEN ? CF_GENERAL : 0u) | (REFINE ? CF_REFINE : 0u) | (LEAN ? CF_LEAN : 0u)>;
+template <bool GEN> using PrepareFlags = CtxFlags<CF_PREP | (GEN ? CF_GENERAL : 0u)>;      // the setup kernel
+typedef CtxFlags<0u> PlainFlags;                   // everything in LDS, blocked routines (the micro tools of the blocked path)
+typedef CtxFlags<CF_WAVE_ONLY> WaveToolFlags;      // everything in LDS, wave path (the micro tools of the wave path)
+
+template <class F>
 struct CtxT {
-  static constexpr bool hbm = kHbm;
-  static constexpr bool prep = kPrep;
-  static constexpr bool refine = kRefine;
-  static constexpr bool lean = kLean;
-  static constexpr bool general = kGeneral;
-  static constexpr bool root_lds = kRootLds;      // Work::root holds the root block from the Schur step on (spill modes)
-  static constexpr bool wave_only = kWaveOnly;
+  static constexpr bool hbm = F::hbm;
+  static constexpr bool prep = F::prep;
+  static constexpr bool refine = F::refine;
+  static constexpr bool lean = F::lean;
+  static constexpr bool general = F::general;
+  static constexpr bool root_lds = F::root_lds;
+  static constexpr bool wave_only = F::wave_only;
   // the wave-level routines address the KKT store as LDS: the spill-mode instances do not carry them
-  static constexpr bool no_wave = kHbm;
+  static constexpr bool no_wave = hbm;
   double* red;
   long long* prof;
   // (opaque to the optimiser: otherwise every per-thread table address `base + tid * size` of every phase is
@@ -479,25 +186,17 @@ struct CtxT {
   // lanes of one wave run in lockstep; this only orders their memory traffic (LDS: in-order per
   // wave; spilled arrays in HBM: wait for the vector-memory counters as well)
   __device__ void wave_sync() const {
-    if (kHbm) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
+    if (hbm) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
     else { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
   }
 };
-typedef CtxT<false> Ctx;
+typedef CtxT<PlainFlags> Ctx;
 #endif
 
 #define OMGX_PFOR(i, n) for (int i = c.tid(); i < (n); i += c.nthr())
 #define OMGX_PFOR_U4(i, n) _Pragma("unroll 4") for (int i = c.tid(); i < (n); i += c.nthr())
 
-// optional per-phase cycle counters (profiling build only, -DOMGX_PROFILE)
-enum { PH_JAC = 0, PH_RESID, PH_ASSEMBLE, PH_FACTOR, PH_SOLVE, PH_STEP, PH_LINESEARCH, PH_UPDATE, PH_F_LEAF, PH_F_SCHUR, PH_F_ROOT, PH_LA, PH_LS, PH_LB, PH_SETUP, PH_TOTAL,
-       PH_S_DESC, PH_S_PARAMS, PH_S_JAC0, PH_S_CLASS, PH_S_INIT, PH_A_ZERO, PH_A_PAIRS, PH_A_REST, PH_A_DIAG,
-       PH_K_FWD, PH_K_ROOTRHS, PH_K_ROOT, PH_K_LEAFRHS, PH_K_BWD, PH_L_TERMS, PH_L_ROWS,
-       PH_F_PARK, PH_F_SWEEP, PH_F_SCALE, PH_A_TCOL, PH_A_HESS, PH_P_LOAD, PH_P_DIV, PH_P_BSPL, PH_P_SLOTS,
-       PH_WG_HEAD, PH_WG_TAIL,      // outside PH_TOTAL: kernel entry (or the workgroup's previous solve) to the start of a solve; its last solve to its exit
-       PH_F_SCHUR_MFMA, PH_F_SCHUR_SUB,      // PH_F_SCHUR split by wave 0's clock: forming the tiles of S_l on the matrix pipe; subtracting them from the root (with its barriers)
-       PH_K_PRELOAD,      // wave 1's clock: loading the operands of its leaf's substitutions while wave 0 has the root (kkt_root_solve_wave)
-       PH_COUNT };
+// per-phase cycle counters (PH_*, omgx_types.h; profiling build only, -DOMGX_PROFILE)
 #if defined(OMGX_PROFILE) && !defined(OMGX_HOST_PORT)
 #define OMGX_TIC() long long tic_ = (c.sync(), clock64())
 #define OMGX_TOC(k) do { c.sync(); long long now_ = clock64(); if (c.tid() == 0 && c.prof) c.prof[k] += now_ - tic_; tic_ = now_; } while (0)
@@ -754,7 +453,6 @@ OMGX_FN double jitem_value(const JItem& q, const Work& w, const double* xv) {
 // the workgroup over all entries, 5 over the x-dependent ones; here a thread has the items of four entries in flight, a
 // group of 64 owners whose entries are all single items loads just those.  fn(entry, row, value); items summed in step
 // order.  glen[o >> 6]: items per entry the group walks (1, or a multiple of 2).
-#define OMGX_JE_OWN 4
 template <class C, class F>
 OMGX_FN void jac_entries4(const C& c, const JItem* ell, const int32_t* own, const int32_t* glen, int n_own, const Work& w, const double* xv, F fn) {
   OMGX_PFOR(o, n_own) {
@@ -858,36 +556,6 @@ OMGX_FN double row_value_share(const C& c, const Tables& T, const Work& w, int r
 }
 
 // ---------------------------------------------------------------------------
-// block-arrow KKT store
-// ---------------------------------------------------------------------------
-OMGX_FN int tri(int i, int k) { return i * (i + 1) / 2 + k; }   // packed lower, row-major, i >= k
-
-struct Kkt {
-  // (copies of the few table pointers / dimensions it needs, not pointers to the structs: a struct whose address
-  // escapes into a helper object cannot be kept in scalar registers -- the compiler copied all of Dims and
-  // Tables into every lane's scratch memory at kernel entry)
-  const int32_t *d_off, *b_off, *leaf_off, *leaf_bw, *cpl_ptr, *cpl_idx, *blk, *cpl_map, *lf_w, *lf_ldb, *lf_band, *lf_kind, *dl_pos;
-  int n_leaf, n_root, root_off;
-  double* a;
-  OMGX_HDF void bind(const Dims& dd, const Tables& TT, double* store) {
-    d_off = TT.d_off; b_off = TT.b_off; leaf_off = TT.leaf_off; leaf_bw = TT.leaf_bw; cpl_ptr = TT.cpl_ptr;
-    cpl_idx = TT.cpl_idx; blk = TT.blk; cpl_map = TT.cpl_map;
-    lf_w = TT.lf_w; lf_ldb = TT.lf_ldb; lf_band = TT.lf_band; lf_kind = TT.lf_kind; dl_pos = TT.dl_pos;
-    n_leaf = dd.n_leaf; n_root = dd.n_root; root_off = dd.root_off; a = store;
-  }
-  // leaf l: panel of (n_l + nc_l + 1) rows with odd leading dimension ld_l; rows [0,n_l) hold the
-  // leaf block D_l (lower part), rows [n_l, n_l+nc_l) the coupling rows B_l (one per coupled
-  // root position), row n_l+nc_l the right-hand side of the leaf.  Root block R: packed lower,
-  // row-major, nr rows + one more for its right-hand side.  The right-hand sides are carried through
-  // the factorisation like coupling rows, so the forward substitutions L^{-1} r come out of it.
-  OMGX_FN double* P(int l) const { return a + d_off[l]; }
-  OMGX_HDF int ld(int l) const { return b_off[l]; }
-  OMGX_FN double* R() const { return a + d_off[n_leaf]; }
-  OMGX_HDF int nl(int l) const { return leaf_off[l + 1] - leaf_off[l]; }
-  OMGX_HDF int nc(int l) const { return cpl_ptr[l + 1] - cpl_ptr[l]; }
-};
-
-// ---------------------------------------------------------------------------
 // Blocked LDL' (panel width 4 = the K of v_mfma_f64_16x16x4_f64).
 //
 // A "matrix" here is a set of rows: the first nfact rows/columns form the
@@ -902,11 +570,7 @@ struct Kkt {
 //            16x16 tile on the device.
 // Two workgroup barriers per 4 columns instead of two per column.
 // ---------------------------------------------------------------------------
-// offsets (not pointers) so that every access stays a provable LDS access (ds_* instead of flat_*)
-struct BMat { int a, ld, nfact, rows, npos, dinv, pan, cpl, bw, pad_; };   // cpl: offset of the leaf's coupling index list (cpl_ptr[l])   // a: offset in kkt; dinv: offset in w.dinv (-1: none); pan: offset in w.col
-static_assert(sizeof(BMat) <= OMGX_BMAT_DOUBLES * sizeof(double), "BMat larger than its LDS slot");
 #define OMGX_NB 4
-#define OMGX_PAN_SMALL(n) (4 * (n) + 16)      // per leaf in the spill modes: ldl_left4 keeps n inverse pivots + 10 doubles per 4 columns there
 
 // (branch-free on purpose: with `ld ? row-major : packed` as a conditional the compiler sinks the
 // LDS load that uses the address into the two branches, and a sequence of such loads -- the ten
@@ -936,11 +600,6 @@ OMGX_FN double rcp_pivot(double d) {
 }
 #endif
 
-}  // namespace omgx
-#ifndef OMGX_HOST_PORT
-#include "omgx_wave.h"      // register-resident wave-level LDL' (device only)
-#endif
-namespace omgx {
 
 // 4x4 (or smaller) diagonal block LDL' from the stored lower entries
 struct Blk4 { double l10, l20, l21, l30, l31, l32, d0, d1, d2, d3, i0, i1, i2, i3; };
@@ -1332,32 +991,6 @@ OMGX_FN void ldl_blocked(const C& c, const BMat* Ms, int nm, double* A, double* 
   *bad = c.rmax(badl ? 1.0 : 0.0) > 0.0 ? 1 : 0;
 }
 
-// Matrix descriptors of the block-arrow store, at the head of w.col (shared by the workgroup), followed by the staging area
-// and the panel buffers.  kkt_describe_fill is the one definition of their fields: a kernel runs it per workgroup
-// (kkt_describe: the plan tables it reads are global memory, i.e. a chain of dependent loads per look-up), the plan runs it
-// once per template for the instances on the wave path, whose descriptors depend on the template alone (HostPlan::bmat_img,
-// Tables::bmat_img) and are then copied (kkt_descriptors).
-template <bool WAVE_ONLY, bool HBM, bool ROOT_LDS>
-OMGX_HDF void kkt_describe_fill(const Dims& d, const Kkt& K, BMat* Ms) {
-  const int pan0 = (OMGX_BMAT_DOUBLES + OMGX_STAGE_LD) * (OMGX_MAX_LEAF + 1);      // (offset of the panel buffers in w.col)
-  int pan = pan0;
-  for (int l = 0; l < d.n_leaf; ++l) {
-    BMat& M = Ms[l];
-    if constexpr (WAVE_ONLY) {
-      // compact store: a = band of the leaf block (sparse diagonal leaf: its arrays), pan = its carried rows
-      // (sparse: number of coupling slots), pad_ = row stride of the band, bw = stored band (-1: sparse leaf)
-      M.a = K.d_off[l]; M.ld = K.ld(l); M.nfact = K.nl(l); M.rows = K.nl(l) + K.nc(l) + 1; M.npos = M.nfact;
-      M.dinv = K.leaf_off[l]; M.pan = K.lf_w[l]; M.cpl = K.cpl_ptr[l]; M.bw = K.lf_kind[l] ? -1 : K.lf_band[l]; M.pad_ = K.lf_ldb[l];
-      continue;
-    }
-    M.a = K.d_off[l]; M.ld = K.ld(l); M.nfact = K.nl(l); M.rows = K.nl(l) + K.nc(l) + 1; M.npos = M.nfact;   // + the rhs row
-    M.dinv = K.leaf_off[l]; M.pan = pan; pan += HBM ? OMGX_PAN_SMALL(M.nfact) : OMGX_PAN_LD * M.rows; M.cpl = K.cpl_ptr[l]; M.bw = K.leaf_bw[l];
-  }
-  BMat& Mr = Ms[d.n_leaf];
-  Mr.a = ROOT_LDS ? 0 : K.d_off[d.n_leaf]; Mr.ld = 0; Mr.nfact = d.nr; Mr.rows = d.nr + 1; Mr.npos = d.n_root; Mr.dinv = -1; Mr.pan = pan0; Mr.cpl = 0; Mr.bw = d.nr;
-  Mr.pad_ = K.d_off[d.n_leaf];      // where the assembly writes the root block (Mr.a: where the factorisation reads it)
-}
-
 template <class C>
 OMGX_FN void kkt_describe(const C& c, const Dims& d, const Kkt& K, Work& w, bool sync_after = true) {
   // (one thread, a chain of table loads: the first thread of the SECOND wave, so that a caller whose next stage is serial work
@@ -1387,730 +1020,11 @@ OMGX_FN void kkt_descriptors(const C& c, const Dims& d, const Tables& T, Work& w
   }
 }
 
+}  // namespace omgx
 #ifndef OMGX_HOST_PORT
-// ---------------------------------------------------------------------------
-// Wave path (every panel of the store fits one wave, Dims::wave_ok): register-resident factorisation
-// (omgx_wave.h).  Leaf l is factorised by wave l % nwaves -- all leaves at once, no workgroup barrier inside
-// --, the Schur complements S_l = Wt Delta^{-1} Wt' are formed on the matrix pipe (16x16x4 fp64 MFMA tiles)
-// and subtracted from the root in leaf order (fixed order of the sums): by tile owners where the plan allows
-// it (Dims::schur_tiles), else by the wave that factorised the leaf, one leaf per barrier-separated round;
-// the root is factorised by wave 0.
-// ---------------------------------------------------------------------------
-OMGX_FN WPanel wpanel_leaf(const BMat& M) {
-  WPanel P; P.base = M.a; P.ld = M.ld; P.n = M.nfact; P.nreg = M.rows - 2; P.nvec = 2; P.npos = M.nfact; P.bw = M.bw;
-  P.vrow = M.rows - 2; P.band = M.bw; P.ldb = M.pad_; P.wbase = M.pan;
-  return P;
-}
-OMGX_FN WPanel wpanel_root(const BMat& M, int n_root) {
-  WPanel P; P.base = M.a; P.ld = 0; P.n = M.nfact; P.nreg = M.nfact; P.nvec = 1; P.npos = n_root; P.bw = M.nfact;
-  P.vrow = M.nfact; P.band = -1; P.ldb = 0; P.wbase = 0;
-  return P;
-}
-
-// Sparse diagonal leaf (the terminal slacks g*: every variable alone on its diagonal, coupled to one trajectory
-// coefficient and to t): arrays of n entries each -- diagonal | S coupling slots | t coupling | right-hand side.
-// Nothing to factorise; its Schur complement has one owner per target (the plan checked that no root position is
-// coupled to two of its variables), the two entries every variable shares -- (t, t) and (rhs, t) -- are wave sums.
-struct DiagLeaf { int base, n, S, dinv, dl; };
-OMGX_FN DiagLeaf diag_leaf(const BMat& M) {
-  DiagLeaf L;
-  L.base = __builtin_amdgcn_readfirstlane(M.a); L.n = __builtin_amdgcn_readfirstlane(M.nfact);
-  L.S = __builtin_amdgcn_readfirstlane(M.pan); L.dinv = __builtin_amdgcn_readfirstlane(M.dinv); L.dl = 4 * L.dinv;
-  return L;
-}
-// slot s of variable j of the diagonal leaf: the root position it is coupled to (-1: none).  From the LDS copy of the table
-// behind the descriptors where the plan put one (Dims::schur_tiles), from the global table otherwise.
-OMGX_FN int diag_leaf_pos(const Dims& d, const Kkt& K, const Work& w, const DiagLeaf& L, int s, int j) {
-  if (d.schur_tiles) return ((const int32_t*)w.col)[d.schur_dl + s * L.n + j];
-  return K.dl_pos[L.dl + s * L.n + j];
-}
-// entry i of the coupling index list of a banded leaf (BMat::cpl): of the one row every banded leaf has, in LDS, or of the global table
-OMGX_FN int leaf_cpl_at(const Dims& d, const Kkt& K, const Work& w, int cpl, int i) {
-  if (d.schur_tiles) return ((const int32_t*)w.col)[d.schur_row + i];
-  return K.cpl_idx[__builtin_amdgcn_readfirstlane(cpl) + i];
-}
-
-// Schur complement of the sparse diagonal leaf: lane j owns variable j.  v_0 .. v_{S-1} at root positions p_0 .. p_{S-1},
-// v_t at the position of t (n_root - 1), the right-hand side r_j at row nr of the root.  load() reads the leaf (and forms
-// the two wave sums every variable shares), apply() subtracts from the root: a caller may put a barrier between them.
-struct DiagSchur {
-  double vs[4], di, vt, rj, stt, srt;
-  int ps[4], S;
-  bool on;
-  template <class C>
-  OMGX_FN void load(const C& c, const Dims& d, const Kkt& K, const Work& w, const BMat& M) {
-    const DiagLeaf L = diag_leaf(M);
-    const int lane = c.lane(), j = lane < L.n ? lane : 0;
-    on = lane < L.n; S = L.S;
-    const double* A = w.kkt + L.base + j;
-    di = w.dinv[L.dinv + j];
-    vt = A[(1 + L.S) * L.n]; rj = A[(2 + L.S) * L.n];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const bool has = s < L.S;
-      ps[s] = has ? diag_leaf_pos(d, K, w, L, s, j) : -1;
-      const double v = A[(1 + (has ? s : 0)) * L.n];
-      vs[s] = (has && on && ps[s] >= 0) ? v : 0.0;
-    }
-    // shared targets: fixed-order wave sums
-    stt = c.wave_sum(on ? vt * di * vt : 0.0); srt = c.wave_sum(on ? rj * di * vt : 0.0);
-  }
-  template <class C>
-  OMGX_FN void apply(const C& c, const Dims& d, double* R) const {
-    const int pt = d.n_root - 1;
-    if (on) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        if (ps[s] < 0 || s >= S) continue;
-        const double u = vs[s] * di;
-#pragma unroll
-        for (int s2 = 0; s2 <= s; ++s2) {
-          if (ps[s2] < 0) continue;
-          const int pa = ps[s] > ps[s2] ? ps[s] : ps[s2], pb = ps[s] > ps[s2] ? ps[s2] : ps[s];
-          R[tri(pa, pb)] -= u * vs[s2];
-        }
-        R[tri(pt, ps[s])] -= u * vt;                  // (t is the last root variable: pt > every p_s)
-        R[tri(d.nr, ps[s])] -= u * rj;
-      }
-    }
-    if (c.lane() == 0) { R[tri(pt, pt)] -= stt; R[tri(d.nr, pt)] -= srt; }
-  }
-};
-
-// One tile of the Schur complements S_l = W_l D_l^-1 W_l' of CNT banded leaves (descriptors Ms[0 .. CNT-1]), formed side by side on
-// the matrix pipe -- rows ra of W_l against rows cb, four columns j0 .. j0+3 of the leaf per MFMA, a zero accumulator per leaf: per
-// entry the products and the j0 order of the round form in kkt_factor_wave -- and subtracted from r in leaf order.
-// No branch inside the loops, so the loads of the CNT leaves go out together, and the operands of the next four columns are
-// requested before the MFMAs of these four (the loads clamp their index: the request behind the last columns is harmless).
-// Whole blocks of four columns need no predicate; behind the end of a leaf (its order is no multiple of four, or it is shorter
-// than the longest of the group) both operands are zero as in the round form (acc + 0 * 0: the same bits).  Rows at or beyond
-// nc1 read the last row instead of zeros: entry (a, b) of a tile is a sum over row a and row b alone, and the caller never stores
-// such a row.
-template <int CNT>
-OMGX_FN void schur_tile_group(const Work& w, const BMat* Ms, int ra, int cb, int nc1, int q, double (&r)[4]) {
-  typedef double v4d __attribute__((ext_vector_type(4)));
-  const int rac = ra < nc1 ? ra : nc1 - 1, cbc = cb < nc1 ? cb : nc1 - 1;
-  v4d acc[CNT];
-  int n[CNT], ao[CNT], bo[CNT], dv[CNT], nmax = 0, nfull = OMGX_WAVE_ROWS;
-#pragma unroll
-  for (int k = 0; k < CNT; ++k) {
-    const int ld = __builtin_amdgcn_readfirstlane(Ms[k].ld), wo = __builtin_amdgcn_readfirstlane(Ms[k].pan);
-    acc[k] = (v4d){0.0, 0.0, 0.0, 0.0};
-    n[k] = __builtin_amdgcn_readfirstlane(Ms[k].nfact); dv[k] = __builtin_amdgcn_readfirstlane(Ms[k].dinv);
-    ao[k] = wo + rac * ld; bo[k] = wo + cbc * ld;
-    nmax = n[k] > nmax ? n[k] : nmax; nfull = (n[k] & ~3) < nfull ? (n[k] & ~3) : nfull;
-  }
-  double wa[CNT], wb[CNT], dj[CNT];
-  auto request = [&](int j) {
-#pragma unroll
-    for (int k = 0; k < CNT; ++k) {
-      const int jc = j < n[k] ? j : n[k] - 1;
-      wa[k] = w.kkt[ao[k] + jc]; wb[k] = w.kkt[bo[k] + jc]; dj[k] = w.dinv[dv[k] + jc];       // unconditional loads
-    }
-  };
-  request(q);
-  int j0 = 0;
-  for (; j0 < nfull; j0 += 4) {
-    double a[CNT], b[CNT];
-#pragma unroll
-    for (int k = 0; k < CNT; ++k) { a[k] = wa[k] * dj[k]; b[k] = wb[k]; }
-    request(j0 + 4 + q);
-#pragma unroll
-    for (int k = 0; k < CNT; ++k) acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[k], b[k], acc[k], 0, 0, 0);
-  }
-  for (; j0 < nmax; j0 += 4) {
-    const int j = j0 + q;
-    double a[CNT], b[CNT];
-#pragma unroll
-    for (int k = 0; k < CNT; ++k) { const bool in = j < n[k]; a[k] = (in ? wa[k] : 0.0) * dj[k]; b[k] = in ? wb[k] : 0.0; }
-    request(j + 4);
-#pragma unroll
-    for (int k = 0; k < CNT; ++k) acc[k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[k], b[k], acc[k], 0, 0, 0);
-  }
-#pragma unroll
-  for (int k = 0; k < CNT; ++k) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] -= acc[k][i];
-  }
-}
-
-// The Schur phase of kkt_factor_wave: the leaves are factorised (Wt = B L^-T in their carried rows, inverse pivots in w.dinv), the
-// packed root R -= sum_l S_l.  Every wave of the workgroup calls it and passes the same number of barriers whichever form
-// runs; the last statement of either form is a barrier.  ts0_ / tm_: wave 0's clock at the start of the phase and its cycles
-// up to the end of its MFMA loops (profiling build; dead otherwise).  A routine of its own so that tools/micro/schur_tiles.hip
-// can run the two forms against each other.
-template <class C>
-OMGX_FN void kkt_schur_wave(const C& c, const Dims& d, const Kkt& K, Work& w, [[maybe_unused]] long long ts0_, [[maybe_unused]] long long& tm_) {
-  typedef double v4d __attribute__((ext_vector_type(4)));
-  const BMat* Ms = (const BMat*)w.col;
-  const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
-  double* R = K.R();
-  if (d.schur_tiles && nw >= 3) {
-    // Tile owners: the banded leaves (0 .. nb-1, in front of the diagonal leaf) all couple to the same root positions in the same
-    // order, so tile (row block, column block) of every S_l lands on the same root entries.  Wave T = 0, 1, 2 owns tile (0,0),
-    // (1,0), (1,1): it forms that tile for every leaf (the statements and the j0 order of the round form below, a zero
-    // accumulator per leaf, three leaves in flight) and subtracts them in leaf order from a register copy of its root entries
-    // -- per root entry the operands and the order of the round form, hence its bits -- and stores once.  Then the diagonal
-    // leaf, read by its wave while the tiles are formed.  Two barriers, whatever the wave and whatever it had to do.
-    const int nb = d.schur_tiles;
-    const int32_t* si = (const int32_t*)w.col + d.schur_row;
-    const int nc1 = __builtin_amdgcn_readfirstlane(Ms[0].rows) - __builtin_amdgcn_readfirstlane(Ms[0].nfact);      // coupling rows + the right-hand-side row (last)
-    if (wave == 0 || (wave < 3 && nc1 > 16)) {
-      const int rb = wave >= 1 ? 16 : 0, kb = wave == 2 ? 16 : 0;
-      const int cb = kb + (lane & 15), ci_b = si[cb < nc1 - 1 ? cb : 0];
-      int ad[4]; bool ok[4]; double r[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int ca = rb + (lane >> 4) + 4 * i;
-        const int ci_a = ca < nc1 - 1 ? si[ca] : d.nr;
-        ok[i] = ca < nc1 && cb < nc1 - 1 && (rb != kb || cb <= ca);
-        ad[i] = ok[i] ? tri(ci_a, ci_b) : 0;
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) r[i] = R[ad[i]];
-      const int ra = rb + (lane & 15), q = lane >> 4;
-      for (int l0 = 0; l0 < nb; l0 += 3) {
-        const int cnt = nb - l0;
-        if (cnt >= 3) schur_tile_group<3>(w, Ms + l0, ra, cb, nc1, q, r);
-        else if (cnt == 2) schur_tile_group<2>(w, Ms + l0, ra, cb, nc1, q, r);
-        else schur_tile_group<1>(w, Ms + l0, ra, cb, nc1, q, r);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) if (ok[i]) R[ad[i]] = r[i];
-    }
-#ifdef OMGX_PROFILE
-    tm_ = clock64() - ts0_;
+#include "omgx_kkt_wave.h"      // the linear solve of the wave path (device only)
 #endif
-    const int dw = nw > 3 ? 3 : 0;
-    const bool diag = nb < d.n_leaf && wave == dw;
-    DiagSchur D;
-    if (diag) D.load(c, d, K, w, Ms[nb]);
-    c.sync();
-    if (diag) D.apply(c, d, R);
-    c.sync();
-  } else for (int base = 0; base < d.n_leaf; base += nw) {      // the round form
-    const int l = base + wave;
-#ifdef OMGX_PROFILE
-    const long long tb_ = clock64();
-#endif
-    v4d acc00 = {0.0, 0.0, 0.0, 0.0}, acc10 = acc00, acc11 = acc00;
-    int nc1 = 0, ci_b0 = 0, ci_b1 = 0, ci_a[8];
-    bool sparse = false;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ci_a[i] = 0;
-    if (l < d.n_leaf) {
-      const BMat M = Ms[l];
-      sparse = __builtin_amdgcn_readfirstlane(M.bw) < 0;
-      if (!sparse) {
-      const int n = __builtin_amdgcn_readfirstlane(M.nfact), ld = __builtin_amdgcn_readfirstlane(M.ld);
-      nc1 = __builtin_amdgcn_readfirstlane(M.rows) - n;            // coupling rows + the right-hand-side row (last)
-      const double* Wt = w.kkt + __builtin_amdgcn_readfirstlane(M.pan);
-      const double* di = w.dinv + __builtin_amdgcn_readfirstlane(M.dinv);
-      // root positions of this lane's rows / columns (global table, or its LDS copy: requested before the MFMA loop)
-      const int cb0 = lane & 15, cb1 = 16 + (lane & 15);
-      ci_b0 = leaf_cpl_at(d, K, w, M.cpl, cb0 < nc1 - 1 ? cb0 : 0); ci_b1 = leaf_cpl_at(d, K, w, M.cpl, cb1 < nc1 - 1 ? cb1 : 0);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int ca = 16 * (i >> 2) + (lane >> 4) + 4 * (i & 3);
-        ci_a[i] = ca < nc1 - 1 ? leaf_cpl_at(d, K, w, M.cpl, ca) : d.nr;
-      }
-      const int r0 = lane & 15, r1 = 16 + (lane & 15), q = lane >> 4;
-      const int r0c = r0 < nc1 ? r0 : nc1 - 1, r1c = r1 < nc1 ? r1 : nc1 - 1;
-      const bool two = nc1 > 16;
-      for (int j0 = 0; j0 < n; j0 += 4) {
-        const int j = j0 + q, jc = j < n ? j : n - 1;
-        const double w0 = Wt[r0c * ld + jc], w1 = Wt[r1c * ld + jc], dj = di[jc];       // unconditional loads
-        const double b0 = (r0 < nc1 && j < n) ? w0 : 0.0, b1 = (r1 < nc1 && j < n) ? w1 : 0.0;
-        acc00 = __builtin_amdgcn_mfma_f64_16x16x4f64(b0 * dj, b0, acc00, 0, 0, 0);
-        if (two) {
-          acc10 = __builtin_amdgcn_mfma_f64_16x16x4f64(b1 * dj, b0, acc10, 0, 0, 0);
-          acc11 = __builtin_amdgcn_mfma_f64_16x16x4f64(b1 * dj, b1, acc11, 0, 0, 0);
-        }
-      }
-      }
-    }
-#ifdef OMGX_PROFILE
-    tm_ += clock64() - tb_;
-#endif
-    // subtract from the root, one leaf per round
-    const int lend = base + nw < d.n_leaf ? base + nw : d.n_leaf;
-    for (int lr = base; lr < lend; ++lr) {
-      if (l == lr && !sparse) {
-        const int cb0 = lane & 15, cb1 = 16 + (lane & 15);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int ca0 = (lane >> 4) + 4 * i, ca1 = 16 + ca0;
-          if (ca0 < nc1 && cb0 < nc1 - 1 && cb0 <= ca0) R[tri(ci_a[i], ci_b0)] -= acc00[i];
-          if (ca1 < nc1 && cb0 < nc1 - 1) R[tri(ci_a[4 + i], ci_b0)] -= acc10[i];
-          if (ca1 < nc1 && cb1 < nc1 - 1 && cb1 <= ca1) R[tri(ci_a[4 + i], ci_b1)] -= acc11[i];
-        }
-      } else if (l == lr) {
-        DiagSchur D;
-        D.load(c, d, K, w, Ms[l]);
-        D.apply(c, d, R);
-      }
-      c.sync();
-    }
-  }
-}
-
-// One bit from any wave to every wave: a slot of the reduction scratch per wave and the barrier the caller needs anyway, instead
-// of a reduction of doubles (c.rmax: a DPP ladder in every wave, two barriers).  `flag`: any lane of the wave may raise it.  A
-// caller that goes on to write c.red without another barrier in between has to put one there (the readers of this exchange).
-template <class C>
-OMGX_FN int wave_flags_any(const C& c, int flag) {
-  const int mine = __builtin_amdgcn_ballot_w64(flag != 0) != 0 ? 1 : 0;
-  if (c.lane() == 0) c.red[c.wave()] = mine ? 1.0 : 0.0;
-  c.sync();
-  int any = 0;
-  for (int i = 0; i < c.nwaves(); ++i) any |= c.red[i] != 0.0 ? 1 : 0;
-  return __builtin_amdgcn_readfirstlane(any);
-}
-
-// A banded leaf's share of the solve, in two parts.  load(): what does not depend on the root -- the carried right-hand side
-// L^{-1} r_l, the inverse pivot, and column `lane` of L' scaled by it (wave_bwd_load: 36 or 40 registers of doubles) -- and may
-// therefore run as soon as the leaf factors are final; finish(): the gather of the root solution from `sol`, the chain over the
-// coupling rows, the backward chain, the store.  The statements and their order are those the solve always had, whoever calls
-// the two parts when: the same bits.
-// (The coupling rows Wt[a * ld] stay in the store.  Held in registers as well -- 2 x 30 more -- the lean headline instance
-// spills 71 vector registers, 288 B of scratch for 64; held instead of the L' column they keep 48 B and measure 1.9 % below
-// this form on the bench, which is 0.7 % below the kernel as it was before this routine: profiles/solve_handoff_ab.txt.)
-struct LeafSolveOps {
-  double lt[OMGX_WAVE_COLS], acc0, dl;
-  WPanel P;
-  int nc, dv, cpl;
-  bool small;
-  template <class C>
-  OMGX_FN void load(const C& c, const Work& w, const BMat& M, int koff) {
-    const int lane = c.lane();
-    P = wpanel_uniform(wpanel_leaf(M));
-    nc = P.nreg + 1 - P.n;                               // (wave-uniform values: scalar loop bounds)
-    dv = __builtin_amdgcn_readfirstlane(M.dinv); cpl = M.cpl;
-    const int j = lane < P.n ? lane : 0;
-    acc0 = w.kkt[P.wbase + j + nc * P.ld];               // L^{-1} r_l
-    dl = w.dinv[dv + j];
-    // (the leaf instance that factorised it, kkt_factor_wave: 36 positions instead of 40 where the leaf has no more)
-    small = wave_leaf_small(P.n, P.bw);
-    if (small) wave_bwd_load<OMGX_LEAF_COLS_SMALL, true>(koff, P, dl, lt);
-    else wave_bwd_load<OMGX_WAVE_COLS, true>(koff, P, dl, lt);
-  }
-  template <class C>
-  OMGX_FN void finish(const C& c, const Dims& d, const Kkt& K, const Work& w, double* xg, double* sol) const {
-    const int lane = c.lane();
-    if (lane < nc) xg[lane] = sol[d.root_off + leaf_cpl_at(d, K, w, cpl, lane)];
-    wave_fence();
-    const double* Wt = w.kkt + P.wbase + (lane < P.n ? lane : 0);
-    double acc = acc0;
-#pragma unroll 4
-    for (int a = 0; a < nc; ++a) acc = fma(-Wt[a * P.ld], xg[a], acc);
-    const double x = small ? wave_bwd_chain<OMGX_LEAF_COLS_SMALL>(P.n, lt, acc * dl) : wave_bwd_chain<OMGX_WAVE_COLS>(P.n, lt, acc * dl);
-    if (lane < P.n) sol[dv + lane] = x;
-    wave_fence();
-  }
-};
-
-// The root block and everything behind it: wave 0 factorises the root (its Schur complements are in) and, the inertia being
-// right, substitutes it backwards at once -- the right-hand side rode through wave_ldl --; meanwhile every other wave loads
-// the operands of its first banded leaf (LeafSolveOps::load).  One barrier publishes the root solution and the inertia flag
-// (a slot of the reduction scratch) together.  Wrong inertia: 2 is returned, nothing was stored by wave_ldl and `sol` is
-// untouched -- it still holds the phase-I column the next assembly of this iteration reads.  Right inertia: no assembly of
-// this iteration can follow any more (ipm_iterate leaves its factorisation loop on 0), the leaf waves gather, run their two
-// chains and store: `sol` holds the Newton step on return, 0.
-// Who substitutes which leaf: leaf l goes to wave (l + 1) % nw -- wave 0 has the root and comes last --, and under the tile
-// rule (Dims::schur_tiles) the diagonal leaf, which has nothing to preload, to wave 0.  Only the substitution rotates: the
-// factorisation keeps l % nw.  A wave's later leaves (more leaves than waves) and wave 0's go through the same statements
-// behind the barrier.  Every wave passes the same barriers: one, a second one on either way out.
-template <class C>
-OMGX_FN int kkt_root_solve_wave(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
-  const BMat* Ms = (const BMat*)w.col;
-  const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
-  const int koff = (int)(w.kkt - omgx_lds);            // the out-of-line wave routines address the LDS by offset
-  OMGX_TIC();
-  [[maybe_unused]] long long tr_ = 0;                  // (thread 0's clock behind the root factorisation)
-  const int diag = (d.schur_tiles > 0 && d.schur_tiles < d.n_leaf) ? d.schur_tiles : -1;      // (tile rule: the last leaf)
-  const int n_rr = diag >= 0 ? diag : d.n_leaf;        // leaves dealt round-robin
-  const int l_done = 1 << 20;
-  double* xg = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1) + wave * 64;      // gathered root solution of this wave's leaf
-  int l = wave ? wave - 1 : nw - 1;
-  LeafSolveOps Q;
-  const bool pre = wave != 0 && l < n_rr && __builtin_amdgcn_readfirstlane(Ms[l < n_rr ? l : 0].bw) >= 0;
-  if (wave == 0) {
-    const WPanel P = wpanel_root(Ms[d.n_leaf], d.n_root);
-#ifdef OMGX_PROFILE
-    const long long tr0_ = clock64();
-#endif
-    // (The root on the four waves of the workgroup -- root_ldl_4w, omgx_wave.h: the same bits, 30.2 k -> 22.1 k cycles alone on a CU --
-    // was measured twice and not adopted.  Round 6, for every iteration, one launch per step: f_root drops by 3.4 k only while the
-    // agent that shares the CU loses what the three parked waves left it, 342 k -> 349 k cycles per solve
-    // (profiles/r06_micro_root_ldl.txt).  With this routine, out of line and for iterations >= 1 only -- the solves a launch of the
-    // per-step path waits for --, the leaf waves preloading behind it: +0.7 % on the default bench line against a spread of 3.6 % of
-    // the parent's own runs, lean scratch 64 -> 80 B: taken out again (profiles/solve_handoff_ab.txt section 9).)
-    const int badr = wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, false, 1>(koff, P);
-#ifdef OMGX_PROFILE
-    tr_ = clock64();
-    if (c.tid() == 0) c.prof[PH_F_SWEEP] += tr_ - tr0_;      // raw root time
-#endif
-    if (!badr) {
-      wave_fence();
-      const double dl = wave_dinv<false>(w.kkt, P);
-      const double y = w.kkt[wcarried<false>(P, P.n) + (lane < P.n ? lane : 0)];           // L^{-1} r: the carried vector row
-      const double x = wave_bwd<OMGX_WAVE_COLS, false>(koff, P, dl, y * dl);
-      if (lane < P.n) sol[d.root_off + lane] = x;
-    }
-    if (lane == 0) c.red[0] = badr ? 1.0 : 0.0;
-  } else if (pre) {
-#ifdef OMGX_PROFILE
-    const long long tp0_ = clock64();
-#endif
-    Q.load(c, w, Ms[l], koff);
-#ifdef OMGX_PROFILE
-    if (c.tid() == 64) c.prof[PH_K_PRELOAD] += clock64() - tp0_;      // the preload as wave 1 sees it
-#endif
-  }
-  c.sync();
-  const int badr = __builtin_amdgcn_readfirstlane(c.red[0] != 0.0 ? 1 : 0);
-#ifdef OMGX_PROFILE
-  // f_root: up to the end of wave 0's factorisation; k_root: its substitution and the barrier
-  { const long long now_ = clock64(); if (c.tid() == 0) { c.prof[PH_F_ROOT] += tr_ - tic_; c.prof[PH_K_ROOT] += now_ - tr_; } tic_ = now_; }
-#endif
-  if (badr) { c.sync(); return 2; }                  // 2: the leaves are fine, the root has the wrong inertia  (the barrier: c.red is free again)
-  bool have = pre;                                   // (the operands of leaf l are in Q)
-  for (;;) {                                         // the preloaded leaf, a wave's later leaves, and wave 0's
-    if (wave == 0 && diag >= 0 && l >= n_rr && l < l_done) l = diag;
-    if (!(l < d.n_leaf && (l < n_rr || wave == 0))) break;
-    if (__builtin_amdgcn_readfirstlane(Ms[l].bw) >= 0) {
-      if (!have) Q.load(c, w, Ms[l], koff);
-      have = false;
-      Q.finish(c, d, K, w, xg, sol);
-    } else {
-      // sparse diagonal leaf: x_j = (r_j - sum_s v_s x_r[p_s] - v_t x_t) / d_j
-      const DiagLeaf L = diag_leaf(Ms[l]);
-      const int j = lane < L.n ? lane : 0;
-      const double* A = w.kkt + L.base + j;
-      double acc = A[(2 + L.S) * L.n] - A[(1 + L.S) * L.n] * sol[d.root_off + d.n_root - 1];
-      for (int s = 0; s < L.S; ++s) {
-        const int ps = diag_leaf_pos(d, K, w, L, s, j);
-        acc = fma(-A[(1 + s) * L.n], sol[d.root_off + (ps < 0 ? 0 : ps)] * (ps < 0 ? 0.0 : 1.0), acc);
-      }
-      if (lane < L.n) sol[L.dinv + lane] = acc * w.dinv[L.dinv + j];
-    }
-    l = l == diag ? l_done : l + nw;
-  }
-  c.sync();
-  OMGX_TOC(PH_K_BWD);                                  // what is left behind the root: gather, two chains, store
-  return 0;
-}
-
-// Leaves, Schur complements, root -- and, the inertia being right, the Newton step in `sol` (kkt_root_solve_wave).
-template <class C>
-OMGX_FN int kkt_factor_wave(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
-  const BMat* Ms = (const BMat*)w.col;
-  const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
-  const int koff = (int)(w.kkt - omgx_lds);            // the out-of-line wave routines address the LDS by offset
-  OMGX_TIC();
-  int badl = 0;
-#ifdef OMGX_PROFILE
-  const long long tw0_ = clock64();
-#endif
-  for (int l = wave; l < d.n_leaf; l += nw) {
-    const int kind_bw = __builtin_amdgcn_readfirstlane(Ms[l].bw);
-    if (kind_bw < 0) {
-      const DiagLeaf L = diag_leaf(Ms[l]);
-      const double dj = w.kkt[L.base + (lane < L.n ? lane : 0)];
-      if (lane < L.n) { w.dinv[L.dinv + lane] = rcp_pivot(dj); if (!(dj > 0.0)) badl = 1; }
-      continue;
-    }
-    const WPanel P = wpanel_leaf(Ms[l]);
-    // hyperplane leaves are banded (half bandwidth 5 in reverse Cuthill-McKee order): the instance of 36 columns and band 5
-    // where the leaf fits it, a compile-time band of 8 on 40 columns for the other banded ones
-    const int leaf_n = __builtin_amdgcn_readfirstlane(Ms[l].nfact);
-    if (wave_leaf_small(leaf_n, kind_bw)) badl |= wave_ldl<OMGX_LEAF_COLS_SMALL, OMGX_LEAF_BW_SMALL, true, 2>(koff, P);
-    else badl |= (kind_bw <= 8) ? wave_ldl<OMGX_WAVE_COLS, 8, true, 2>(koff, P) : wave_ldl<OMGX_WAVE_COLS, OMGX_WAVE_COLS, true, 2>(koff, P);
-    wave_fence();
-    const double dl = wave_dinv<true>(w.kkt, P);
-    if (lane < P.n) w.dinv[Ms[l].dinv + lane] = dl;
-  }
-#ifdef OMGX_PROFILE
-  if (c.tid() == 0) { c.prof[PH_F_SCALE] += clock64() - tw0_; c.prof[PH_F_PARK] += 1; }      // raw leaf time of wave 0, number of factorisations
-#endif
-  if (wave_flags_any(c, badl)) { c.sync(); return 1; }       // (its barrier: the panels and inverse pivots are visible)
-  OMGX_TOC(PH_F_LEAF);
-  [[maybe_unused]] long long ts0_ = 0, tm_ = 0;      // (wave 0's own clock: start of the Schur phase, cycles up to the end of its MFMA loops)
-#ifdef OMGX_PROFILE
-  ts0_ = clock64();
-#endif
-  kkt_schur_wave(c, d, K, w, ts0_, tm_);
-  OMGX_TOC(PH_F_SCHUR);
-#ifdef OMGX_PROFILE
-  // (the split of f_schur by wave 0's clock: up to the end of its MFMA loops, and the rest -- subtraction and barriers)
-  if (c.tid() == 0) { c.prof[PH_F_SCHUR_MFMA] += tm_; c.prof[PH_F_SCHUR_SUB] += tic_ - ts0_ - tm_; }
-#endif
-  return kkt_root_solve_wave(c, d, K, w, sol);
-}
-
-// One more solve with the factors kkt_factor_wave left in the store (the factorisation carries the right-hand side of the
-// Newton system along; a second-order correction solves once more with the same factors).  In: the raw right-hand side
-// where kkt_rhs writes it (last carried row of every leaf, row nr of the root).  Leaf waves substitute forwards in
-// registers (wave_fwd_r) and form their share W Delta^{-1} y of the root's right-hand side; wave 0 subtracts the shares in
-// leaf order (fixed order of the sums), substitutes the root forwards and backwards; the leaves finish as in
-// kkt_root_solve_wave.  out [N]: the solution in position order (the equality multipliers of this solve are dropped).
-template <class C>
-OMGX_FN void kkt_solve2_wave(const C& c, const Dims& d, const Kkt& K, Work& w, double* out, bool with_y = false) {
-  const BMat* Ms = (const BMat*)w.col;
-  const int lane = c.lane(), wave = c.wave(), nw = c.nwaves();
-  const int koff = (int)(w.kkt - omgx_lds);
-  double* xg0 = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1);
-  double* R = K.R();
-  const int rrow = tri(d.nr, 0);
-  for (int base = 0; base < d.n_leaf; base += nw) {
-    const int l = base + wave;
-    double* xg = xg0 + wave * 64;
-    if (l < d.n_leaf && __builtin_amdgcn_readfirstlane(Ms[l].bw) >= 0) {
-      const BMat M = Ms[l];
-      const WPanel P = wpanel_uniform(wpanel_leaf(M));
-      const int n = P.n, nc = P.nreg + 1 - P.n, ld = P.ld;
-      const int j = lane < n ? lane : 0;
-      double* Wt = w.kkt + P.wbase;
-      const int dv = __builtin_amdgcn_readfirstlane(M.dinv);
-      const double dl = w.dinv[dv + j];
-      const double y = wave_fwd_r<true>(koff, P, dl, Wt[nc * ld + j]);
-      if (lane < n) { Wt[nc * ld + lane] = y; xg[lane] = y * dl; }
-      wave_fence();
-      // share of coupling row a: sum_j W_aj y_j / d_j
-      const int a = lane < nc ? lane : 0;
-      double acc = 0.0;
-#pragma unroll 4
-      for (int q = 0; q < n; ++q) acc = fma(Wt[a * ld + q], xg[q], acc);
-      wave_fence();
-      if (lane < nc) xg[lane] = acc;
-    }
-    c.sync();
-    if (wave == 0) {
-      const int lend = base + nw < d.n_leaf ? base + nw : d.n_leaf;
-      for (int lr = base; lr < lend; ++lr) {
-        const BMat M = Ms[lr];
-        if (__builtin_amdgcn_readfirstlane(M.bw) >= 0) {
-          const int nc = __builtin_amdgcn_readfirstlane(M.rows) - 1 - __builtin_amdgcn_readfirstlane(M.nfact);
-          const double* xs = xg0 + (lr - base) * 64;
-          if (lane < nc) R[rrow + leaf_cpl_at(d, K, w, M.cpl, lane)] -= xs[lane];
-        } else {
-          // sparse diagonal leaf: y = r; lane j owns variable j and the root positions it is coupled to
-          const DiagLeaf L = diag_leaf(M);
-          const int j = lane < L.n ? lane : 0;
-          const bool on = lane < L.n;
-          const double* A = w.kkt + L.base + j;
-          const double u = A[(2 + L.S) * L.n] * w.dinv[L.dinv + j];
-          for (int s = 0; s < L.S; ++s) {
-            const int ps = diag_leaf_pos(d, K, w, L, s, j);
-            if (on && ps >= 0) R[rrow + ps] -= A[(1 + s) * L.n] * u;
-          }
-          const double st = c.wave_sum(on ? A[(1 + L.S) * L.n] * u : 0.0);
-          if (lane == 0) R[rrow + d.n_root - 1] -= st;
-        }
-        wave_fence();
-      }
-    }
-    c.sync();
-  }
-  if (wave == 0) {
-    const WPanel P = wpanel_root(Ms[d.n_leaf], d.n_root);
-    const double dl = wave_dinv<false>(w.kkt, P);
-    const int j = lane < P.n ? lane : 0;
-    const double y = wave_fwd_r<false>(koff, P, dl, w.kkt[wcarried<false>(P, P.n) + j]);
-    const double x = wave_bwd_r<false>(koff, P, dl, y * dl);
-    if (lane < (with_y ? P.n : d.n_root)) out[d.root_off + lane] = x;      // (with_y: the equality multipliers behind the N positions)
-  }
-  c.sync();
-  double* xg = xg0 + wave * 64;
-  for (int l = wave; l < d.n_leaf; l += nw) {
-    const BMat M = Ms[l];
-    if (__builtin_amdgcn_readfirstlane(M.bw) < 0) {
-      const DiagLeaf L = diag_leaf(M);
-      const int j = lane < L.n ? lane : 0;
-      const double* A = w.kkt + L.base + j;
-      double acc = A[(2 + L.S) * L.n] - A[(1 + L.S) * L.n] * out[d.root_off + d.n_root - 1];
-      for (int s = 0; s < L.S; ++s) {
-        const int ps = diag_leaf_pos(d, K, w, L, s, j);
-        acc = fma(-A[(1 + s) * L.n], out[d.root_off + (ps < 0 ? 0 : ps)] * (ps < 0 ? 0.0 : 1.0), acc);
-      }
-      if (lane < L.n) out[L.dinv + lane] = acc * w.dinv[L.dinv + j];
-      continue;
-    }
-    const WPanel P = wpanel_uniform(wpanel_leaf(M));
-    const int n = P.n, nc = P.nreg + 1 - P.n, ld = P.ld;
-    if (lane < nc) xg[lane] = out[d.root_off + leaf_cpl_at(d, K, w, M.cpl, lane)];
-    wave_fence();
-    const int j = lane < n ? lane : 0;
-    const double* Wt = w.kkt + P.wbase + j;
-    double acc = Wt[nc * ld];
-#pragma unroll 4
-    for (int a = 0; a < nc; ++a) acc = fma(-Wt[a * ld], xg[a], acc);
-    const int dv = __builtin_amdgcn_readfirstlane(M.dinv);
-    const double dl = w.dinv[dv + j];
-    const double x = wave_bwd_r<true>(koff, P, dl, acc * dl);
-    if (lane < n) out[dv + lane] = x;
-    wave_fence();
-  }
-  c.sync();
-}
-#endif
-
-// Factorise the assembled block-arrow matrix in place.  Returns 0 if the
-// inertia is (N positive, n_eq negative), 1 otherwise.
-template <class C>
-OMGX_FN int kkt_factor(const C& c, const Dims& d, const Kkt& K, Work& w) {
-#ifndef OMGX_HOST_PORT
-  if constexpr (C::wave_only) return kkt_factor_wave(c, d, K, w, w.sol);      // (compact store, omgx_plan.h; 0: the Newton step is in w.sol)
-#endif
-  if constexpr (C::wave_only) return 1; else {
-  int bad = 0;
-  OMGX_TIC();
-  BMat* Ms = (BMat*)w.col;
-  double* stage = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1);
-  if (d.n_leaf > 0) {
-#ifdef OMGX_HOST_PORT
-    ldl_left4(c, Ms, d.n_leaf, w.kkt, w.dinv, w.col, &bad);
-#else
-    {
-      int total_rows = 0, nmax = 0; bool room = true;
-      for (int l = 0; l < d.n_leaf; ++l) {
-        total_rows += Ms[l].rows; if (Ms[l].nfact > nmax) nmax = Ms[l].nfact;
-        if (Ms[l].nfact + 30 > OMGX_PAN_LD * Ms[l].rows) room = false;     // staging behind the inverse-pivot slot
-      }
-      // a spare wave per leaf next to the row waves
-      const bool coop = room && ((total_rows + 63) >> 6) + d.n_leaf <= c.nwaves();       // (leaf panels are row-major: baddr_k<1>)
-      if constexpr (C::hbm) ldl_left4(c, Ms, d.n_leaf, w.kkt, w.dinv, w.col, &bad);     // (the small panel scratch of the spill modes has no room for the cooperative form)
-      else if (coop) ldl_left4_coop<1>(c, Ms, d.n_leaf, w.kkt, w.dinv, w.col, &bad, total_rows, nmax);
-      else ldl_left4(c, Ms, d.n_leaf, w.kkt, w.dinv, w.col, &bad);
-    }
-#endif
-#ifdef OMGX_COUNT_FACT
-    if (bad) ++omgx_dbg_cnt[0];
-#endif
-    if (bad) return 1;
-  }
-  OMGX_TOC(PH_F_LEAF);
-  // Schur complement onto the root:  R[ci[a]][ci[b]] -= sum_j Wt[a][j] Wt[b][j] / d_j
-  // (spill modes: from here on the root block lives in LDS -- the Schur updates, its factorisation and its substitutions
-  // are read-modify-write chains on a few thousand doubles; nothing reads the store's copy again)
-  if constexpr (C::root_lds) {
-    const double* Rg = K.R();
-    const int nrd = ((d.nr + 1) * (d.nr + 2)) / 2;
-    OMGX_PFOR(i, nrd) w.root[i] = Rg[i];
-    c.sync();
-  }
-  double* R = C::root_lds ? w.root : K.R();
-#ifdef OMGX_HOST_PORT
-  for (int l = 0; l < d.n_leaf; ++l) {
-    const int n = K.nl(l), nc = K.nc(l), ld = K.ld(l);
-    const double* Wt = K.P(l) + n * ld;
-    const double* di = w.dinv + K.leaf_off[l];
-    const int32_t* ci = K.cpl_idx + K.cpl_ptr[l];
-    // carried rows 0..nc-1 are coupling rows (root position ci[a]), row nc the leaf's right-hand side,
-    // which lands in the root's right-hand-side row (index nr):  r_r -= Wt D^{-1} (L^{-1} r_l)
-    for (int ai = 0; ai <= nc; ++ai) for (int ak = 0; ak <= ai && ak < nc; ++ak) {
-      double acc = 0.0;
-      for (int j = 0; j < n; ++j) acc += Wt[ai * ld + j] * Wt[ak * ld + j] * di[j];
-      R[tri(ai < nc ? ci[ai] : d.nr, ci[ak])] -= acc;
-    }
-  }
-#else
-  {
-    // S = Wt Delta^{-1} Wt' per leaf as 16x16 MFMA tiles (K swept in steps of 4), the tiles of one leaf
-    // dealt round-robin to the waves.  Different leaves add into the same root entries, so the leaves
-    // take turns (one barrier per leaf): plain read-modify-write, fixed order of the sums, no atomics.
-    const int lane = c.lane();
-    for (int l = 0; l < d.n_leaf; ++l) {
-      const BMat M = Ms[l];                       // dimensions from LDS, not from the global plan tables
-      // carried rows: nc - 1 coupling rows + the right-hand-side row (last), which maps to row nr of the root
-      const int n = M.nfact, nc = M.rows - M.nfact;
-      OMGX_PANEL_STRIDES(C, M, sr, sc);
-      const double* Wt = w.kkt + M.a + n * sr;
-      const double* di = w.dinv + M.dinv;
-      const int32_t* ci = K.cpl_idx + M.cpl;
-      const int tn = (nc + 15) >> 4, nwm = c.nwaves() - 1;
-      int tile = 0;
-      for (int ti = 0; ti < tn; ++ti) for (int tj = 0; tj <= ti; ++tj, ++tile) {
-        if ((tile & nwm) != c.wave()) continue;
-        typedef double v4d __attribute__((ext_vector_type(4)));
-        v4d acc = {0.0, 0.0, 0.0, 0.0};
-        const int ra = 16 * ti + (lane & 15), rb = 16 * tj + (lane & 15), q = lane >> 4;
-        const int rac = ra < nc ? ra : nc - 1, rbc = rb < nc ? rb : nc - 1;
-        const double* Wa = Wt + rac * sr;
-        const double* Wb = Wt + rbc * sr;
-        // eight K steps per round: their 24 loads are in flight together (in the spill modes every one of them is
-        // an L2 round trip; one step at a time the sweep over a 64-column leaf was 16 of them in a row)
-        for (int j0 = 0; j0 < n; j0 += 32) {
-          double wa[8], wb[8], wd[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int j = j0 + 4 * u + q;
-            const int jc = j < n ? j : n - 1;
-            wa[u] = Wa[jc * sc]; wd[u] = di[jc]; wb[u] = Wb[jc * sc];     // unconditional loads
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            const int j = j0 + 4 * u + q;
-            const double av = (ra < nc && j < n) ? wa[u] * wd[u] : 0.0;
-            const double bv = (rb < nc && j < n) ? wb[u] : 0.0;
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
-          }
-        }
-        const int cb = 16 * tj + (lane & 15);
-        for (int i = 0; i < 4; ++i) {
-          const int ca = 16 * ti + (lane >> 4) + 4 * i;
-          if (ca < nc && cb < nc - 1 && cb <= ca) R[tri(ca < nc - 1 ? ci[ca] : d.nr, ci[cb])] -= acc[i];
-        }
-      }
-      c.sync();
-    }
-  }
-#endif
-  c.sync();
-  OMGX_TOC(PH_F_SCHUR);
-  // the root is one matrix of a few dozen rows (a single wave): the two-phase MFMA routine spreads its
-  // trailing tiles over all waves and wins there; the leaves (several matrices, many rows) are faster
-  // with the one-barrier left-looking sweep
-  // (the cooperative routine was tried for the root as well -- one row wave + one block wave: 31 k against
-  // 43 k cycles standalone, but 1.5 % slower inside the fused kernel in an A/B of three bench runs each)
-#ifdef OMGX_HOST_PORT
-  // the host twin of "a failed root factorisation leaves the store untouched" (kkt_refactor_root): keep a copy
-  if (d.wave_ok) omgx_rbak.assign(R, R + ((size_t)(d.nr + 1) * (d.nr + 2)) / 2);
-#endif
-  ldl_blocked<2>(c, Ms + d.n_leaf, 1, C::root_lds ? w.root : w.kkt, w.dinv, w.col, stage, &bad);
-  OMGX_TOC(PH_F_ROOT);
-#ifdef OMGX_COUNT_FACT
-  if (bad) ++omgx_dbg_cnt[1];
-#endif
-  return bad ? 2 : 0;
-  }
-}
-
-// The root block once more after its diagonal was changed (inertia correction of the root variables only: the
-// leaf factors and the Schur complements stay).  Device: wave path only.  Host: from the copy taken before the
-// failed attempt.
-template <class C>
-OMGX_FN void kkt_root_before_retry(const C& c, const Dims& d, const Kkt& K, Work& w) {
-#ifdef OMGX_HOST_PORT
-  double* R = K.R();
-  for (size_t i = 0; i < omgx_rbak.size(); ++i) R[i] = omgx_rbak[i];
-#endif
-}
-template <class C>
-OMGX_FN int kkt_refactor_root(const C& c, const Dims& d, const Kkt& K, Work& w) {
-#ifndef OMGX_HOST_PORT
-  if constexpr (!C::wave_only) return 1;      // (never reached: the blocked instances run with Dims::wave_ok = 0)
-  else return kkt_root_solve_wave(c, d, K, w, w.sol);      // (the leaf factors stay valid and final: the leaf waves preload here too)
-#else
-  int bad = 0;
-  BMat* Ms = (BMat*)w.col;
-  double* stage = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1);
-  double* R = K.R();
-  omgx_rbak.assign(R, R + ((size_t)(d.nr + 1) * (d.nr + 2)) / 2);
-  ldl_blocked<2>(c, Ms + d.n_leaf, 1, w.kkt, w.dinv, w.col, stage, &bad);
-  return bad ? 2 : 0;
-#endif
-}
+namespace omgx {
 
 // x <- L^{-T} y for the same storage (entry (i, j) of L, i > j, multiplies x_i into row j).  With
 // `iv` (inverse pivots) the storage holds U = L D instead of L (the leaf panels after ldl_left4):
@@ -2182,12 +1096,9 @@ OMGX_FN void trsv_fwd4(const C& c, const double* A, Addr L, int n, double* y, co
 // are done: the rows hold L^{-1} r.  What is left: scale by the inverse pivots, the root's backward
 // substitution, the leaves' correction by the root solution and their backward substitutions.
 // sol: position order + equality multipliers.
+// (blocked storage: the blocked device instances and the host twin)
 template <class C>
-OMGX_FN void kkt_solve(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
-#ifndef OMGX_HOST_PORT
-  if constexpr (C::wave_only) return;      // (the factorisation that returned 0 ended in the substitutions: kkt_root_solve_wave)
-#endif
-  if constexpr (!C::wave_only) {
+OMGX_FN void kkt_solve_blocked(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
   double* yr = sol + d.root_off;
   // leaf dimensions from the matrix descriptors kkt_factor left in LDS (not from the global plan
   // tables: every look-up there is a dependent global load)
@@ -2242,7 +1153,6 @@ OMGX_FN void kkt_solve(const C& c, const Dims& d, const Kkt& K, Work& w, double*
   }
   c.sync();
   OMGX_TOC(PH_K_BWD);
-  }
 }
 
 // Right-hand side of the Newton system into the carried rows of the block-arrow store (after the
@@ -2283,91 +1193,317 @@ OMGX_FN int kkt_rhs_slot(const Dims& d, const BMat* Ms, int q) {
   else { OMGX_PANEL_STRIDES(C, M, sr, sc); return M.a + (M.rows - 1) * sr + (q - M.dinv) * sc; }
 }
 
-#ifdef OMGX_HOST_PORT
-static thread_local std::vector<double> omgx_sol2;       // output of a second solve (position order + equality multipliers)
-#endif
-// One more solve with the factors of the iteration (second-order correction): the caller wrote the right-hand side into
-// the slots of kkt_rhs; out [N] receives the solution in position order (the equality multipliers of this solve are
-// dropped).  Device: the wave routines on the wave path (Dims::wave_ok), the blocked form below otherwise; host port: plain loops
-// over the storage its blocked routines leave (leaf panels U = L D with inverse pivots aside, root L with the pivots
-// on the diagonal).
-template <class C>
-OMGX_FN void kkt_solve2(const C& c, const Dims& d, const Kkt& K, Work& w, double* out, bool with_y = false) {
+
+// ---------------------------------------------------------------------------
+// The five entry points of the linear solve: kkt_factor / kkt_refactor_root / kkt_root_before_retry / kkt_solve / kkt_solve2.
+// Three implementations stand behind them:
+//   device, wave path   kkt_factor_wave, kkt_root_solve_wave, kkt_solve2_wave                  (omgx_kkt_wave.h)
+//   device, blocked     the body of kkt_factor, kkt_solve_blocked, kkt_solve2_blocked
+//   host twin           kkt_factor_host, kkt_refactor_root_host, kkt_root_restore_host, kkt_solve2_host; kkt_solve_blocked
+// Each target has its section with its entry points, which pick among the bodies of that target (C::wave_only); no body
+// holds code of the other target.
+// ---------------------------------------------------------------------------
 #ifndef OMGX_HOST_PORT
-  if constexpr (C::wave_only) {
-    kkt_solve2_wave(c, d, K, w, out, with_y);
-  } else {
-    // Blocked storage (templates off the wave path, spill modes included): leaf right-hand sides from their carried rows into
-    // `out` (LDS), a wave per leaf substitutes forwards, the leaves subtract W Delta^-1 y from the root's right-hand side one
-    // after the other (fixed order), wave 0 substitutes the root forwards and backwards in its right-hand-side row, the leaves
-    // finish as in kkt_solve.
-    const BMat* Ms = (const BMat*)w.col;
-    const int nr = d.nr, rbase = Ms[d.n_leaf].a;
-    double* rootp = C::root_lds ? w.root : w.kkt;
-    double* rr = rootp + rbase + tri(nr, 0);
-    if constexpr (C::root_lds) { OMGX_PFOR(k, nr) rr[k] = w.kkt[Ms[d.n_leaf].pad_ + tri(nr, k)]; }
-    OMGX_PFOR(q, d.root_off) {
-      int l = 0;
-      while (q >= Ms[l].dinv + Ms[l].nfact) ++l;
-      const BMat M = Ms[l];
-      OMGX_PANEL_STRIDES(C, M, sr, sc);
-      out[q] = w.kkt[M.a + (M.rows - 1) * sr + (q - M.dinv) * sc];
-    }
-    c.sync();
-    for (int l = c.wave(); l < d.n_leaf; l += c.nwaves()) {
-      const BMat M = Ms[l];
-      const int base = M.a;
-      OMGX_PANEL_STRIDES(C, M, sr, sc);
-      trsv_fwd4(c, w.kkt, [=](int i, int j) { return base + i * sr + j * sc; }, M.nfact, out + M.dinv, w.dinv + M.dinv);
-    }
-    c.sync();
-    for (int l = 0; l < d.n_leaf; ++l) {
-      const BMat M = Ms[l];
-      const int n = M.nfact, nc = M.rows - 1 - n;
-      OMGX_PANEL_STRIDES(C, M, sr, sc);
-      const int32_t* ci = K.cpl_idx + M.cpl;
-      const double* yl = out + M.dinv;
-      const double* iv = w.dinv + M.dinv;
-      OMGX_PFOR(a, nc) {
-        const double* Pa = w.kkt + M.a + (n + a) * sr;
-        double acc = 0.0;
+// ---------------------------------------------------------------------------
+// device: the blocked storage (templates off the wave path, spill modes included) and the entry points.  The wave path is
+// omgx_kkt_wave.h.
+// ---------------------------------------------------------------------------
+// Blocked storage (templates off the wave path, spill modes included): leaf right-hand sides from their carried rows into
+// `out` (LDS), a wave per leaf substitutes forwards, the leaves subtract W Delta^-1 y from the root's right-hand side one
+// after the other (fixed order), wave 0 substitutes the root forwards and backwards in its right-hand-side row, the leaves
+// finish as in kkt_solve.
+template <class C>
+OMGX_FN void kkt_solve2_blocked(const C& c, const Dims& d, const Kkt& K, Work& w, double* out) {
+  const BMat* Ms = (const BMat*)w.col;
+  const int nr = d.nr, rbase = Ms[d.n_leaf].a;
+  double* rootp = C::root_lds ? w.root : w.kkt;
+  double* rr = rootp + rbase + tri(nr, 0);
+  if constexpr (C::root_lds) { OMGX_PFOR(k, nr) rr[k] = w.kkt[Ms[d.n_leaf].pad_ + tri(nr, k)]; }
+  OMGX_PFOR(q, d.root_off) {
+    int l = 0;
+    while (q >= Ms[l].dinv + Ms[l].nfact) ++l;
+    const BMat M = Ms[l];
+    OMGX_PANEL_STRIDES(C, M, sr, sc);
+    out[q] = w.kkt[M.a + (M.rows - 1) * sr + (q - M.dinv) * sc];
+  }
+  c.sync();
+  for (int l = c.wave(); l < d.n_leaf; l += c.nwaves()) {
+    const BMat M = Ms[l];
+    const int base = M.a;
+    OMGX_PANEL_STRIDES(C, M, sr, sc);
+    trsv_fwd4(c, w.kkt, [=](int i, int j) { return base + i * sr + j * sc; }, M.nfact, out + M.dinv, w.dinv + M.dinv);
+  }
+  c.sync();
+  for (int l = 0; l < d.n_leaf; ++l) {
+    const BMat M = Ms[l];
+    const int n = M.nfact, nc = M.rows - 1 - n;
+    OMGX_PANEL_STRIDES(C, M, sr, sc);
+    const int32_t* ci = K.cpl_idx + M.cpl;
+    const double* yl = out + M.dinv;
+    const double* iv = w.dinv + M.dinv;
+    OMGX_PFOR(a, nc) {
+      const double* Pa = w.kkt + M.a + (n + a) * sr;
+      double acc = 0.0;
 #pragma unroll 4
-        for (int j = 0; j < n; ++j) acc += Pa[j * sc] * (yl[j] * iv[j]);
-        rr[ci[a]] -= acc;
+      for (int j = 0; j < n; ++j) acc += Pa[j * sc] * (yl[j] * iv[j]);
+      rr[ci[a]] -= acc;
+    }
+    c.sync();
+  }
+  if (c.wave() == 0) trsv_fwd4(c, rootp, [=](int i, int j) { return rbase + tri(i, j); }, nr, rr);
+  c.sync();
+  OMGX_PFOR(q, d.root_off) out[q] *= w.dinv[q];
+  OMGX_PFOR(k, nr) rr[k] = rr[k] / rootp[rbase + tri(k, k)];
+  c.sync();
+  if (c.wave() == 0) trsv_bwd4(c, rootp, [=](int i, int j) { return rbase + tri(i, j); }, nr, rr);
+  c.sync();
+  OMGX_PFOR(q, d.root_off) {
+    int l = 0;
+    while (q >= Ms[l].dinv + Ms[l].nfact) ++l;
+    const BMat M = Ms[l];
+    const int n = M.nfact, nc = M.rows - 1 - M.nfact, j = q - M.dinv;
+    OMGX_PANEL_STRIDES(C, M, sr, sc);
+    const double* Pn = w.kkt + M.a + n * sr + j * sc;
+    const int32_t* ci = K.cpl_idx + M.cpl;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int a = 0; a < nc; ++a) acc += Pn[a * sr] * rr[ci[a]];
+    out[q] -= acc * w.dinv[q];
+  }
+  c.sync();
+  for (int l = c.wave(); l < d.n_leaf; l += c.nwaves()) {
+    const BMat M = Ms[l];
+    const int base = M.a;
+    OMGX_PANEL_STRIDES(C, M, sr, sc);
+    trsv_bwd4(c, w.kkt, [=](int i, int j) { return base + i * sr + j * sc; }, M.nfact, out + M.dinv, w.dinv + M.dinv);
+  }
+  OMGX_PFOR(k, d.n_root) out[d.root_off + k] = rr[k];
+  c.sync();
+}
+
+// Factorise the assembled block-arrow matrix in place.  Returns 0 if the
+// inertia is (N positive, n_eq negative), 1 otherwise.
+// (The blocked factorisation -- leaf sweep with its cooperative form, Schur complements on the matrix pipe, root -- stands in
+// the entry point itself: behind a call of its own, kkt_factor_blocked, the mode-0 blocked instances compiled to other
+// instructions at two places, profiles/core_units_isa.txt.)
+template <class C>
+OMGX_FN int kkt_factor(const C& c, const Dims& d, const Kkt& K, Work& w) {
+  if constexpr (C::wave_only) return kkt_factor_wave(c, d, K, w, w.sol);      // (compact store, omgx_plan.h; 0: the Newton step is in w.sol)
+  else {
+  int bad = 0;
+  OMGX_TIC();
+  BMat* Ms = (BMat*)w.col;
+  double* stage = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1);
+  if (d.n_leaf > 0) {
+    {
+      int total_rows = 0, nmax = 0; bool room = true;
+      for (int l = 0; l < d.n_leaf; ++l) {
+        total_rows += Ms[l].rows; if (Ms[l].nfact > nmax) nmax = Ms[l].nfact;
+        if (Ms[l].nfact + 30 > OMGX_PAN_LD * Ms[l].rows) room = false;     // staging behind the inverse-pivot slot
+      }
+      // a spare wave per leaf next to the row waves
+      const bool coop = room && ((total_rows + 63) >> 6) + d.n_leaf <= c.nwaves();       // (leaf panels are row-major: baddr_k<1>)
+      if constexpr (C::hbm) ldl_left4(c, Ms, d.n_leaf, w.kkt, w.dinv, w.col, &bad);     // (the small panel scratch of the spill modes has no room for the cooperative form)
+      else if (coop) ldl_left4_coop<1>(c, Ms, d.n_leaf, w.kkt, w.dinv, w.col, &bad, total_rows, nmax);
+      else ldl_left4(c, Ms, d.n_leaf, w.kkt, w.dinv, w.col, &bad);
+    }
+#ifdef OMGX_COUNT_FACT
+    if (bad) ++omgx_dbg_cnt[0];
+#endif
+    if (bad) return 1;
+  }
+  OMGX_TOC(PH_F_LEAF);
+  // Schur complement onto the root:  R[ci[a]][ci[b]] -= sum_j Wt[a][j] Wt[b][j] / d_j
+  // (spill modes: from here on the root block lives in LDS -- the Schur updates, its factorisation and its substitutions
+  // are read-modify-write chains on a few thousand doubles; nothing reads the store's copy again)
+  if constexpr (C::root_lds) {
+    const double* Rg = K.R();
+    const int nrd = ((d.nr + 1) * (d.nr + 2)) / 2;
+    OMGX_PFOR(i, nrd) w.root[i] = Rg[i];
+    c.sync();
+  }
+  double* R = C::root_lds ? w.root : K.R();
+  {
+    // S = Wt Delta^{-1} Wt' per leaf as 16x16 MFMA tiles (K swept in steps of 4), the tiles of one leaf
+    // dealt round-robin to the waves.  Different leaves add into the same root entries, so the leaves
+    // take turns (one barrier per leaf): plain read-modify-write, fixed order of the sums, no atomics.
+    const int lane = c.lane();
+    for (int l = 0; l < d.n_leaf; ++l) {
+      const BMat M = Ms[l];                       // dimensions from LDS, not from the global plan tables
+      // carried rows: nc - 1 coupling rows + the right-hand-side row (last), which maps to row nr of the root
+      const int n = M.nfact, nc = M.rows - M.nfact;
+      OMGX_PANEL_STRIDES(C, M, sr, sc);
+      const double* Wt = w.kkt + M.a + n * sr;
+      const double* di = w.dinv + M.dinv;
+      const int32_t* ci = K.cpl_idx + M.cpl;
+      const int tn = (nc + 15) >> 4, nwm = c.nwaves() - 1;
+      int tile = 0;
+      for (int ti = 0; ti < tn; ++ti) for (int tj = 0; tj <= ti; ++tj, ++tile) {
+        if ((tile & nwm) != c.wave()) continue;
+        typedef double v4d __attribute__((ext_vector_type(4)));
+        v4d acc = {0.0, 0.0, 0.0, 0.0};
+        const int ra = 16 * ti + (lane & 15), rb = 16 * tj + (lane & 15), q = lane >> 4;
+        const int rac = ra < nc ? ra : nc - 1, rbc = rb < nc ? rb : nc - 1;
+        const double* Wa = Wt + rac * sr;
+        const double* Wb = Wt + rbc * sr;
+        // eight K steps per round: their 24 loads are in flight together (in the spill modes every one of them is
+        // an L2 round trip; one step at a time the sweep over a 64-column leaf was 16 of them in a row)
+        for (int j0 = 0; j0 < n; j0 += 32) {
+          double wa[8], wb[8], wd[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const int j = j0 + 4 * u + q;
+            const int jc = j < n ? j : n - 1;
+            wa[u] = Wa[jc * sc]; wd[u] = di[jc]; wb[u] = Wb[jc * sc];     // unconditional loads
+          }
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const int j = j0 + 4 * u + q;
+            const double av = (ra < nc && j < n) ? wa[u] * wd[u] : 0.0;
+            const double bv = (rb < nc && j < n) ? wb[u] : 0.0;
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+          }
+        }
+        const int cb = 16 * tj + (lane & 15);
+        for (int i = 0; i < 4; ++i) {
+          const int ca = 16 * ti + (lane >> 4) + 4 * i;
+          if (ca < nc && cb < nc - 1 && cb <= ca) R[tri(ca < nc - 1 ? ci[ca] : d.nr, ci[cb])] -= acc[i];
+        }
       }
       c.sync();
     }
-    if (c.wave() == 0) trsv_fwd4(c, rootp, [=](int i, int j) { return rbase + tri(i, j); }, nr, rr);
-    c.sync();
-    OMGX_PFOR(q, d.root_off) out[q] *= w.dinv[q];
-    OMGX_PFOR(k, nr) rr[k] = rr[k] / rootp[rbase + tri(k, k)];
-    c.sync();
-    if (c.wave() == 0) trsv_bwd4(c, rootp, [=](int i, int j) { return rbase + tri(i, j); }, nr, rr);
-    c.sync();
-    OMGX_PFOR(q, d.root_off) {
-      int l = 0;
-      while (q >= Ms[l].dinv + Ms[l].nfact) ++l;
-      const BMat M = Ms[l];
-      const int n = M.nfact, nc = M.rows - 1 - M.nfact, j = q - M.dinv;
-      OMGX_PANEL_STRIDES(C, M, sr, sc);
-      const double* Pn = w.kkt + M.a + n * sr + j * sc;
-      const int32_t* ci = K.cpl_idx + M.cpl;
-      double acc = 0.0;
-#pragma unroll 4
-      for (int a = 0; a < nc; ++a) acc += Pn[a * sr] * rr[ci[a]];
-      out[q] -= acc * w.dinv[q];
-    }
-    c.sync();
-    for (int l = c.wave(); l < d.n_leaf; l += c.nwaves()) {
-      const BMat M = Ms[l];
-      const int base = M.a;
-      OMGX_PANEL_STRIDES(C, M, sr, sc);
-      trsv_bwd4(c, w.kkt, [=](int i, int j) { return base + i * sr + j * sc; }, M.nfact, out + M.dinv, w.dinv + M.dinv);
-    }
-    OMGX_PFOR(k, d.n_root) out[d.root_off + k] = rr[k];
+  }
+  c.sync();
+  OMGX_TOC(PH_F_SCHUR);
+  // the root is one matrix of a few dozen rows (a single wave): the two-phase MFMA routine spreads its
+  // trailing tiles over all waves and wins there; the leaves (several matrices, many rows) are faster
+  // with the one-barrier left-looking sweep
+  // (the cooperative routine was tried for the root as well -- one row wave + one block wave: 31 k against
+  // 43 k cycles standalone, but 1.5 % slower inside the fused kernel in an A/B of three bench runs each)
+  ldl_blocked<2>(c, Ms + d.n_leaf, 1, C::root_lds ? w.root : w.kkt, w.dinv, w.col, stage, &bad);
+  OMGX_TOC(PH_F_ROOT);
+#ifdef OMGX_COUNT_FACT
+  if (bad) ++omgx_dbg_cnt[1];
+#endif
+  return bad ? 2 : 0;
+  }
+}
+
+// The root block once more after its diagonal was changed (inertia correction of the root variables only: the
+// leaf factors and the Schur complements stay).  Device: wave path only, where a failed root factorisation leaves the store
+// untouched: nothing to do before the retry.
+template <class C>
+OMGX_FN void kkt_root_before_retry(const C& c, const Dims& d, const Kkt& K, Work& w) {
+}
+template <class C>
+OMGX_FN int kkt_refactor_root(const C& c, const Dims& d, const Kkt& K, Work& w) {
+  if constexpr (C::wave_only) return kkt_root_solve_wave(c, d, K, w, w.sol);      // (the leaf factors stay valid and final: the leaf waves preload here too)
+  else return 1;      // (never reached: the blocked instances run with Dims::wave_ok = 0)
+}
+
+// Finish the solve of K sol = rhs (kkt_solve_blocked).  Wave path: nothing is left to do, the factorisation that returned 0
+// ended in the substitutions (kkt_root_solve_wave).
+template <class C>
+OMGX_FN void kkt_solve(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
+  if constexpr (!C::wave_only) kkt_solve_blocked(c, d, K, w, sol);
+}
+
+// One more solve with the factors of the iteration (second-order correction): the caller wrote the right-hand side into
+// the slots of kkt_rhs; out [N] receives the solution in position order (the equality multipliers of this solve are
+// dropped).  Device: the wave routines on the wave path (Dims::wave_ok), the blocked form otherwise.
+template <class C>
+OMGX_FN void kkt_solve2(const C& c, const Dims& d, const Kkt& K, Work& w, double* out, bool with_y = false) {
+  if constexpr (C::wave_only) kkt_solve2_wave(c, d, K, w, out, with_y);
+  else kkt_solve2_blocked(c, d, K, w, out);
+}
+
+#else
+// ---------------------------------------------------------------------------
+// host twin: the blocked routines by one thread, plain loops for the Schur complements and the second solve.  The host twin
+// of the wave path (Dims::wave_ok) is the same algorithm plus a saved copy of the root block -- the wave path's failed root
+// factorisation leaves the store untouched, the blocked one does not.
+// ---------------------------------------------------------------------------
+struct HostTwin {
+  std::vector<double> rbak;      // root block before its factorisation (host twin of the wave path)
+  std::vector<double> sol2;      // output of a second solve (position order + equality multipliers)
+};
+static thread_local HostTwin omgx_host_twin;
+
+template <class C>
+OMGX_FN int kkt_factor_host(const C& c, const Dims& d, const Kkt& K, Work& w) {
+  int bad = 0;
+  OMGX_TIC();
+  BMat* Ms = (BMat*)w.col;
+  double* stage = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1);
+  if (d.n_leaf > 0) {
+    ldl_left4(c, Ms, d.n_leaf, w.kkt, w.dinv, w.col, &bad);
+#ifdef OMGX_COUNT_FACT
+    if (bad) ++omgx_dbg_cnt[0];
+#endif
+    if (bad) return 1;
+  }
+  OMGX_TOC(PH_F_LEAF);
+  // Schur complement onto the root:  R[ci[a]][ci[b]] -= sum_j Wt[a][j] Wt[b][j] / d_j
+  // (spill modes: from here on the root block lives in LDS -- the Schur updates, its factorisation and its substitutions
+  // are read-modify-write chains on a few thousand doubles; nothing reads the store's copy again)
+  if constexpr (C::root_lds) {
+    const double* Rg = K.R();
+    const int nrd = ((d.nr + 1) * (d.nr + 2)) / 2;
+    OMGX_PFOR(i, nrd) w.root[i] = Rg[i];
     c.sync();
   }
-#else
+  double* R = C::root_lds ? w.root : K.R();
+  for (int l = 0; l < d.n_leaf; ++l) {
+    const int n = K.nl(l), nc = K.nc(l), ld = K.ld(l);
+    const double* Wt = K.P(l) + n * ld;
+    const double* di = w.dinv + K.leaf_off[l];
+    const int32_t* ci = K.cpl_idx + K.cpl_ptr[l];
+    // carried rows 0..nc-1 are coupling rows (root position ci[a]), row nc the leaf's right-hand side,
+    // which lands in the root's right-hand-side row (index nr):  r_r -= Wt D^{-1} (L^{-1} r_l)
+    for (int ai = 0; ai <= nc; ++ai) for (int ak = 0; ak <= ai && ak < nc; ++ak) {
+      double acc = 0.0;
+      for (int j = 0; j < n; ++j) acc += Wt[ai * ld + j] * Wt[ak * ld + j] * di[j];
+      R[tri(ai < nc ? ci[ai] : d.nr, ci[ak])] -= acc;
+    }
+  }
+  c.sync();
+  OMGX_TOC(PH_F_SCHUR);
+  // the root is one matrix of a few dozen rows (a single wave): the two-phase MFMA routine spreads its
+  // trailing tiles over all waves and wins there; the leaves (several matrices, many rows) are faster
+  // with the one-barrier left-looking sweep
+  // (the cooperative routine was tried for the root as well -- one row wave + one block wave: 31 k against
+  // 43 k cycles standalone, but 1.5 % slower inside the fused kernel in an A/B of three bench runs each)
+  // the host twin of "a failed root factorisation leaves the store untouched" (kkt_refactor_root): keep a copy
+  if (d.wave_ok) omgx_host_twin.rbak.assign(R, R + ((size_t)(d.nr + 1) * (d.nr + 2)) / 2);
+  ldl_blocked<2>(c, Ms + d.n_leaf, 1, C::root_lds ? w.root : w.kkt, w.dinv, w.col, stage, &bad);
+  OMGX_TOC(PH_F_ROOT);
+#ifdef OMGX_COUNT_FACT
+  if (bad) ++omgx_dbg_cnt[1];
+#endif
+  return bad ? 2 : 0;
+}
+
+// the root block as it was before the failed attempt
+OMGX_FN void kkt_root_restore_host(const Kkt& K) {
+  double* R = K.R();
+  for (size_t i = 0; i < omgx_host_twin.rbak.size(); ++i) R[i] = omgx_host_twin.rbak[i];
+}
+
+template <class C>
+OMGX_FN int kkt_refactor_root_host(const C& c, const Dims& d, const Kkt& K, Work& w) {
+  int bad = 0;
+  BMat* Ms = (BMat*)w.col;
+  double* stage = w.col + OMGX_BMAT_DOUBLES * (OMGX_MAX_LEAF + 1);
+  double* R = K.R();
+  omgx_host_twin.rbak.assign(R, R + ((size_t)(d.nr + 1) * (d.nr + 2)) / 2);
+  ldl_blocked<2>(c, Ms + d.n_leaf, 1, w.kkt, w.dinv, w.col, stage, &bad);
+  return bad ? 2 : 0;
+}
+
+// plain loops over the storage the blocked routines leave (leaf panels U = L D with inverse pivots aside, root L with the
+// pivots on the diagonal)
+template <class C>
+OMGX_FN void kkt_solve2_host(const C& c, const Dims& d, const Kkt& K, Work& w, double* out, bool with_y) {
   const BMat* Ms = (const BMat*)w.col;
   double* R = w.kkt + Ms[d.n_leaf].a;
   const int nr = d.nr;
@@ -2394,11 +1530,34 @@ OMGX_FN void kkt_solve2(const C& c, const Dims& d, const Kkt& K, Work& w, double
     for (int j = 0; j < i; ++j) acc -= R[tri(i, j)] * R[tri(nr, j)];
     R[tri(nr, i)] = acc;
   }
-  omgx_sol2.resize((size_t)d.N + d.n_eq);
-  kkt_solve(c, d, K, w, omgx_sol2.data());
-  for (int q = 0; q < d.N + (with_y ? d.n_eq : 0); ++q) out[q] = omgx_sol2[q];
-#endif
+  omgx_host_twin.sol2.resize((size_t)d.N + d.n_eq);
+  kkt_solve_blocked(c, d, K, w, omgx_host_twin.sol2.data());
+  for (int q = 0; q < d.N + (with_y ? d.n_eq : 0); ++q) out[q] = omgx_host_twin.sol2[q];
 }
+
+// the entry points of the host twin (their contracts: at the device entry points above)
+template <class C>
+OMGX_FN int kkt_factor(const C& c, const Dims& d, const Kkt& K, Work& w) {
+  return kkt_factor_host(c, d, K, w);
+}
+template <class C>
+OMGX_FN void kkt_root_before_retry(const C& c, const Dims& d, const Kkt& K, Work& w) {
+  kkt_root_restore_host(K);
+}
+template <class C>
+OMGX_FN int kkt_refactor_root(const C& c, const Dims& d, const Kkt& K, Work& w) {
+  return kkt_refactor_root_host(c, d, K, w);
+}
+template <class C>
+OMGX_FN void kkt_solve(const C& c, const Dims& d, const Kkt& K, Work& w, double* sol) {
+  kkt_solve_blocked(c, d, K, w, sol);
+}
+template <class C>
+OMGX_FN void kkt_solve2(const C& c, const Dims& d, const Kkt& K, Work& w, double* out, bool with_y = false) {
+  kkt_solve2_host(c, d, K, w, out, with_y);
+}
+#endif
+
 
 // Lagrangian Hessian, the share of owner bin `bin`: the items of the terms with >= 2 variables, weight w.ht[row] =
 // multiplier x signed scale (row m = objective: 1), summed per KKT address in table order and added to the store
@@ -2453,23 +1612,10 @@ OMGX_FN void hess_fix(const C& c, const Dims& d, const Tables& T, Work& w) {
   c.sync();
 }
 
+
 // ---------------------------------------------------------------------------
 // the solve
 // ---------------------------------------------------------------------------
-struct Result { int status, iters; double f, mu, t, dw; };
-
-// The reference's stop criterion of the point-mass classes on an agent's parameter vector (`problems/point2point.py:98-102` ->
-// `vehicles/holonomic.py:145-151`, `holonomic3d.py`: |state0 - poseT| <= tol and |input0| <= tol, Euclidean norms): what ends a
-// vehicle's loop in `execution/simulator.py:39-62`.  One statement for the solve kernel's stop rule and the host build's.
-OMGX_HD bool stop_criterium(const double* p, int o_state, int o_input, int o_pose, int n_dim, double tol) {
-  double e2 = 0.0, u2 = 0.0;
-  for (int k = 0; k < n_dim; ++k) {
-    const double e = p[o_state + k] - p[o_pose + k], u = p[o_input + k];
-    e2 += e * e; u2 += u * u;
-  }
-  return sqrt(e2) <= tol && sqrt(u2) <= tol;
-}
-
 // The inertia correction at which every nonlinear variable gets at least its Gershgorin row sum g_q (w.xt, position order) under
 // the cap min(dw f_q, g_q + 0.03 dw): max_q g_q / f_q, with a margin of 1 % and the smallest correction on top
 template <class C>
@@ -2483,15 +1629,12 @@ OMGX_FN double gersh_cap(const C& c, int N, const Tables& T, const Work& w, doub
   return c.uni(1.01 * c.rmax(g) + OMGX_DW_FIRST);
 }
 
-// What the setup of a solve hands to its iteration (beside the work arrays): status 1 = go on, 3 = invalid rows / start point
-struct Start { int status, warm, use_t; double mu, zt, f; };
-
 // Setup of one solve: parameter stage, Jacobian and row values at x0, row classification and gradient-based scaling, start
 // values of the multipliers and of the barrier parameter.  Runs either at the head of the solve kernel (ipm_solve) or -- for
 // a whole batch at once, many workgroups per CU -- as a kernel of its own ahead of it (ipm_prepare_kernel, omgx.hip; C::prep:
 // the row arrays and the Jacobian values then live in the agent's record in global memory, no KKT store, no descriptors):
 // the same statements in the same order either way, the same bits.
-// The absolute tolerances of a solve (Opts::compl_tol, Opts::viol_tol; 0 = off).  The lean instances (CtxT kLean) are launched only
+// The absolute tolerances of a solve (Opts::compl_tol, Opts::viol_tol; 0 = off).  The lean instances (CtxFlags lean) are launched only
 // with both off: compile-time zeros there, and everything conditioned on them folds to what it computes today with both at 0
 template <class C> OMGX_HD double opt_compl_tol(const Opts& o) { if constexpr (C::lean) return 0.0; else return o.compl_tol; }
 template <class C> OMGX_HD double opt_viol_tol(const Opts& o) { if constexpr (C::lean) return 0.0; else return o.viol_tol; }
@@ -2642,23 +1785,6 @@ OMGX_FN Start ipm_setup(const C& c, const Dims& d, const Tables& T, const Opts& 
 #endif
   res.warm = warm ? 1 : 0; res.use_t = use_t ? 1 : 0; res.mu = mu; res.zt = zt; res.f = f;
   return res;
-}
-
-// Record of a prepared solve (one per agent, global memory; written by ipm_prepare_kernel, read by the solve kernel): offsets
-// in doubles.  sc: {status, warm, use_t, mu, zt, f, -, -}; x: [N] start point (lifted auxiliaries on their rows, x[n_var] = t);
-// the row arrays; rtype bytes; the scaled Jacobian values (+ the padding slot).
-struct PrepLayout { int sc, x, slots, hv, rho, vv, z, rtype, jval, total; };
-OMGX_HD PrepLayout prep_layout(const Dims& d) {
-  PrepLayout L; int o = 0;
-  L.sc = o; o += 8;
-  L.x = o; o += d.N;
-  L.slots = o; o += d.n_slots;
-  L.hv = o; o += d.n_con; L.rho = o; o += d.n_con; L.vv = o; o += d.n_con; L.z = o; o += d.n_con;
-  L.rtype = o; o += (d.n_con + 7) / 8;
-  o = (o + 1) & ~1;                       // (the Jacobian values 16-byte aligned)
-  L.jval = o; o += d.nnz_j + 1;
-  L.total = (o + 1) & ~1;
-  return L;
 }
 
 #ifndef OMGX_HOST_PORT

@@ -11,7 +11,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/omgx.h"
-#include "omgx_core.h"
+#include "omgx_types.h"
 
 // out[b, o, k, i] = d^o/dt^o spline_k(t0[b] + i*dt); one block = (agent, 1024-sample chunk).
 //

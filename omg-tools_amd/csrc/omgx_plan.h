@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 #include "../../include/omgx.h"
-#include "omgx_core.h"
+#include "omgx_types.h"
 
 namespace omgx {
 

@@ -2,6 +2,7 @@
 // and the table of its instances per workspace mode.  Included by the three units omgx_inst_rollout_*.hip and by nothing else.
 #pragma once
 #include "omgx_device.h"
+#include "omgx_core.h"
 
 // PLANT (omgx_batch_set_plant): step (1) is the plant's predict + stop test on the travelled state, and after the solve the plant's
 // simulate takes the place of the log append; every other statement is the same one.
@@ -21,7 +22,7 @@ ipm_rollout_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles, 
   extern __shared__ __align__(16) double lds[];
   omgx::Work w;
   omgx::work_carve_split<MODE>(w, lds, MODE == omgx::WS_LDS ? nullptr : slabs + (size_t)blockIdx.x * slab_doubles, d, kkt_doubles);
-  omgx::CtxT<omgx::ws_kkt_hbm(MODE), WAVE_ONLY, omgx::ws_root_lds(MODE), GEN> c; c.red = w.red;
+  omgx::CtxT<omgx::SolveFlags<MODE, WAVE_ONLY, GEN>> c; c.red = w.red;
   c.prof = nullptr;
   __shared__ int slot_lds[2];      // (the slot queue as in the solve kernel: null when the grid covers the batch, else asked ahead)
   int slot_par = 0;

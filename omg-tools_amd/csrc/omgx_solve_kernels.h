@@ -13,9 +13,10 @@
 //                      picks per launch: LEAN exactly when the launch uses none of them.
 #pragma once
 #include "omgx_device.h"
+#include "omgx_core.h"
 
 // LEAN: the instance for launches that leave every optional feature off -- no stop rule, no fused store / signals, no ADMM centre, no
-// prepared setup, no restart pass or restart guesses, no absolute tolerances (omgx::CtxT kLean), no refinement: the plain
+// prepared setup, no restart pass or restart guesses, no absolute tolerances (omgx::CtxFlags lean), no refinement: the plain
 // receding-horizon solve of the benchmark classes.  Those blocks are compiled out (the arguments stay: one signature, one launch
 // site); omgx_batch_solve picks the instance per launch from what it is about to pass (lean_launch).  What stays is what such a
 // launch uses: order, stats, dw_state, stagger, prio_iter, warm start, the dynamic slot hand-out, bounds_shared.
@@ -39,7 +40,7 @@ ipm_solve_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, int kkt_doubles,
   omgx::Work w;
     omgx::work_carve_split<MODE>(w, lds, MODE == omgx::WS_LDS ? nullptr : slabs + (size_t)blockIdx.x * slab_doubles,
                                d, kkt_doubles);
-  omgx::CtxT<omgx::ws_kkt_hbm(MODE), WAVE_ONLY, omgx::ws_root_lds(MODE), GEN, false, REFINE, LEAN> c; c.red = w.red;
+  omgx::CtxT<omgx::SolveFlags<MODE, WAVE_ONLY, GEN, REFINE, LEAN>> c; c.red = w.red;
 #ifdef OMGX_PROFILE
   __shared__ long long prof_lds[omgx::PH_COUNT];
   c.prof = prof_lds;
@@ -227,7 +228,7 @@ ipm_prepare_kernel(omgx::Dims d, omgx::Tables T, omgx::Opts o, const double* __r
     w.hv = rec + L.hv; w.rho = rec + L.rho; w.vv = rec + L.vv; w.z = rec + L.z;
     w.rtype = (int8_t*)(rec + L.rtype); w.jval = rec + L.jval;
   }
-  omgx::CtxT<false, false, false, GEN, true> c; c.red = w.red; c.prof = nullptr;
+  omgx::CtxT<omgx::PrepareFlags<GEN>> c; c.red = w.red; c.prof = nullptr;
   const double* lbb = lb + (bounds_shared ? 0 : (size_t)b * d.n_con);
   const double* ubb = ub + (bounds_shared ? 0 : (size_t)b * d.n_con);
   const omgx::Start st = omgx::ipm_setup(c, d, T, o, w, p + (size_t)b * d.n_par, x0 + (size_t)b * d.n_var, lbb, ubb,
@@ -253,7 +254,7 @@ ipm_eval_kernel(omgx::Dims d, omgx::Tables T, int kkt_doubles, const double* __r
   omgx::Work w;
   omgx::work_carve_split<MODE>(w, lds, MODE == omgx::WS_LDS ? nullptr : slabs + (size_t)blockIdx.x * slab_doubles,
                                d, kkt_doubles);
-  omgx::CtxT<omgx::ws_kkt_hbm(MODE), WAVE_ONLY, omgx::ws_root_lds(MODE), GEN> c; c.red = w.red; c.prof = nullptr;
+  omgx::CtxT<omgx::SolveFlags<MODE, WAVE_ONLY, GEN>> c; c.red = w.red; c.prof = nullptr;
   const size_t stride = (size_t)d.n_con + 1 + d.nnz_j + kkt_doubles;
   for (int b = blockIdx.x; b < n_agents; b += gridDim.x) {
     double* o = out + (size_t)b * stride;

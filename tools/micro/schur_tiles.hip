@@ -24,7 +24,7 @@ enum { IMG_OFF = 0, IMG_DOUBLES = 160, DINV_OFF = IMG_OFF + IMG_DOUBLES, DINV_DO
 __global__ __launch_bounds__(256) void k_schur(const double* in, double* out, long long* cyc, int reps, int total, Dims d, Kkt K,
                                                int root_off, int root_len) {
   extern __shared__ double lds[];
-  CtxT<false, true> c; c.red = lds + RED_OFF; c.prof = nullptr;
+  CtxT<WaveToolFlags> c; c.red = lds + RED_OFF; c.prof = nullptr;
   Work w; w.col = lds + IMG_OFF; w.dinv = lds + DINV_OFF; w.red = lds + RED_OFF; w.kkt = lds + KKT_OFF; w.root = nullptr;
   K.a = w.kkt;
   long long t_sum = 0, tm = 0;

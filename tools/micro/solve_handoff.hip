@@ -101,7 +101,7 @@ OMGX_FN void old_solve_wave(const C& c, const Dims& d, const Kkt& K, Work& w, do
 template <int FORM>
 __global__ __launch_bounds__(512) void k_solve(const double* in, double* out, long long* cyc, int* ret, int reps, int total, Dims d, Kkt K) {
   double* lds = omgx_lds;
-  CtxT<false, true> c; c.red = lds + RED_OFF; c.prof = nullptr;
+  CtxT<WaveToolFlags> c; c.red = lds + RED_OFF; c.prof = nullptr;
   Work w; w.col = lds + IMG_OFF; w.dinv = lds + DINV_OFF; w.red = lds + RED_OFF; w.sol = lds + SOL_OFF; w.kkt = lds + KKT_OFF; w.root = nullptr;
   K.a = w.kkt;
   long long t_sum = 0;
